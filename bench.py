@@ -3,6 +3,12 @@
 
     python bench.py --gpus N --steps K --warmup W          (stand-alone: for N > 1 it starts its own N rank processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --full                                  (+ every extra object listed below)
+    python bench.py --dump-outputs DIR                      (+ the last timed step's results as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds of one timed step); the extra objects below are null in it.  ``--full`` measures them too,
+after the headline's timed region.
 
 One "step" = one full optimisation step of the stage-2 joint BRDF + normal + visibility + light
 optimisation (forward, losses, backward, Adam + SparseAdam, scheduler) on a synthetic BEAR-shaped batch
@@ -16,7 +22,7 @@ pixels across ranks with one flat-bucket RCCL all-reduce of the gradients per st
 WEAK scaling (32768 px per GPU; the reference trains on all ~10^5 in-mask pixels of a view per step); the
 ``strong`` object on the same line times a FIXED global batch of 262144 pixels split N ways.
 
-Extra objects on the JSON line (all measured after the headline's timed region):
+Extra objects on the JSON line (--full only; all measured after the headline's timed region):
   roofline      dominant kernel (fused 256-wide visibility MLP, MFMA-bound), HIP events on the launch stream from a SECOND,
                 separately instrumented pass (the headline's timed region records nothing).  ``achieved`` / ``frac`` count the
                 flops the kernel's own algorithm needs (2 x 462,848 MAC per row: the two input-block layers are factorised into
@@ -39,6 +45,14 @@ Extra objects on the JSON line (all measured after the headline's timed region):
   allreduce_ms  average time of one gradient all-reduce of the step's bucket size (N > 1)
   stage1        BASELINE configs[1] (stage-1 BEAR train step, 4096 rays x 128 samples, 256 march steps), N = 1 only:
                 ms/step, ray-samples/s, rooflines of the chain engine, the weight-gradient GEMM and the composite
+
+--dump-outputs DIR (rank 0) writes, after the timed steps and before anything else runs, what the last timed step computed:
+  loss.<term>.npy  the loss terms TrainStep.step returns        out.<key>.npy    the model outputs it returns
+  param.<key>.npy  the parameters and light tables its optimiser update left behind
+Floating arrays as float32, masks and indices as float64.  An array of more than DUMP_MAX_ELEMS elements is written as a
+fixed sample: the elements at DUMP_MAX_ELEMS flat positions drawn with seed 0 and sorted (the same positions for the same
+shape in every run).  The inputs (weights, batch, jitter draws) depend on the arguments only, so two builds run with the
+same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -55,6 +69,37 @@ from bench_legs import (  # noqa: E402,F401  (workload constants, CPU baselines,
     PEAK_F32_MFMA_TFLOPS, PEAK_HBM_GBS, make_step, _cpu_steps, parity_check, cpu_baseline, _cpu_all_cores, cpu_worker,
     sampler_in_loop, stage1_measure, _stage1_cfg1, stage1_cpu_baseline, stage1_parity, settle_gc, time_steps,
     cfg4_case, strong_cfg4, guarded, run_cfg4_child, _free_port)
+
+DUMP_MAX_ELEMS = 1 << 18  # --dump-outputs: elements per array (1 MB in f32); larger arrays are written as a seeded sample
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path, terms, out, step):
+    """--dump-outputs: the loss terms and outputs of the last timed step and the parameters it left, as PATH/<name>.npy
+    (see the module docstring)."""
+    import numpy as np
+    import torch
+    arrays = {'loss.' + k: v for k, v in terms.items() if torch.is_tensor(v)}
+    arrays.update({'out.' + k: v for k, v in out.items() if torch.is_tensor(v)})
+    arrays.update({'param.' + k: v for k, v in step.model.state_dict().items()})
+    for name in ('light_para', 'light_inten_para'):
+        table = getattr(step, name, None)
+        if table is not None:
+            arrays['param.%s.weight' % name] = table.weight
+    host = {}
+    for name, v in sorted(arrays.items()):
+        v = v.detach()
+        v = v.float() if v.is_floating_point() else v.double()
+        if v.numel() > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_MAX_ELEMS, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(pos).to(v.device)]
+        host[name] = v.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (limit %d)' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 # ----------------------------------------------------------------------------------------------- self-launch
@@ -88,6 +133,11 @@ def main():
     ap.add_argument('--cfg4-graph', action='store_true', help='N > 1: also capture / replay HIP graphs in the strong_cfg4 diagnostic (default: its eager step only)')
     ap.add_argument('--cpu-worker', default=None, help=argparse.SUPPRESS)  # internal: one worker of the all-core CPU baseline (never touches the GPU)
     ap.add_argument('--no-cpu-all-cores', action='store_true', help='skip the all-core leg of the CPU baseline (P worker processes)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the extra objects of the line (roofline, launch count, reference_dict, bf16 experiments, sampler_in_loop, '
+                         'the other scaling mode, all-reduce, strong_cfg4, stage 1, parity, CPU baselines); the --no-* switches apply to these')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the loss terms, outputs and parameters of the last timed step as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
 
     if args.cpu_worker:
@@ -95,6 +145,9 @@ def main():
         return
     if args.gpus < 1:
         raise SystemExit('bench.py: --gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('bench.py: --steps must be >= 1 and --warmup >= 0')
+    extra = args.full and not args.no_extra
     import torch  # (device_count() does not initialise the GPU on this image: the parent stays exec-safe)
     have = torch.cuda.device_count()
     if not args.single_device and have < args.gpus:
@@ -116,7 +169,7 @@ def main():
         wall[name] = round(wall.get(name, 0.0) + now - t_mark[0], 2)
         t_mark[0] = now
     cfg4_n1 = None
-    if args.gpus == 1 and not args.no_extra and int(os.environ.get('WORLD_SIZE', '1')) == 1:
+    if args.gpus == 1 and extra and int(os.environ.get('WORLD_SIZE', '1')) == 1:
         # N = 1: the strong_cfg4 object needs a process group of its own (RCCL in a world of one rank) and captures HIP graphs
         # next to RCCL's watchdog thread -- it runs in a CHILD process, started HERE, before this process has touched the GPU
         # (nothing is ever exec'ed from a GPU-initialised process), so that nothing it does can take the headline line down
@@ -150,7 +203,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            terms, _ = step.step(inp, gt, l_slt, train_order=False)
+            terms, out = step.step(inp, gt, l_slt, train_order=False)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -160,7 +213,7 @@ def main():
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dist.all_reduce(ns, op=dist.ReduceOp.SUM)
-        return float(t.item()), int(ns.item()), terms
+        return float(t.item()), int(ns.item()), terms, out
 
     def instrumented(inp, gt, steps):
         """Per-kernel durations: HIP events around every C-ABI launch on its launch stream (hip._Prof), in a pass of its own.
@@ -208,33 +261,37 @@ def main():
     head_batch, other_batch = (weak_batch, strong_batch) if args.scaling == 'weak' else (strong_batch, weak_batch)
     inp, gt = head_batch()
     mark('imports, model, batch')
-    dt, ns_total, terms = timed(inp, gt, args.steps, args.warmup)
+    dt, ns_total, terms, out = timed(inp, gt, args.steps, args.warmup)
     mark('headline (warm-up + timed steps)')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, terms, out, step)
+        mark('dump outputs')
+    del out
     px_local = inp['uv'].shape[1]
-    events = instrumented(inp, gt, min(args.steps, 10))
-    launches = count_launches(inp, gt) if not args.no_extra else None
+    events = instrumented(inp, gt, min(args.steps, 10)) if args.full else []
+    launches = count_launches(inp, gt) if extra else None
     mark('instrumented pass + launch count')
     ref_dict = None
-    if not args.no_extra and world == 1:
+    if extra and world == 1:
         # the drop-in number: the reference's own dictionary, no 'surface_idx' -- PSNetwork.forward then builds the index list
         # from surface_mask itself (nonzero(): a host synchronisation inside the step)
         inp_ref = {k: v for k, v in inp.items() if k != 'surface_idx'}
         k3 = max(3, min(args.steps, 20))
-        dt3, ns3, _ = timed(inp_ref, gt, k3, 2)
+        dt3, ns3, _, _ = timed(inp_ref, gt, k3, 2)
         ref_dict = {'value': round(ns3 * N_LIGHTS / (dt3 / k3), 1), 'unit': 'ray-samples/s', 'ms_per_step': round(dt3 / k3 * 1e3, 3),
                     'steps': k3, 'warmup': 2, 'batch': "the reference's model_input keys only (stage2/model/renderer.py:110-125); the "
                     "surface index list is built inside the step"}
         del inp_ref
     mark('reference_dict')
     x6 = None
-    if not args.no_extra and world == 1:
+    if extra and world == 1:
         # EXPERIMENT, never the headline: the L shading rows (gradient-free: vis.detach(), renderer.py:197) on the split-bf16
         # engine -- fp32 operands as three bf16 planes, six partial products per multiply, fp32 accumulation -- which passes the
         # same elementwise oracle gate as the exact-fp32 path (tests/test_bf16_gpu.py).  Separate object, own dtype label.
         step.model.train_vis_bf16x6 = True
         try:
             k4 = max(3, min(args.steps, 30))
-            dt4, ns4, terms4 = timed(inp, gt, k4, 3)
+            dt4, ns4, terms4, _ = timed(inp, gt, k4, 3)
             ev4 = instrumented(inp, gt, 5)
             xk = [(r, a.elapsed_time(b)) for (name, r, a, b, _f) in ev4 if name == 'mlp_infer_x3']
             x6 = {'value': round(ns4 * N_LIGHTS / (dt4 / k4), 1), 'unit': 'ray-samples/s', 'ms_per_step': round(dt4 / k4 * 1e3, 3),
@@ -243,7 +300,7 @@ def main():
                   'scope': 'the L x Ns shading rows of visibility_net only (conf train.vis_bf16x6); V supervised rows, every gradient '
                            'and all other kernels: exact f32 as in the headline'}
             with hip.wgrad_precision('bf16x6'):   # + the visibility net's 256 x 256 weight gradients (V supervised rows) on the split-bf16 kernel
-                dt5, ns5, terms5 = timed(inp, gt, k4, 3)
+                dt5, ns5, terms5, _ = timed(inp, gt, k4, 3)
             x6['with_wgrad_bf16x6'] = {'value': round(ns5 * N_LIGHTS / (dt5 / k4), 1), 'ms_per_step': round(dt5 / k4 * 1e3, 3),
                                        'loss': round(float(terms5['total'].detach()), 6),
                                        'scope': 'as above + psn_gemm_tn_grouped_x3 for the 256 x 256 weight-gradient products of visibility_net'}
@@ -251,7 +308,7 @@ def main():
             with hip.wgrad_precision('bf16x3'), ops.chain_precision('bf16x3'):
                 # + the backward chains of the 256-wide networks (V supervised rows, normal / albedo nets) and the weight gradients
                 # as three bf16 partial products: every large MFMA stream of the step except the V rows' forward on the bf16 pipe
-                dt6_, ns6_, terms6_ = timed(inp, gt, k4, 3)
+                dt6_, ns6_, terms6_, _ = timed(inp, gt, k4, 3)
             x6['with_chains_wgrad_bf16x3'] = {'value': round(ns6_ * N_LIGHTS / (dt6_ / k4), 1), 'ms_per_step': round(dt6_ / k4 * 1e3, 3),
                                               'loss': round(float(terms6_['total'].detach()), 6),
                                               'scope': "shading rows bf16x6 + ops.chain_precision('bf16x3') + hip.wgrad_precision('bf16x3') "
@@ -260,7 +317,7 @@ def main():
             try:
                 with hip.wgrad_precision('bf16x3'), ops.chain_precision('bf16x3'):
                     # the shading rows through the exact engine's own kernel on split-bf16 weight stages (PSN_W_BF16X2, three products)
-                    dt7_, ns7_, terms7_ = timed(inp, gt, k4, 3)
+                    dt7_, ns7_, terms7_, _ = timed(inp, gt, k4, 3)
                     ev7 = instrumented(inp, gt, 5)
                 lk = [(r, a.elapsed_time(b)) for (name, r, a, b, _f) in ev7 if name == 'mlp_infer' and r >= 1000000]
                 x6['all_bf16x3'] = {'value': round(ns7_ * N_LIGHTS / (dt7_ / k4), 1), 'ms_per_step': round(dt7_ / k4 * 1e3, 3),
@@ -290,7 +347,7 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = ns_total * N_LIGHTS / (dt / args.steps)
     in_loop = None
-    if not args.no_extra and world == 1:
+    if extra and world == 1:
         try:
             in_loop = sampler_in_loop(device, step)
             in_loop['value_over_headline'] = round(in_loop['value'] / value, 4)
@@ -300,10 +357,10 @@ def main():
     mark('sampler_in_loop')
     other = None
     allreduce_ms = None
-    if not args.no_extra:
+    if extra:
         inp, gt = other_batch()
         k2 = max(3, min(args.steps, 10 if args.scaling == 'weak' else 20))
-        dt2, ns2, _ = timed(inp, gt, k2, 2)
+        dt2, ns2, _, _ = timed(inp, gt, k2, 2)
         other = {'scaling': 'strong' if args.scaling == 'weak' else 'weak', 'value': round(ns2 * N_LIGHTS / (dt2 / k2), 1),
                  'unit': 'ray-samples/s', 'ms_per_step': round(dt2 / k2 * 1e3, 3), 'steps': k2, 'warmup': 2,
                  'pixels_per_gpu': inp['uv'].shape[1], 'surface_pixels_total': ns2,
@@ -316,7 +373,7 @@ def main():
 
     mark('other scaling mode')
     stage1 = None
-    if world == 1 and not args.no_stage1:
+    if world == 1 and args.full and not args.no_stage1:
         del step
         torch.cuda.empty_cache()
         stage1 = stage1_measure(device)
@@ -365,7 +422,7 @@ def main():
                                 'Round 6: the workgroups visit the (light, point) row set point-tile-major (psn_mlp_block_order), so the '
                                 'per-point init table is read from the fabric once instead of once per light'}
         cpu = parity = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU oracle is timed at N = 1 only (other ranks would idle behind it)
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU oracle is timed at N = 1 only (other ranks would idle behind it)
             try:
                 parity = parity_check(device)
             except Exception as e:  # noqa: BLE001
@@ -397,7 +454,7 @@ def main():
             'stage1': stage1,
             'wall_s': wall,
         }
-    if not args.no_extra and world > 1:
+    if extra and world > 1:
         # The diagnostic object runs LAST, behind a watchdog: it captures HIP graphs around RCCL collectives on every rank, a path no
         # multi-GPU node has exercised yet -- if it does not come back, rank 0 still prints the headline line (assembled above).
         cfg4 = guarded(lambda: strong_cfg4(device, step.dp, rank, world, graph_at_n=args.cfg4_graph or os.environ.get('PSN_BENCH_CFG4_GRAPH') == '1'), line, rank)

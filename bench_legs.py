@@ -151,9 +151,10 @@ def cpu_baseline(n_pixels=4096, steps=3, all_core_workers=True):
             'single_thread': {'value': sweep.get(1), 'cores': 1, 'sample': '1024 px, min of 2 timed steps after 1 warm-up'}}
 
 
-def _cpu_all_cores(threads, nproc, n_pixels=512, steps=1, max_workers=16):
+def _cpu_all_cores(threads, nproc, n_pixels=512, steps=1, max_workers=15):
     """P worker processes x ``threads`` torch threads, all timing ``_cpu_steps(n_pixels, steps)`` concurrently (children of this
-    process that never touch the GPU: `bench.py --cpu-worker`); value = the sum of the workers' rates."""
+    process that never touch the GPU: `bench.py --cpu-worker`); value = the sum of the workers' rates.  At most 15 workers: with
+    this GPU-holding parent that is 16 processes, the most a shared node lets run next to one GPU."""
     import subprocess
     P = max(1, min(max_workers, nproc // max(threads, 1)))
     env = dict(os.environ, OMP_NUM_THREADS=str(threads), MKL_NUM_THREADS=str(threads), HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES='')
