@@ -661,14 +661,6 @@ __global__ __launch_bounds__(256, 1) void gemm_tn256_grouped_kernel(GroupedArgs 
 typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gbf16x2 __attribute__((ext_vector_type(2)));
 typedef float gfloatx2 __attribute__((ext_vector_type(2)));
-#ifndef X3_SCHED
-#define X3_SCHED 1
-#endif
-#ifndef X3_DO_MFMA   // (timing-only builds of tools/dbg: which part of a step the kernel waits for)
-#define X3_DO_MFMA 1
-#define X3_DO_STAGE 1
-#define X3_DO_FETCH 1
-#endif
 constexpr int XK = 16, X_ROW = 48, X_PLANE = T256 * X_ROW, X_OPND = 3 * X_PLANE, X_BUF = 2 * X_OPND;  // bytes
 __device__ __forceinline__ int x3g_cvt2(float a, float b) {
     gfloatx2 f;
@@ -810,9 +802,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tn256_x3_grouped_kernel(GroupedAr
     //  arrangement changes nothing and only fewer joules per product would)
 #define X3_STEP(T, S)                                       \
     {                                                       \
-        if (X3_DO_MFMA) multiply((T) & 1);                  \
-        if (X3_DO_STAGE) stage((T) + 1, ((T) + 1) & 1, ra[S], rb[S]); \
-        if (X3_DO_FETCH) fetch((T) + 3, ra[S], rb[S]);      \
+        multiply((T) & 1);                                  \
+        stage((T) + 1, ((T) + 1) & 1, ra[S], rb[S]);        \
+        fetch((T) + 3, ra[S], rb[S]);                       \
         lds_barrier();                                      \
     }
     int t = 0;

@@ -88,7 +88,8 @@ struct InferArgs {
     // (row, lane group g) holds bit 4 mt + r = (activation feature 16 mt + 4 g + r > 0); read back by PSN_ACT_RELU_BITS chains
     // through mask[l], 32 bytes per row and layer instead of the 1 KB activation row
     unsigned long long* save_bits[PSN_MLP_MAX_LAYERS];
-    int tb_lds;  // lean variant: 1 = a workgroup whose rows share one B-table row reads that init row through LDS (A/B: PSN_TB_LDS=0)    // lean variant, SRC == 0, pair row sets row = group * pm_period + point (stage 2: group = light, renderer.py:163,183-193): the
+    int tb_lds;  // lean variant: 1 = a workgroup whose rows share one B-table row reads that init row through LDS (A/B: PSN_TB_LDS=0)
+    // lean variant, SRC == 0, pair row sets row = group * pm_period + point (stage 2: group = light, renderer.py:163,183-193): the
     // workgroups visit the 64-row blocks POINT-TILE-major with the group (light) running fastest, every XCD a contiguous share of
     // that order -- the workgroups resident at one time then share a handful of point tiles, whose A-side init rows (U[Ns, 512],
     // 60 MB at 29k points) stay in the XCD's L2 instead of being streamed from the fabric once per light.  0 = row order.

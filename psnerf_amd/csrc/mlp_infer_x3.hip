@@ -19,9 +19,8 @@
 // of a layer (its three pieces in K slots 0..2 of one k-step, against the constant operand (1, 1, 1, 0, ...): exact) rides
 // with the layer's first stage.  Input block: as in the exact-fp32 engine, a layer is linear in it, so W_in [pe(x_n) | pe(l_g)]
 // + b = U[n] + V[g] with U = W_a pe(x) (one fp32 row per point) and V = W_b pe(l) + b (one per group) computed by two small
-// fp32 GEMMs on the host side; the layers that read the input block START their accumulators from U[n] + V[g] (fp32 adds,
-// the row of U prefetched under the previous layer's epilogue) and spend no MFMA on it: layer 0 is that sum alone.
-#include <cstdlib>
+// fp32 GEMMs on the host side; the layers that read the input block START their accumulators from U[n] + V[g] (fp32 adds)
+// and spend no MFMA on it: layer 0 is that sum alone.
 #include "common.h"
 
 namespace psn {
@@ -108,292 +107,8 @@ __device__ __forceinline__ void x3_split2(float a, float b, int& hi, int& mid, i
     lo = x3_cvt2(ra - x3_bf16_to_f32_lo(mid), rb - x3_bf16_to_f32_hi(mid));
 }
 
-// The six partial products of one (k-step, output tile pair): fragments a[plane][o] (o = tile of the pair), B planes
-// b[plane].  Consecutive MFMAs alternate between the two accumulators, smallest terms first.
-__device__ __forceinline__ void x3_mma_pair(floatx16& c0, floatx16& c1, const xbf16x8 (&a)[3][2], const xbf16x8& bh, const xbf16x8& bm, const xbf16x8& bl) {
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][0], bh, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][1], bh, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], bl, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], bl, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], bm, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], bm, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], bh, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], bh, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], bm, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], bm, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], bh, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], bh, c1, 0, 0, 0);
-}
-
-// One 48 KB stage = 2 k-steps against all 8 output tiles: 8 (k-step, tile pair) groups of 12 MFMAs; the 6 fragment reads of
-// group g + 1 are issued at the head of group g, this wave's LDS-DMA pieces of the next stage ride in the first groups.
-template <typename BOp, typename RequestPiece>
-__device__ __forceinline__ void x3_stage_mma(floatx16 (&acc)[8], const xbf16x8* __restrict__ wl, int lane, int n_pieces, BOp bop, RequestPiece request_piece) {
-    xbf16x8 a[2][3][2];
-    auto load_frags = [&](int grp, xbf16x8 (&f)[3][2]) __attribute__((always_inline)) {
-        const int ks = grp >> 2, p = grp & 3;
-#pragma unroll
-        for (int o = 0; o < 2; ++o)
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) f[pl][o] = wl[((ks * 8 + 2 * p + o) * 3 + pl) * 64 + lane];
-    };
-    load_frags(0, a[0]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int grp = 0; grp < 8; ++grp) {
-        const int ks = grp >> 2, p = grp & 3;
-        if (grp + 1 < 8) {
-            load_frags(grp + 1, a[(grp + 1) & 1]);
-            // the reads are ISSUED here, a whole group (12 MFMAs = 384 cycles) ahead of their use: without the region boundary
-            // the register allocator merges the two fragment sets and sinks the reads behind this group's last MFMAs, and with
-            // one wave per SIMD their latency is then exposed at the head of every group
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        x3_mma_pair(acc[2 * p], acc[2 * p + 1], a[grp & 1], bop(0, ks), bop(1, ks), bop(2, ks));
-        // the next stage's pieces go out in the first two groups: a stage lasts only 96 MFMAs = 3072 cycles, and a piece issued
-        // in its second half lands after the stage has ended (an L2 round trip is ~1500 cycles)
-        if (grp < 2) {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) request_piece(6 * grp + j);
-        } else if (grp == 2 && n_pieces > 12) { request_piece(12); request_piece(13); }  // the bias k-step of the next layer (wave-uniform)
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// OCC = false: the grouped ReLU network of stage 2 (input block through the fp32 init tables U / V, see the header comment).
-// OCC = true (psn_mlp_infer_x3_occ): the stage-1 occupancy network (stage1/model/network.py:85-101) on query points -- the
-// positional encoding is formed in the prologue with the expressions of pe_encode / mlp_infer_kernel<SRC = 2> and parked in LDS
-// (48 floats per row); layer 0 multiplies its three planes in natural K order (two 48 KB stages: k-steps 0..3, the fourth all
-// zeros); every layer starts from its bias k-step; the activation is softplus(beta = 100) (common.h softplus100_pair, the
-// exact-fp32 engine's code) before the split; the epilogue IN FRONT of the skip layer writes the encoding columns into the
-// input features >= pe_first (217 ... 255: cat[h, pe] of network.py:90, the 1 / sqrt(2) is folded into the packed weights),
-// so that layer is an ordinary 256-input layer; output = sigmoid(-10 logit), optionally scattered (out_rows) for a row count
-// that lives on the device (n_rows_dev) -- the shadow-ray path of stage1/model/rendering.py:378-408.
-template <bool OCC>
-__global__ __launch_bounds__(256, 1) void mlp_infer_x3_kernel(X3Args g) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char xsmem[];  // 2 x (48 KB stage + 8 KB bias k-step) [+ 24 KB encoding]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ln = lane & 31, lh = lane >> 5;
-    const int n_hidden = g.d.n_hidden;
-    unsigned group = 0, tile = blockIdx.x;
-    long long n_rows_eff = 0;
-    if constexpr (OCC) {
-        n_rows_eff = g.n_rows;
-        if (g.n_rows_dev != nullptr) { const long long nd = *g.n_rows_dev; n_rows_eff = nd < n_rows_eff ? nd : n_rows_eff; }
-        if ((long long)blockIdx.x * (kX3Waves * 32) >= n_rows_eff) return;  // (wave-uniform: before anything is requested)
-    } else {
-        group = blockIdx.x / g.tiles_per_group;
-        tile = blockIdx.x - group * g.tiles_per_group;
-    }
-    const unsigned init_stride = g.n_in_layers * 256u;
-    const float* vrow = OCC ? nullptr : g.V + (size_t)group * init_stride + 4 * lh;
-
-    const unsigned char* wptr = g.w;  // the NEXT stage to request
-    int in_idx = 0;                   // input layers seen so far
-    int gstage = 0;
-    // OCC = false: first stage of layer 1 (layer 0 has no weights of its own left) + that layer's bias k-step unless it reads
-    // the input block.  OCC = true: first stage of layer 0 + its bias k-step.
-    const bool l1_bias = OCC ? true : (n_hidden > 1 && g.d.has_in[1] == 0);
-    const unsigned char* first_bias = OCC ? g.bias : g.bias + kX3BiasBytes;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) x3_dma_piece(wptr, xsmem, first_bias, wave, lane, j);
-    if (l1_bias) { x3_dma_piece(wptr, xsmem, first_bias, wave, lane, 12); x3_dma_piece(wptr, xsmem, first_bias, wave, lane, 13); }
-    wptr += kX3StageBytes;
-
-    const unsigned n = tile * (unsigned)(kX3Waves * 32) + wave * 32 + ln;
-    const bool valid = OCC ? (long long)n < n_rows_eff : n < g.rows_per_group;
-    const unsigned row = OCC ? n : group * g.rows_per_group + n;
-    const float* urow = OCC ? nullptr : g.U + (size_t)(valid ? n : g.rows_per_group - 1) * init_stride + 4 * lh;
-    float* pe_row = reinterpret_cast<float*>(xsmem + 2 * kX3BufBytes) + (wave * 32 + ln) * kX3PeStride;  // OCC: this lane's row
-    if constexpr (OCC) {
-        // positional encoding of this lane's point (network.py:141-150): [p s, sin(2^f p s), cos(2^f p s)] per octave f; the
-        // two lanes of a row share the 18 (octave, coordinate) sincos pairs; expressions as compute_xin_tile (mlp_infer.hip)
-        float q[3] = {0.f, 0.f, 0.f};
-        if (valid) { q[0] = g.points[(size_t)n * 3]; q[1] = g.points[(size_t)n * 3 + 1]; q[2] = g.points[(size_t)n * 3 + 2]; }
-        const int n_pairs = 3 * g.pe_octaves, half = (n_pairs + 1) / 2;
-        for (int pi = lh * half; pi < (lh == 0 ? half : n_pairs); ++pi) {
-            const int f = pi / 3, c = pi - 3 * f;
-            const float arg = ldexpf((c == 0 ? q[0] : (c == 1 ? q[1] : q[2])) * g.pe_scale, f);
-            float sn, cs;
-            sincosf(arg, &sn, &cs);
-            pe_row[3 + 6 * f + c] = sn;
-            pe_row[3 + 6 * f + 3 + c] = cs;
-        }
-        if (lh == 0) { pe_row[0] = q[0] * g.pe_scale; pe_row[1] = q[1] * g.pe_scale; pe_row[2] = q[2] * g.pe_scale; }
-        else for (int col = 3 + 2 * n_pairs; col < kX3PeStride; ++col) pe_row[col] = 0.0f;
-        // (read back by the same wave only -- layer 0 and the epilogue in front of the skip layer --, behind the barrier of
-        //  the first stage)
-    }
-    xbf16x8 ones_b;  // K slots 0..2 (lane half 0) carry the constant 1: the three bias pieces add up exactly
-    {
-        xintx4 o = {lh == 0 ? 0x3F803F80 : 0, lh == 0 ? 0x00003F80 : 0, 0, 0};
-        ones_b = __builtin_bit_cast(xbf16x8, o);
-    }
-
-    floatx16 acc[8];
-    xbf16x8 bact[3][16];
-    // lane (n, h), tile ot, register v = 4 q + r  <->  feature 32 ot + 8 q + 4 h + r: four consecutive floats per (ot, q).
-    // acc = U[n] + V[g] (fp32).  (Requesting the U row ahead of the preceding epilogue needs 128 more registers than the
-    // 512 a wave has -- measured: scratch spills --, so its latency is exposed once per input layer: ~1 % of a pass.)
-    auto init_acc_uv = [&](int idx) __attribute__((always_inline)) {
-        const float* pu = urow + idx * 256;
-        const float* pv = vrow + idx * 256;
-#pragma unroll
-        for (int ot = 0; ot < 8; ++ot)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 u = *reinterpret_cast<const float4*>(pu + 32 * ot + 8 * q);
-                const float4 t = *reinterpret_cast<const float4*>(pv + 32 * ot + 8 * q);
-                acc[ot][4 * q] = u.x + t.x; acc[ot][4 * q + 1] = u.y + t.y; acc[ot][4 * q + 2] = u.z + t.z; acc[ot][4 * q + 3] = u.w + t.w;
-            }
-#pragma unroll
-        for (int ot = 0; ot < 8; ++ot) asm volatile("" : "+v"(acc[ot]));  // complete before the next LDS-DMA pieces are issued (asm: invisible to vmcnt)
-    };
-
-    // One stage: this wave's pieces have landed, barrier, MFMAs with the request for the next stage in their gaps.
-#define X3_STAGE(BOP, NEXT_HAS_BIAS, BSRC)                                                                   \
-    {                                                                                                        \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                     \
-        __syncthreads();                                                                                     \
-        const xbf16x8* wl = reinterpret_cast<const xbf16x8*>(xsmem + (gstage & 1) * kX3BufBytes);            \
-        unsigned char* nxt = xsmem + ((gstage + 1) & 1) * kX3BufBytes;                                       \
-        const unsigned char* bsrc_ = (BSRC);                                                                 \
-        x3_stage_mma(acc, wl, lane, (NEXT_HAS_BIAS) ? 14 : 12, BOP,                                          \
-                     [&](int j_) { x3_dma_piece(wptr, nxt, bsrc_, wave, lane, j_); });                       \
-        wptr += kX3StageBytes;                                                                               \
-        ++gstage;                                                                                            \
-    }
-    // bias of the layer whose first stage sits in LDS buffer (gstage & 1): acc = b_hi + b_mid + b_lo (exact)
-    auto init_acc_bias = [&]() __attribute__((always_inline)) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        const xbf16x8* bl = reinterpret_cast<const xbf16x8*>(xsmem + (gstage & 1) * kX3BufBytes + kX3StageBytes);
-        floatx16 zero;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) zero[i] = 0.0f;
-#pragma unroll
-        for (int ot = 0; ot < 8; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[ot * 64 + lane], ones_b, zero, 0, 0, 0);
-    };
-    // ReLU (OCC: softplus) + split of the finished accumulators into the three B-operand planes of the next layer; OCC,
-    // inject: the features >= pe_first take the row's encoding columns instead (the cat[h, pe] in front of the skip layer;
-    // pe_first >= 192, so only output tiles 6 and 7 are concerned)
-    auto epilogue = [&](bool inject) __attribute__((always_inline)) {
-#pragma unroll
-        for (int ot = 0; ot < 8; ++ot) {
-#pragma unroll
-            for (int qp = 0; qp < 2; ++qp) {
-                xintx4 oh, om, ol;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float c0, c1;
-                    if constexpr (OCC) {
-                        f32x2 sp, unused;
-                        softplus100_pair<false>(f32x2{acc[ot][8 * qp + 2 * i], acc[ot][8 * qp + 2 * i + 1]}, sp, unused);
-                        c0 = sp.x; c1 = sp.y;
-                        if (ot >= 6 && inject) {
-                            const int f0 = 32 * ot + 16 * qp + 8 * ((2 * i) >> 2) + 4 * lh + ((2 * i) & 3);  // feature of slot j = 2 i
-                            const int k0 = f0 - g.pe_first, k1 = f0 + 1 - g.pe_first;
-                            const float p0 = pe_row[k0 < 0 ? 0 : k0], p1 = pe_row[k1 < 0 ? 0 : k1];
-                            c0 = k0 >= 0 ? p0 : c0;
-                            c1 = k1 >= 0 ? p1 : c1;
-                        }
-                    } else {
-                        c0 = relu1(acc[ot][8 * qp + 2 * i]); c1 = relu1(acc[ot][8 * qp + 2 * i + 1]);
-                    }
-                    int h_, m_, l_;
-                    x3_split2(c0, c1, h_, m_, l_);
-                    oh[i] = h_; om[i] = m_; ol[i] = l_;
-                }
-                bact[0][2 * ot + qp] = __builtin_bit_cast(xbf16x8, oh);
-                bact[1][2 * ot + qp] = __builtin_bit_cast(xbf16x8, om);
-                bact[2][2 * ot + qp] = __builtin_bit_cast(xbf16x8, ol);
-            }
-        }
-    };
-
-    if constexpr (OCC) {
-        // layer 0: bias + W_0 pe(x) on the matrix pipe, natural K order: k-step ks, slot j of lane (n, h) = column 16 ks + 8 h + j
-        init_acc_bias();  // (its barrier also orders the encoding writes above against the reads below)
-        xbf16x8 bin[3][4];
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) {
-            const float4 v0 = *reinterpret_cast<const float4*>(pe_row + 16 * ks + 8 * lh), v1 = *reinterpret_cast<const float4*>(pe_row + 16 * ks + 8 * lh + 4);
-            xintx4 oh, om, ol;
-            int h_, m_, l_;
-            x3_split2(v0.x, v0.y, h_, m_, l_); oh[0] = h_; om[0] = m_; ol[0] = l_;
-            x3_split2(v0.z, v0.w, h_, m_, l_); oh[1] = h_; om[1] = m_; ol[1] = l_;
-            x3_split2(v1.x, v1.y, h_, m_, l_); oh[2] = h_; om[2] = m_; ol[2] = l_;
-            x3_split2(v1.z, v1.w, h_, m_, l_); oh[3] = h_; om[3] = m_; ol[3] = l_;
-            bin[0][ks] = __builtin_bit_cast(xbf16x8, oh); bin[1][ks] = __builtin_bit_cast(xbf16x8, om); bin[2][ks] = __builtin_bit_cast(xbf16x8, ol);
-        }
-        {
-            xintx4 z = {0, 0, 0, 0};
-            bin[0][3] = bin[1][3] = bin[2][3] = __builtin_bit_cast(xbf16x8, z);
-        }
-        X3_STAGE(([&](int pl, int ks) -> xbf16x8 { return bin[pl][ks]; }), false, g.bias)
-        X3_STAGE(([&](int pl, int ks) -> xbf16x8 { return bin[pl][2 + ks]; }), n_hidden > 1, g.bias + kX3BiasBytes)
-    } else {
-        // layer 0: U[n] + V[g] alone
-        init_acc_uv(0);
-        ++in_idx;
-    }
-    for (int li = 1; li < n_hidden; ++li) {
-        const bool has_in = !OCC && g.d.has_in[li] != 0;
-        epilogue(OCC && li == g.skip_layer);                   // of layer li - 1
-        if (has_in) { init_acc_uv(in_idx); ++in_idx; }
-        else init_acc_bias();
-        const bool next_bias = li + 1 < n_hidden && (OCC || g.d.has_in[li + 1] == 0);
-        const unsigned char* next_bsrc = g.bias + (size_t)(li + 1 < n_hidden ? li + 1 : 0) * kX3BiasBytes;
-#define X3_ACT_STAGE(S, LAST)                                                                                 \
-        X3_STAGE(([&](int pl, int ks) -> xbf16x8 { return bact[pl][2 * (S) + ks]; }), (LAST) && next_bias, next_bsrc)
-        X3_ACT_STAGE(0, false) X3_ACT_STAGE(1, false) X3_ACT_STAGE(2, false) X3_ACT_STAGE(3, false)
-        X3_ACT_STAGE(4, false) X3_ACT_STAGE(5, false) X3_ACT_STAGE(6, false) X3_ACT_STAGE(7, true)
-#undef X3_ACT_STAGE
-    }
-    epilogue(false);
-#undef X3_STAGE
-    // final layer: one output tile (n_out <= 32), 16 k-steps x 3 planes in ONE 48 KB stage; four accumulator chains
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    {
-        const xbf16x8* wl = reinterpret_cast<const xbf16x8*>(xsmem + (gstage & 1) * kX3BufBytes);
-        floatx16 f[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) f[c][i] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-            const xbf16x8 ah = wl[(ks * 3 + 0) * 64 + lane], am = wl[(ks * 3 + 1) * 64 + lane], al = wl[(ks * 3 + 2) * 64 + lane];
-            floatx16& c = f[ks & 3];
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bact[0][ks], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bact[2][ks], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bact[1][ks], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bact[0][ks], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bact[1][ks], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bact[0][ks], c, 0, 0, 0);
-        }
-        const int n_out = g.d.n_out;
-        if (valid) {
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int m = 8 * (v >> 2) + 4 * lh + (v & 3);
-                if (m < n_out) {
-                    float x = (f[0][v] + f[1][v]) + (f[2][v] + f[3][v]) + g.final_bias[m];
-                    if (g.d.out_act == PSN_OUT_SIGMOID) x = sigmoidf_(x);
-                    else if (g.d.out_act == PSN_OUT_OCC) x = sigmoidf_(x * -10.0f);
-                    const int64_t orow = (OCC && g.out_rows != nullptr) ? g.out_rows[row] : (int64_t)row;
-                    g.out[orow * n_out + m] = x;
-                }
-            }
-        }
-    }
-}
-
 // ============================================================================================================================
-// PIPELINED form (round 4): the epilogue of a layer -- activation + three-way split of 128 accumulators per lane, ~10 k cycles of
+// Pipelining (round 4): the epilogue of a layer -- activation + three-way split of 128 accumulators per lane, ~10 k cycles of
 // vector work next to 24.6 k cycles of MFMAs per layer, fully exposed with one wave per SIMD -- runs INSIDE the next layer's MFMA
 // stream.  Stage S of layer l + 1 (k-steps 2 S, 2 S + 1) consumes exactly the features of OUTPUT TILE S of layer l, so only tile
 // 0 has to be ready when the layer starts; the 8 (k-step, tile pair) groups of stage S each carry one eighth of the epilogue of
@@ -401,7 +116,7 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3_kernel(X3Args g) {
 // layer's accumulators alive while the new ones accumulate: TWO accumulator sets (256 registers) -- paid for by keeping only
 // TWO tiles of B-operand planes (48 registers instead of 192: a tile is dead once its stage has run).  The last stage of a layer
 // writes its results back into the first set (MFMA with D != C), so the layer loop carries one set and needs no copies.
-// 456 -> ~400 registers, one wave per SIMD as before.
+// ~400 registers (456 with the whole epilogue between two layers), one wave per SIMD.
 template <bool OCC>
 __device__ __forceinline__ void x3_epi_job(const floatx16& a, const int j, const int ot, const int lh, const bool inject, const float* pe_row,
                                            const int pe_first, xintx4 (&st)[3][2]) {
@@ -424,23 +139,6 @@ __device__ __forceinline__ void x3_epi_job(const floatx16& a, const int j, const
     int h_, m_, l_;
     x3_split2(c0, c1, h_, m_, l_);
     st[0][qp][i] = h_; st[1][qp][i] = m_; st[2][qp][i] = l_;
-}
-
-// x3_mma_pair whose FIRST product of each chain reads its C operand from (s0, s1) and writes (c0, c1): moves the accumulators
-__device__ __forceinline__ void x3_mma_pair_move(floatx16& c0, floatx16& c1, const floatx16& s0, const floatx16& s1, const xbf16x8 (&a)[3][2],
-                                                 const xbf16x8& bh, const xbf16x8& bm, const xbf16x8& bl) {
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][0], bh, s0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][1], bh, s1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], bl, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], bl, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], bm, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], bm, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], bh, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], bh, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], bm, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], bm, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], bh, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], bh, c1, 0, 0, 0);
 }
 
 // The epilogue of ONE accumulator pair (x3_epi_job) cut into six phases of <= 8 vector instructions (two quarter-rate
@@ -510,9 +208,12 @@ struct X3EpiPhases {
     }
 };
 
-// One stage of the pipelined form.  dst / src: the accumulators written / read (the same set, except in a layer's last stage,
-// whose first k-step moves src -> dst).  HAS_JOB: group grp carries accumulator pair grp of tile `job_ot` of the previous
-// layer (job_acc) through its six phases, one behind each pair of MFMAs (the order of the 12 products is x3_mma_pair's).
+// One 48 KB stage = 2 k-steps against all 8 output tiles: 8 (k-step, tile pair) groups of 12 MFMAs, the six partial products of
+// fragments fr[plane][o] (o = tile of the pair) against the B planes bh / bm / bl; consecutive MFMAs alternate between the two
+// accumulators, smallest terms first.  The 6 fragment reads of group g + 1 are issued at the head of group g, this wave's
+// LDS-DMA pieces of the next stage ride in the first groups.  dst / src: the accumulators written / read (the same set, except
+// in a layer's last stage, whose first k-step moves src -> dst).  HAS_JOB: group grp carries accumulator pair grp of tile
+// `job_ot` of the previous layer (job_acc) through its six phases, one behind each pair of MFMAs.
 template <bool OCC, bool MOVE, bool HAS_JOB, typename BOp, typename RequestPiece>
 __device__ __forceinline__ void x3_stage_mma_p(floatx16 (&dst)[8], floatx16 (&src)[8], const xbf16x8* __restrict__ wl, int lane, int n_pieces, BOp bop,
                                                RequestPiece request_piece, const floatx16& job_acc, const int job_ot, const int lh, const bool inject,
@@ -532,7 +233,10 @@ __device__ __forceinline__ void x3_stage_mma_p(floatx16 (&dst)[8], floatx16 (&sr
         const int ks = grp >> 2, p = grp & 3;
         if (grp + 1 < 8) {
             load_frags(grp + 1, a[(grp + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);  // (see x3_stage_mma: the reads are issued a whole group ahead of their use)
+            // the reads are ISSUED here, a whole group (12 MFMAs = 384 cycles) ahead of their use: without the region boundary
+            // the register allocator merges the two fragment sets and sinks the reads behind this group's last MFMAs, and with
+            // one wave per SIMD their latency is then exposed at the head of every group
+            __builtin_amdgcn_sched_barrier(0);
         }
         const xbf16x8 (&fr)[3][2] = a[grp & 1];
         const xbf16x8 bh = bop(0, ks), bm = bop(1, ks), bl = bop(2, ks);
@@ -545,14 +249,26 @@ __device__ __forceinline__ void x3_stage_mma_p(floatx16 (&dst)[8], floatx16 (&sr
         if constexpr (HAS_JOB) { ph.run(K, job_acc, grp, job_ot, lh, inject, pe_row, pe_first, job_st); __builtin_amdgcn_sched_barrier(0); }
         X3P_SUB(0, 2, bh) X3P_SUB(1, 0, bl) X3P_SUB(2, 1, bm) X3P_SUB(3, 1, bh) X3P_SUB(4, 0, bm) X3P_SUB(5, 0, bh)
 #undef X3P_SUB
+        // the next stage's pieces go out in the first two groups: a stage lasts only 96 MFMAs = 3072 cycles, and a piece issued
+        // in its second half lands after the stage has ended (an L2 round trip is ~1500 cycles)
         if (grp < 2) {
 #pragma unroll
             for (int j = 0; j < 6; ++j) request_piece(6 * grp + j);
-        } else if (grp == 2 && n_pieces > 12) { request_piece(12); request_piece(13); }
+        } else if (grp == 2 && n_pieces > 12) { request_piece(12); request_piece(13); }  // the bias k-step of the next layer (wave-uniform)
         __builtin_amdgcn_sched_barrier(0);
     }
 }
 
+// OCC = false: the grouped ReLU network of stage 2 (input block through the fp32 init tables U / V, see the header comment).
+// OCC = true (psn_mlp_infer_x3_occ): the stage-1 occupancy network (stage1/model/network.py:85-101) on query points -- the
+// positional encoding is formed in the prologue with the expressions of pe_encode / mlp_infer_kernel<SRC = 2> and parked in LDS
+// (48 floats per row); layer 0 multiplies its three planes in natural K order (two 48 KB stages: k-steps 0..3, the fourth all
+// zeros); every layer starts from its bias k-step; the activation is softplus(beta = 100) (common.h softplus100_pair, the
+// exact-fp32 engine's code) before the split; the epilogue IN FRONT of the skip layer writes the encoding columns into the
+// input features >= pe_first (217 ... 255: cat[h, pe] of network.py:90, the 1 / sqrt(2) is folded into the packed weights),
+// so that layer is an ordinary 256-input layer; output = sigmoid(-10 logit), optionally scattered (out_rows) for a row count
+// that lives on the device (n_rows_dev) -- the shadow-ray path of stage1/model/rendering.py:378-408.  Sweep form
+// (psn_march_sweep_x3, n_steps > 0): the rows are (ray, step) pairs and the point is formed in the prologue, see X3Args.
 template <bool OCC>
 __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char xsmem[];  // 2 x (48 KB stage + 8 KB bias k-step) [+ 24 KB encoding]
@@ -589,8 +305,10 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
     }
     const unsigned init_stride = g.n_in_layers * 256u;
     const float* vrow = OCC ? nullptr : g.V + (size_t)group * init_stride + 4 * lh;
-    const unsigned char* wptr = g.w;
-    int in_idx = 0, gstage = 0;
+    const unsigned char* wptr = g.w;  // the NEXT stage to request
+    int in_idx = 0, gstage = 0;       // in_idx: input layers seen so far
+    // OCC = false: first stage of layer 1 (layer 0 has no weights of its own left) + that layer's bias k-step unless it reads
+    // the input block.  OCC = true: first stage of layer 0 + its bias k-step.
     const bool l1_bias = OCC ? true : (n_hidden > 1 && g.d.has_in[1] == 0);
     const unsigned char* first_bias = OCC ? g.bias : g.bias + kX3BiasBytes;
 #pragma unroll
@@ -614,6 +332,8 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
             q[1] = g.ray_o[m_ray * 3 + 1] + g.ray_d[m_ray * 3 + 1] * d;
             q[2] = g.ray_o[m_ray * 3 + 2] + g.ray_d[m_ray * 3 + 2] * d;
         } else if (valid) { q[0] = g.points[(size_t)n * 3]; q[1] = g.points[(size_t)n * 3 + 1]; q[2] = g.points[(size_t)n * 3 + 2]; }
+        // positional encoding of this lane's point (network.py:141-150): [p s, sin(2^f p s), cos(2^f p s)] per octave f; the
+        // two lanes of a row share the 18 (octave, coordinate) sincos pairs; expressions as compute_xin_tile (mlp_infer.hip)
         const int n_pairs = 3 * g.pe_octaves, half = (n_pairs + 1) / 2;
         for (int pi = lh * half; pi < (lh == 0 ? half : n_pairs); ++pi) {
             const int f = pi / 3, c = pi - 3 * f;
@@ -625,8 +345,10 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
         }
         if (lh == 0) { pe_row[0] = q[0] * g.pe_scale; pe_row[1] = q[1] * g.pe_scale; pe_row[2] = q[2] * g.pe_scale; }
         else for (int col = 3 + 2 * n_pairs; col < kX3PeStride; ++col) pe_row[col] = 0.0f;
+        // (read back by the same wave only -- layer 0 and the epilogue in front of the skip layer --, behind the barrier of
+        //  the first stage)
     }
-    xbf16x8 ones_b;
+    xbf16x8 ones_b;  // K slots 0..2 (lane half 0) carry the constant 1: the three bias pieces add up exactly
     {
         xintx4 o = {lh == 0 ? 0x3F803F80 : 0, lh == 0 ? 0x00003F80 : 0, 0, 0};
         ones_b = __builtin_bit_cast(xbf16x8, o);
@@ -635,6 +357,9 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
     floatx16 cur[8], tmp[8];  // cur: the finished pre-activations of the previous layer (loop-carried); tmp: the layer being accumulated
     xintx4 st[2][3][2];       // B-operand planes of two output tiles: [ring slot][plane][k-step of the tile]
 
+    // lane (n, h), tile ot, register v = 4 q + r  <->  feature 32 ot + 8 q + 4 h + r: four consecutive floats per (ot, q).
+    // acc = U[n] + V[g] (fp32).  (Requesting the U row ahead of the preceding epilogue needs 128 more registers than the
+    // 512 a wave has -- measured: scratch spills --, so its latency is exposed once per input layer: ~1 % of a pass.)
     auto init_uv = [&](floatx16 (&acc)[8], int idx) __attribute__((always_inline)) {
         const float* pu = urow + idx * 256;
         const float* pv = vrow + idx * 256;
@@ -647,8 +372,9 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
                 acc[ot][4 * q] = u.x + t.x; acc[ot][4 * q + 1] = u.y + t.y; acc[ot][4 * q + 2] = u.z + t.z; acc[ot][4 * q + 3] = u.w + t.w;
             }
 #pragma unroll
-        for (int ot = 0; ot < 8; ++ot) asm volatile("" : "+v"(acc[ot]));
+        for (int ot = 0; ot < 8; ++ot) asm volatile("" : "+v"(acc[ot]));  // complete before the next LDS-DMA pieces are issued (asm: invisible to vmcnt)
     };
+    // bias of the layer whose first stage sits in LDS buffer (gstage & 1): acc = b_hi + b_mid + b_lo (exact)
     auto init_bias = [&](floatx16 (&acc)[8]) __attribute__((always_inline)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -676,7 +402,8 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
 
     bool inject_ = false;
     if constexpr (OCC) {
-        init_bias(cur);
+        // layer 0: bias + W_0 pe(x) on the matrix pipe, natural K order: k-step ks, slot j of lane (n, h) = column 16 ks + 8 h + j
+        init_bias(cur);  // (its barrier also orders the encoding writes above against the reads below)
         xbf16x8 bin[3][4];
 #pragma unroll
         for (int ks = 0; ks < 3; ++ks) {
@@ -696,6 +423,7 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
         X3P_STAGE(false, false, cur, cur, ([&](int pl, int ks) -> xbf16x8 { return bin[pl][ks]; }), false, g.bias, cur[0], 0, st[0])
         X3P_STAGE(false, false, cur, cur, ([&](int pl, int ks) -> xbf16x8 { return bin[pl][2 + ks]; }), n_hidden > 1, g.bias + kX3BiasBytes, cur[0], 0, st[0])
     } else {
+        // layer 0: U[n] + V[g] alone
         init_uv(cur, 0);
         ++in_idx;
     }
@@ -839,9 +567,20 @@ __global__ __launch_bounds__(256) void x3_pack_bias_kernel(const float* __restri
 }
 }  // namespace psn
 
-static bool x3_pipelined() {
-    const char* e = getenv("PSN_X3_PIPE");
-    return !(e != nullptr && e[0] == '0');
+// Launch of mlp_infer_x3p_kernel<OCC>: 112 KB of dynamic LDS (+ 24 KB of encoding for OCC) need the opt-in attribute, set per
+// call as in bf16_launch (mlp_infer_bf16.hip)
+template <bool OCC>
+static int x3_launch(const psn::X3Args& a, int64_t blocks, void* stream, const char* what) {
+    using namespace psn;
+    const size_t lds_bytes = 2 * kX3BufBytes + (OCC ? kX3PeBytes : 0);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_infer_x3p_kernel<OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) {
+        set_error("%s: cannot reserve %zu bytes of LDS: %s", what, lds_bytes, hipGetErrorString(e));
+        return PSN_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(mlp_infer_x3p_kernel<OCC>, dim3((unsigned)blocks), dim3(kX3Waves * 64), lds_bytes, (hipStream_t)stream, a);
+    PSN_CHECK_LAUNCH(what);
+    return PSN_OK;
 }
 
 extern "C" int psn_x3_pack(const float* W, int64_t ldw, int rows, int cols, int permuted, int n_ot, int ks0, int n_ks, uint16_t* dst,
@@ -891,20 +630,10 @@ extern "C" int psn_mlp_infer_x3_grouped(const PsnBf16Desc* desc, const uint16_t*
     a.out = out;
     const int64_t blocks = (int64_t)a.tiles_per_group * n_groups;
     PSN_CHECK_ARG(blocks < (1ll << 31), "mlp_infer_x3_grouped: too many rows");
-    const size_t lds_bytes = 2 * kX3BufBytes;
-    // PSN_X3_PIPE=0 selects the round-3 form (whole epilogue between two layers) for A/B runs; default: the pipelined form
-    const auto kern = x3_pipelined() ? &mlp_infer_x3p_kernel<false> : &mlp_infer_x3_kernel<false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        set_error("mlp_infer_x3_grouped: cannot reserve %zu bytes of LDS: %s", lds_bytes, hipGetErrorString(e));
-        return PSN_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kX3Waves * 64), lds_bytes, (hipStream_t)stream, a);
-    PSN_CHECK_LAUNCH("mlp_infer_x3_grouped");
-    return PSN_OK;
+    return x3_launch<false>(a, blocks, stream, "mlp_infer_x3_grouped");
 }
 
-// Stage-1 occupancy network on the split-bf16 engine: sigmoid(-10 logit) of n_rows query points, see mlp_infer_x3_kernel<true>.
+// Stage-1 occupancy network on the split-bf16 engine: sigmoid(-10 logit) of n_rows query points, see mlp_infer_x3p_kernel<true>.
 extern "C" int psn_mlp_infer_x3_occ(const PsnBf16Desc* desc, const uint16_t* packed_w, const uint16_t* bias_steps, const float* final_bias,
                                     const float* points, int64_t n_rows, const long long* n_rows_dev, const int64_t* out_rows,
                                     int pe_octaves, float pe_scale, int skip_layer, int pe_first, float* out, void* stream) {
@@ -927,17 +656,7 @@ extern "C" int psn_mlp_infer_x3_occ(const PsnBf16Desc* desc, const uint16_t* pac
     a.points = points; a.n_rows = n_rows; a.n_rows_dev = n_rows_dev; a.out_rows = out_rows;
     a.pe_octaves = pe_octaves; a.pe_scale = pe_scale; a.skip_layer = skip_layer < 1 ? -1 : skip_layer; a.pe_first = pe_first;
     a.out = out;
-    const int64_t blocks = (n_rows + kX3Waves * 32 - 1) / (kX3Waves * 32);
-    const size_t lds_bytes = 2 * kX3BufBytes + kX3PeBytes;
-    const auto kern = x3_pipelined() ? &mlp_infer_x3p_kernel<true> : &mlp_infer_x3_kernel<true>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        set_error("mlp_infer_x3_occ: cannot reserve %zu bytes of LDS: %s", lds_bytes, hipGetErrorString(e));
-        return PSN_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kX3Waves * 64), lds_bytes, (hipStream_t)stream, a);
-    PSN_CHECK_LAUNCH("mlp_infer_x3_occ");
-    return PSN_OK;
+    return x3_launch<true>(a, (n_rows + kX3Waves * 32 - 1) / (kX3Waves * 32), stream, "mlp_infer_x3_occ");
 }
 
 // The ray-march sweep of stage1/model/rendering.py:447-462 on the split-bf16 engine (opt-in experiment; psn_march_sweep is the
@@ -957,7 +676,6 @@ extern "C" int psn_march_sweep_x3(const PsnBf16Desc* desc, const uint16_t* packe
     PSN_CHECK_ARG(skip_layer < d.n_hidden && (skip_layer < 1 || (pe_first >= 192 && pe_first + 3 + 6 * pe_octaves <= 256)), "march_sweep_x3: skip_layer=%d pe_first=%d", skip_layer, pe_first);
     PSN_CHECK_ARG(n_steps >= 128 && n_steps % (kX3Waves * 32) == 0 && n_rays >= 0 && n_rays * (int64_t)n_steps < (1ll << 31),
                   "march_sweep_x3: n_steps=%d must be a multiple of 128, rays x steps < 2^31", n_steps);
-    PSN_CHECK_ARG(x3_pipelined(), "march_sweep_x3: built for the pipelined kernel only (PSN_X3_PIPE=0 is set)");
     if (n_rays == 0) return PSN_OK;
     X3Args a = {};
     a.d = d;
@@ -969,15 +687,5 @@ extern "C" int psn_march_sweep_x3(const PsnBf16Desc* desc, const uint16_t* packe
     a.out = occ;
     a.ray_o = origin; a.ray_d = dir; a.far = far; a.u = u; a.omu = omu; a.near = near; a.tau = tau; a.n_steps = n_steps;
     a.skip = skip; a.n_blocks = n_blocks;
-    const int64_t blocks = n_rays * (n_steps / (kX3Waves * 32));
-    const size_t lds_bytes = 2 * kX3BufBytes + kX3PeBytes;
-    const auto kern = &mlp_infer_x3p_kernel<true>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        set_error("march_sweep_x3: cannot reserve %zu bytes of LDS: %s", lds_bytes, hipGetErrorString(e));
-        return PSN_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kX3Waves * 64), lds_bytes, (hipStream_t)stream, a);
-    PSN_CHECK_LAUNCH("march_sweep_x3");
-    return PSN_OK;
+    return x3_launch<true>(a, n_rays * (n_steps / (kX3Waves * 32)), stream, "march_sweep_x3");
 }

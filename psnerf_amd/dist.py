@@ -75,9 +75,6 @@ class DataParallel(object):
         return out
 
     # ---- loss denominators ----------------------------------------------------------------------
-    def new_step(self):
-        pass
-
     def global_count(self, mask):
         """Number of True elements of ``mask`` summed over ranks (python int).  Every rank must call this the
         same number of times per step (it is a collective): callers compute it once and pass the value on."""

@@ -68,10 +68,6 @@ def _pad_cols(w, n):
     return torch.nn.functional.pad(w, (0, n - w.shape[1])) if w.shape[1] < n else w
 
 
-def _pad_rows(w, n):  # F.pad with nothing to pad still clones: one fill + one copy kernel per call, ~50 per train step
-    return torch.nn.functional.pad(w, (0, 0, 0, n - w.shape[0])) if w.shape[0] < n else w
-
-
 def _pad_vec(b, n):
     return torch.nn.functional.pad(b, (0, n - b.shape[0])) if b.shape[0] < n else b
 
@@ -93,7 +89,6 @@ def _zeros(shape, device):
     return z
 
 
-TRIM_ACT_KTILES = True  # drop the last activation k-tile of a layer whose input has <= 32 * (n_mt - 1) columns (A/B switch)
 DIRECT_INIT = 'direct'  # layer spec init_a=DIRECT_INIT: the init table is supplied by the caller at call time (no weights)
 
 
@@ -163,7 +158,7 @@ def pack_layers(layers, in_kt_a, in_kt_b, n_out, out_act, device, has_final=True
         if L.get('w_act') is not None:  # K order of the packed layer: activation tiles first, input-feature tiles last
             # only the k-tiles that hold real columns (7 of 8 behind the 217-output layer of the stage-1 geometry network);
             # the final layer always takes the full width (its stage layout is fixed)
-            n_kt_act = hid - 1 if (TRIM_ACT_KTILES and not last and hid > 1 and _src(L['w_act'])[3] <= (hid - 1) * 32) else hid
+            n_kt_act = hid - 1 if (not last and hid > 1 and _src(L['w_act'])[3] <= (hid - 1) * 32) else hid
             plan.append((L['w_act'], n_mt, n_kt_act, off))
             off += n_kt_act * tile
         if L.get('w_in') is not None:
@@ -453,15 +448,13 @@ def _t(w):
     return Transposed(w)
 
 
-def pack_geo_chains(weights, biases, skips, d_pe, single_dump=False, x3=False):
+def pack_geo_chains(weights, biases, skips, d_pe, x3=False):
     """The four fused chains of ops.GeoFieldFused for the 256-wide softplus geometry network
     (stage1/model/network.py:85-120); ``weights`` are the EFFECTIVE dense matrices with the 1/sqrt(2) of the skip
     layer already folded in.  Returns dict(fwd, sweep, sweep_bwd, value_bwd, value_bwd_nosweep) of PackedMLP.
-    ``single_dump`` (experiment, ops.GEO_SINGLE_DUMP): the consumer chains take the dumped softplus outputs A_l where they took the
-    dumped sigmoids S_l and re-form s = 1 - exp(-100 a) in their activation programs; the value pass then dumps one tensor per layer.
+    The value pass dumps one tensor per layer, the softplus outputs A_l; the consumer chains take them where they need the
+    sigmoids s_l and re-form s = 1 - exp(-100 a) in their activation programs (the ACT_*_A codes).
     ``x3`` (experiment, ops.CHAIN_X3): the four chains' matrix work as three bf16 partial products (pack_layers x3)."""
-    mul_aux, mul2, sp_bwd = ((hip.ACT_MUL_AUX_A, hip.ACT_MUL2_A, hip.ACT_SOFTPLUS_BWD_A) if single_dump else
-                             (hip.ACT_MUL_AUX, hip.ACT_MUL2, hip.ACT_SOFTPLUS_BWD))
     n = len(weights)
     assert len(skips) == 1 and weights[1].shape[1] == 256 and weights[n - 1].shape[0] == 257
     sk = skips[0]
@@ -479,16 +472,16 @@ def pack_geo_chains(weights, biases, skips, d_pe, single_dump=False, x3=False):
             return dict(w_in=W[l][:, d_a:], w_act=W[l][:, :d_a])
         return dict(w_in=None, w_act=W[l])
 
-    # F1: value pass, dumps a_{l+1} and sigmoid(100 z_l); HEAD = 256 features, final = occupancy logit
+    # F1: value pass, dumps a_{l+1}; HEAD = 256 features, final = occupancy logit
     layers = [dict(bias=b[l], act=hip.ACT_SOFTPLUS100, **fwd_in(l)) for l in range(n - 1)]
     layers.append(dict(w_in=None, w_act=W[n - 1][1:], bias=b[n - 1][1:], act=hip.ACT_HEAD))
     layers.append(dict(w_in=None, w_act=W[n - 1][:1], bias=b[n - 1][:1], act=hip.ACT_NONE))
     fwd = pack_layers(layers, ka, 0, 1, hip.OUT_NONE, dev, x3=x3)
 
     # F2: reverse sweep r_l = (r_{l+1} * s_l) W_l, starting from row 0 of the last layer (init table with one row)
-    layers = [dict(init_a=DIRECT_INIT, init_b=None, w_act=None, bias=zeros, act=mul_aux)]
+    layers = [dict(init_a=DIRECT_INIT, init_b=None, w_act=None, bias=zeros, act=hip.ACT_MUL_AUX_A)]
     for l in range(n - 2, 0, -1):
-        layers.append(dict(w_act=_t(W[l]), bias=zeros, act=mul_aux))
+        layers.append(dict(w_act=_t(W[l]), bias=zeros, act=hip.ACT_MUL_AUX_A))
     # ... and ends with r_0 = u_0 W_0 (256 -> d_pe encoding columns) as a 64-output FINAL layer: 4 output tiles instead of the 16
     # of a hidden-type layer, the [Q, d_pe] result written densely
     layers.append(dict(w_act=_t(W[0]), bias=_zeros(64, dev), act=hip.ACT_NONE))
@@ -496,7 +489,7 @@ def pack_geo_chains(weights, biases, skips, d_pe, single_dump=False, x3=False):
     sweep = pack_layers(layers, ka, 0, d_pe, hip.OUT_NONE, dev, x3=x3)
 
     # B1: adjoint of the sweep: du_l = dR_l W_l^T ; dR_{l+1} = du_l * s_l ; dS_l = du_l * R_{l+1}
-    layers = [dict(bias=zeros, act=mul2, **fwd_in(l)) for l in range(n - 1)]
+    layers = [dict(bias=zeros, act=hip.ACT_MUL2_A, **fwd_in(l)) for l in range(n - 1)]
     sweep_bwd = pack_layers(layers, ka, 0, 0, hip.OUT_NONE, dev, has_final=False, x3=x3)
 
     # B2: adjoint of the value pass: da_l = W_l^T dz_l ; dz_{l-1} = s (da + 100 dS (1 - s))   [or s * da without sweep]
@@ -506,8 +499,8 @@ def pack_geo_chains(weights, biases, skips, d_pe, single_dump=False, x3=False):
             ls.append(dict(w_act=_t(W[l]), bias=zeros, act=act))
         return pack_layers(ls, ka, 0, 0, hip.OUT_NONE, dev, has_final=False, x3=x3)
 
-    return dict(fwd=fwd, sweep=sweep, sweep_bwd=sweep_bwd, value_bwd=value_bwd(sp_bwd),
-                value_bwd_nosweep=value_bwd(mul_aux), d_a=d_a, single_dump=bool(single_dump))
+    return dict(fwd=fwd, sweep=sweep, sweep_bwd=sweep_bwd, value_bwd=value_bwd(hip.ACT_SOFTPLUS_BWD_A),
+                value_bwd_nosweep=value_bwd(hip.ACT_MUL_AUX_A), d_a=d_a)
 
 
 def pack_app_chains(weights, biases, d_x, x3=False):

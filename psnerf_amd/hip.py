@@ -1032,7 +1032,7 @@ def _tn_is_tall(it):
 
 # EXPERIMENT (BASELINE configs[4] bf16 path): the 256 x 256-tile weight gradients on the bf16 matrix pipe with split operands
 # (psn_gemm_tn_grouped_x3).  Process-wide switch for A/B runs and the labelled bench objects; never on by default.
-WGRAD_X3 = os.environ.get('PSN_WGRAD_X3', '0') == '1'
+WGRAD_X3 = False
 
 
 class wgrad_precision(object):

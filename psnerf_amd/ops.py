@@ -779,19 +779,16 @@ class VisibilityPair(torch.autograd.Function):
 # --------------------------------------------------------------------------- stage-1 geometry field, fused chains
 # One dump per softplus layer (round 5): the value pass writes A_l = softplus_100(z_l) only; the three consumer
 # chains re-form sigmoid(100 z_l) = 1 - exp(-100 A_l) in their activation programs (PSN_ACT_*_A: a separate instantiation of the
-# chain kernel -- as extra cases of the one kernel they spilled 92 registers).  Measured at 262,144 points (profiles/r05a_*single_dump*):
+# chain kernel -- as extra cases of the one kernel they spilled 92 registers).  Measured at 262,144 points (HISTORY.md §8 item 5):
 # F1 writes 2.42 GB instead of 4.58 GB and takes 6 % fewer cycles, F2 / B1 / B2 pay 1.2 - 2.3 % for the exponentials (+25 M vector
 # instructions each); chains -0.3 % cycles, the configs[1] step -0.2 .. -0.45 ms (43.8 -> 43.5 ms), eight [Q, 256] tensors (4.3 GB at
-# 524k render samples) are no longer allocated.  Results differ in the last bits (gradients 6e-7 relative).  PSN_GEO_SINGLE_DUMP=0
-# restores the two-dump chains (A/B: tools/dbg/ab_single_dump.py).
-import os as _os
-GEO_SINGLE_DUMP = _os.environ.get('PSN_GEO_SINGLE_DUMP', '1') == '1'
+# 524k render samples) are no longer allocated.  Results differ in the last bits (gradients 6e-7 relative).
 # Split-bf16 form of the stage-1 chains (experiment, never the headline; BASELINE configs[4] "bf16 MFMA path"): the four geometry
 # chains and the two appearance chains multiply on v_mfma_f32_16x16x32_bf16 -- every fp32 operand as two bf16 pieces, three partial
 # products, fp32 accumulation (csrc/mlp_infer.hip stage_compute_x3; PsnMlpDesc.w_format = PSN_W_BF16X2) -- while the activation
 # programs, dumps and epilogues stay fp32.  ``with ops.chain_precision('bf16x3'):`` around forward AND backward (the packs are
 # rebuilt when the mode changes).
-CHAIN_X3 = _os.environ.get('PSN_CHAIN_X3', '0') == '1'
+CHAIN_X3 = False
 
 
 class chain_precision(object):
@@ -836,12 +833,10 @@ class GeoFieldFused(torch.autograd.Function):
         d_a = chains['d_a']
         sk = skips[0]
         pe = hip.pe_encode(p, n_octaves, 64, scale)  # [Q,64] xin table (39 real columns)
-        A = [torch.empty(Q, 256, device=dev) for _ in range(n - 1)]   # A[l] = softplus output of layer l = input of l+1
-        single = bool(chains.get('single_dump'))
-        # single-dump experiment (GEO_SINGLE_DUMP): the sigmoids are not dumped, the consumer chains re-form them from A
-        S = A if single else [torch.empty(Q, 256, device=dev) for _ in range(n - 1)]
+        # A[l] = softplus output of layer l = input of l+1; the sigmoids S[l] are not dumped, the consumer chains re-form them from A
+        A = [torch.empty(Q, 256, device=dev) for _ in range(n - 1)]
         feat = torch.empty(Q, 256, device=dev)
-        logit = chains['fwd'](pe, Q, save=A + [feat], save2=None if single else S + [None, None])
+        logit = chains['fwd'](pe, Q, save=A + [feat])
         A[sk - 1][:, d_a:] = pe[:, :d_pe]  # the skip layer's input is [a (217) | pe (39)]: complete the dumped tile
         grad = None
         U = R = None
@@ -855,7 +850,7 @@ class GeoFieldFused(torch.autograd.Function):
             # tiles only; r0 = u_0 W_0 [Q, d_pe] is the chain's final layer (64 outputs wide, 4 output tiles)
             t_sk = sum(1 << t for t in range(d_a // 16, (d_a + d_pe - 1) // 16 + 1))
             r0 = chains['sweep'](None, Q, a_div=1, a_mod=1, init_a_direct=w_row,
-                                 mask=[S[n - 2 - j] for j in range(n - 1)] + [None],
+                                 mask=[A[n - 2 - j] for j in range(n - 1)] + [None],
                                  save=[U[n - 2 - j] for j in range(n - 1)],
                                  save2=[None] + [r_sk if n - 1 - j == sk else None for j in range(1, n - 1)] + [None],
                                  save2_tiles=[None] + [t_sk if n - 1 - j == sk else None for j in range(1, n - 1)] + [None])
@@ -863,7 +858,7 @@ class GeoFieldFused(torch.autograd.Function):
             grad = hip.pe_encode_bwd(p, r0, n_octaves, scale, add=r_sk[:, d_a:d_a + d_pe])
         if any(ctx.needs_input_grad):
             ctx.meta = (n, sk, d_pe, d_a, n_octaves, scale, with_grad, chains, feat_rows)
-            keep = [p, pe] + Ws + A + ([] if single else S)
+            keep = [p, pe] + Ws + A
             if with_grad:
                 keep += U
             ctx.save_for_backward(*keep)
@@ -879,8 +874,6 @@ class GeoFieldFused(torch.autograd.Function):
         p, pe = sv[0], sv[1]
         Ws = sv[2:2 + n]
         A = sv[2 + n:2 + 2 * n - 1]
-        single = bool(chains.get('single_dump'))
-        S = A if single else sv[2 + 2 * n - 1:2 + 3 * n - 2]
         Q, dev = p.shape[0], p.device
         sweep = with_grad and d_grad is not None
         d_logit = torch.zeros(Q, 1, device=dev) if d_logit is None else d_logit.contiguous()
@@ -891,8 +884,7 @@ class GeoFieldFused(torch.autograd.Function):
 
         E = None
         if sweep:
-            base = 2 + (2 if single else 3) * n - (1 if single else 2)
-            U = sv[base:base + n - 1]
+            U = sv[2 + 2 * n - 1:2 + 3 * n - 2]
             dd_pe = hip.pe_encode_jvp(p, d_grad.contiguous(), n_octaves, 64, scale)  # adjoint of d_pe, [Q,64]
             dR = [dd_pe] + [torch.empty(Q, 256, device=dev) for _ in range(n - 1)]   # dR[l], l = 0..n-1
             # Adjoint of the sweep u_l = r_{l+1} * s_l, r_l = W_l^T u_l:  du_l = W_l dr_l,  dr_{l+1} = du_l * s_l  and
@@ -900,7 +892,7 @@ class GeoFieldFused(torch.autograd.Function):
             # = 100 (1 - s_l) (du_l * u_l): the chain therefore multiplies with the dumped U_l instead of a dumped R_{l+1}
             # (one tensor less written by the sweep and none read back), and dumps E_l = du_l * u_l.
             E = [torch.empty(Q, 256, device=dev) for _ in range(n - 1)]
-            chains['sweep_bwd'](dd_pe, Q, mask=list(S), aux2=list(U), save=dR[1:], save2=E)
+            chains['sweep_bwd'](dd_pe, Q, mask=list(A), aux2=list(U), save=dR[1:], save2=E)
             dR[sk][:, d_a:] = dd_pe[:, :d_pe]  # adjoint of the skip layer's [a | pe] sweep value
 
         # adjoint of the value pass: dz_l = s_l da_l + 100 (1 - s_l) E_l
@@ -908,7 +900,7 @@ class GeoFieldFused(torch.autograd.Function):
         key = 'value_bwd' if sweep else 'value_bwd_nosweep'
         # the rank-1 term d_logit (x) w_row of W_last^T d_out is formed inside the chain kernel (rank_init)
         chains[key](None, Q, a_div=1, a_mod=Q, rank_init=(d_logit.reshape(Q, 1).contiguous(), w_row), act_init=d_feat, act_init_rows=feat_rows,
-                    mask=[S[n - 2 - j] for j in range(n - 1)],
+                    mask=[A[n - 2 - j] for j in range(n - 1)],
                     aux2=[E[n - 2 - j] for j in range(n - 1)] if sweep else None,
                     save=[dZ[n - 2 - j] for j in range(n - 1)])
         # Every weight gradient of the call in ONE grouped launch: dW_l = dZ_l^T A_{l-1} (+ U_l^T dR_l from the sweep),

@@ -47,8 +47,6 @@ class _Captured(object):
 
 
 class GraphedTrainStep(object):
-    SKIP_PADDING = True  # pad_to_pixels: hand the device-side surface count to the model (False: the padding rows are evaluated; A/B)
-
     def __init__(self, step, warmup=2, max_graphs=8, overlap_small_nets=None, adopt_inputs=False, agree=None, pad_to_pixels=False,
                  pad_multiple=0, clone_terms=False):
         """``overlap_small_nets``: None keeps the model's setting; False captures a single-stream graph (0.04 ms of host
@@ -121,15 +119,12 @@ class GraphedTrainStep(object):
         st = self.step_obj
         if train_order:
             st.train_fix()
-        st.dp.new_step()
         model_input = st.select_vis_lights(model_input, vidx)
         if self.pad_to_pixels:
             model_input = dict(model_input)
             sm = model_input['surface_mask'][0].contiguous()
             # (the count stays on the device: the visibility launch skips the shading rows of the padding with it)
-            model_input['surface_idx'], cnt = hip.surface_index(sm, sm.numel())
-            if self.SKIP_PADDING:
-                model_input['surface_count'] = cnt
+            model_input['surface_idx'], model_input['surface_count'] = hip.surface_index(sm, sm.numel())
         elif self.pad_multiple and model_input.get('surface_idx') is not None and model_input['surface_idx'].numel() > 0:
             idx = model_input['surface_idx']
             ns, k = idx.numel(), self.pad_multiple
@@ -137,8 +132,7 @@ class GraphedTrainStep(object):
             if cap != ns:
                 model_input = dict(model_input)
                 model_input['surface_idx'] = torch.cat([idx, idx[-1:].expand(cap - ns)])
-                if self.SKIP_PADDING:
-                    model_input['surface_count'] = torch.full((1,), float(ns), device=idx.device, dtype=torch.float32)
+                model_input['surface_count'] = torch.full((1,), float(ns), device=idx.device, dtype=torch.float32)
         if 'surface_idx' not in model_input:
             # the reference's dictionary (no index list of the surface pixels): built here, OUTSIDE the graph -- nonzero() is a
             # host synchronisation and cannot be captured; its length is part of the graph's signature

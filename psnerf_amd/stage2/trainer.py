@@ -173,7 +173,6 @@ class TrainStep(object):
         (train_fix, iteration count, schedulers); stage2/graph.py replays the device phases from HIP graphs."""
         if train_order:
             self.train_fix()
-        self.dp.new_step()
         model_input = self.select_vis_lights(model_input, vidx)
         terms, out, trainable, train_light = self._fwd_bwd(model_input, ground_truth, l_slt, noise=noise)
         self._reduce(trainable)

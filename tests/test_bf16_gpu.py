@@ -456,7 +456,7 @@ def test_chain_bf16x3_geometry_field_vs_exact_and_float64(cuda):
         for p in params:
             p.grad = None
         with ops.chain_precision(mode):
-            chains = fused.pack_geo_chains(params[0::2], params[1::2], list(skips), net.d_pe, single_dump=ops.GEO_SINGLE_DUMP, x3=ops.CHAIN_X3)
+            chains = fused.pack_geo_chains(params[0::2], params[1::2], list(skips), net.d_pe, x3=ops.CHAIN_X3)
             logit, feat, grad = ops.GeoFieldFused.apply(pts, octaves, scale, skips, True, chains, None, *params)
             objective(logit, feat, grad).backward()
         return [logit.detach(), feat.detach(), grad.detach()] + [p.grad.clone() for p in params]

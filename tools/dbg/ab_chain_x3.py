@@ -24,7 +24,7 @@ def run(pts, x3):
         q.grad = None
     pts = pts.clone().requires_grad_()
     with ops.chain_precision('bf16x3' if x3 else 'fp32'):
-        chains = fused.pack_geo_chains(params[0::2], params[1::2], [4], 39, single_dump=ops.GEO_SINGLE_DUMP, x3=x3)
+        chains = fused.pack_geo_chains(params[0::2], params[1::2], [4], 39, x3=x3)
         logit, feat, grad = ops.GeoFieldFused.apply(pts, 6, 1.0, (4,), True, chains, None, *params)
         (logit.sum() + feat.sum() * 0.1 + (grad * grad).sum()).backward()
     return logit.detach(), feat.detach(), grad.detach(), [q.grad.clone() for q in params]

@@ -19,7 +19,7 @@ params = []
 for i, o in zip(dims_in, dims_out):
     params += [(torch.randn(o, i, device=dev) * (1.4 / i ** 0.5)).requires_grad_(), (torch.randn(o, device=dev) * 0.01).requires_grad_()]
 p = (torch.rand(Q, 3, device=dev) - 0.5).requires_grad_()
-chains = fused.pack_geo_chains(params[0::2], params[1::2], [4], 39, single_dump=ops.GEO_SINGLE_DUMP)
+chains = fused.pack_geo_chains(params[0::2], params[1::2], [4], 39)
 names = ['F1 value', 'F2 sweep', 'B1 sweep-adj', 'B2 value-adj']
 macs = [39 * 256 + 6 * 65536 + 256 * 217 + 256 * 256 + 2 * 65536 + 256, 7 * 65536 + 256 * 64, 64 * 256 + 7 * 65536 + 64 * 256, 8 * 65536]
 rep, res = {'rows': Q}, {}

@@ -34,7 +34,7 @@ python3 $R/tools/bench_composite.py 2>/dev/null | tail -1 > $O/composite.json
 # matrix-pipe occupancy of the split-bf16 engine (own PMC pass, --kernel-trace only)
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d /tmp/pmc_x3 -o c -- python3 $R/tools/dbg/bench_x3.py > /dev/null 2>&1
 F=$(find /tmp/pmc_x3 -name '*counter_collection*' | head -1)
-(head -1 $F; grep "mlp_infer_x3_kernel\|mlp_infer_bf16_kernel" $F | head -40) > $O/pmc_x3.csv
+(head -1 $F; grep "mlp_infer_x3p_kernel\|mlp_infer_bf16_kernel" $F | head -40) > $O/pmc_x3.csv
 # round 4 additions: the rank shards of BASELINE cfg 4 on one GPU (data-parallel path on, eager / HIP graph, host vs GPU time),
 # the split-bf16 occupancy engine, the kernel timeline of a replayed 4096-px step
 python3 $R/tools/strong_projection.py --graph --queue-ahead --steps 40 --out $O/strong_projection.json > $O/strong_projection.log 2>&1
@@ -52,12 +52,10 @@ done
 for RAYS in 4096 2048 1024 512; do
     python3 $R/tools/bench_stage1.py --rays $RAYS --steps 30 --warmup 5 2>/dev/null | tail -1
 done > $O/stage1_rank_shards.jsonl
-# round 5 additions: configs[4] at its stated size with the device sampler in the loop, the split-bf16 weight-gradient kernel, the
-# single-dump chains A/B
+# round 5 additions: configs[4] at its stated size with the device sampler in the loop, the split-bf16 weight-gradient kernel
 python3 $R/tools/run_e2e.py --full --json-out $O/e2e_full.json > $O/e2e_full.log 2>&1
 python3 $R/tools/run_e2e.py --full --precision bf16x3 --json-out $O/e2e_full_bf16x3.json > $O/e2e_full_bf16x3.log 2>&1
 python3 $R/tools/dbg/bench_tn256_x3.py 2>/dev/null | tail -1 > $O/tn256_x3.json
-python3 $R/tools/dbg/ab_single_dump.py 2>/dev/null | tail -1 > $O/ab_single_dump.json
 # split-bf16 weight stages (PSN_W_BF16X2): the four geometry chains and the shading-row launch, fp32 vs three partial products
 python3 $R/tools/dbg/ab_chain_x3.py 2>/dev/null | tail -1 > $O/ab_chain_x3.json
 python3 $R/tools/dbg/bench_lrow_x3.py 2>/dev/null | tail -1 > $O/lrow_x3.json
@@ -66,5 +64,5 @@ python3 $R/tools/dbg/bench_lrow_x3.py 2>/dev/null | tail -1 > $O/lrow_x3.json
 python3 $R/tools/ab_block_order.py 2>/dev/null | tail -1 > $O/ab_block_order.json
 bash $R/tools/pmc_block_order.sh $TAG > /dev/null 2>&1
 bash $R/tools/prof_composite.sh $TAG > /dev/null 2>&1
-bash $R/tools/dbg/pmc_chains.sh $TAG single > /dev/null 2>&1
+bash $R/tools/dbg/pmc_chains.sh $TAG > /dev/null 2>&1
 ls -la $O
