@@ -763,6 +763,47 @@ int psn_mf_shade_bwd(const float* light_dir, const float* view, const float* nor
                      int L, int64_t Ns, const float* g_rgb, float* d_albedo, float* d_rough, float* d_normal,
                      float* d_vis, float* d_light_dir, float* d_light_int, float* workspace, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Stage-1 mesh extraction: stage1/model/extracting.py:75-206 with utils/libmise/mise.pyx (multi-resolution iso-surface
+ * refinement) and utils/libmcubes/marchingcubes.h:23-193 (marching cubes, first variant), state resident on the device.
+ *   grid   float32 [n, n, n], n = resolution + 1 points per axis, x-major; NaN = hole (no value yet)
+ *   flags  one byte per grid point (0 = no grid point yet, 1 = pending, 2 = known), 4-byte aligned, padded with zero
+ *          bytes to a multiple of 4
+ *   vox    voxel states of the octree levels 0 .. depth - 1 back to back, level l = (resolution0 << l)^3 bytes x-major
+ *          (0 = absent, 1 = leaf, 2 = split); level 0 starts as all leaves
+ * Sizes beyond PSN_MESH_MAX_RESOLUTION return PSN_E_UNSUPPORTED.
+ *
+ * psn_mise_collect (mise.pyx:107-129 + extracting.py:105-108): the pending points as a compact list -- rows[r] = linear grid
+ *   index, points[r] = box_size * ((float)i / (float)resolution - 0.5f) per axis, float32 in that order -- and their
+ *   transition to known.  count[0] = number of pending points found (entries behind `capacity` are dropped).  The order of
+ *   the list is not defined.  The list feeds psn_mlp_infer_pe_indirect (points, n_rows_dev = count, out_rows = rows, out = grid).
+ * psn_mise_refine (mise.pyx:185-282): one round over every leaf of every level < depth, finest level first.  A leaf is active iff
+ *   the known grid points of its closed cube hold a value >= threshold and a value <= threshold (double, both non-strict); it
+ *   is split, its children become leaves, the points of its half-edge lattice that are no grid points yet become pending.
+ *   pending[0] = number of points that became pending in this round; 0 ends the refinement.
+ * psn_grid_ffill (mise.pyx:143-164, to_dense): in place, every hole takes its predecessor's value along x, then along y,
+ *   then along z (three passes in that order; pure copies).
+ * psn_mc_count (marchingcubes.h:59-72 on the grid padded by one layer of -1e6, extracting.py:170-171; the padding is
+ *   virtual): cells (n + 1)^3, x-major; cube index bit m set iff value(v_m) <= threshold.  code[c] = bit a set iff the
+ *   lattice edge from the cell's lower corner along axis a carries a vertex, | number of triangles << 3;
+ *   block_v / block_t [psn_mc_blocks(n)] = vertices / triangles per run of 256 consecutive cells.
+ * psn_mc_emit (marchingcubes.h:74-187, extracting.py:175-181): v_base / t_base = exclusive scans of those block sums,
+ *   n_vertices / n_faces their totals.  vertices [n_vertices, 3] float64: x1 + (x2 - x1) (threshold - f1) / (f2 - f1) in
+ *   double on the lattice edge, then box_size * ((v - 1) / (n - 1) - 0.5) (box_size <= 0: units of the padded lattice),
+ *   ascending by (owning grid point x-major, axis); faces [n_faces, 3] int64 ascending by (cell x-major, order of the case
+ *   table csrc/mc_table.h, which tools/gen_mc_table.py derives).  v_off: scratch, int32 [(n + 1)^3], uninitialised.
+ * ---------------------------------------------------------------------- */
+#define PSN_MESH_MAX_RESOLUTION 1024
+int psn_mise_collect(unsigned char* flags, int resolution, float box_size, int64_t capacity, int64_t* rows, float* points,
+                     long long* count, void* stream);
+int psn_mise_refine(const float* grid, unsigned char* flags, unsigned char* vox, int resolution0, int depth, double threshold,
+                    long long* pending, void* stream);
+int psn_grid_ffill(float* grid, int n, void* stream);
+int64_t psn_mc_blocks(int n);
+int psn_mc_count(const float* grid, int n, double threshold, unsigned char* code, int* block_v, int* block_t, void* stream);
+int psn_mc_emit(const float* grid, int n, double threshold, const unsigned char* code, const int64_t* v_base, const int64_t* t_base,
+                int64_t n_vertices, int64_t n_faces, double box_size, int* v_off, double* vertices, int64_t* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -400,11 +400,11 @@ def pack_relu_mlp_bf16_grouped(weights, biases, din_a, din_b, skip_at, out_act=h
     return PackedBf16Grouped(desc, buf, fb, wb_t.contiguous(), torch.cat(b_in).contiguous())
 
 
-def pack_geo_occupancy(weights, biases, skips, d_pe, x3=False):
+def pack_geo_occupancy(weights, biases, skips, d_pe, x3=False, out_act=hip.OUT_OCC, negate=False):
     """stage1 occupancy-only network (stage1/model/network.py:85-95,124-125): softplus(beta=100)
     stack, before layer l in ``skips`` the input becomes cat[x, pe]/sqrt(2); only output row 0 of the
     last layer is evaluated, followed by sigmoid(-10 x).  Every query point is distinct, so the input
-    block stays on the MFMA k-tile path."""
+    block stays on the MFMA k-tile path.  ``out_act`` / ``negate``: see pack_geo_logit."""
     ka = (d_pe + 31) // 32
     layers = []
     n = len(weights)
@@ -415,6 +415,8 @@ def pack_geo_occupancy(weights, biases, skips, d_pe, x3=False):
         act = hip.ACT_NONE if last else hip.ACT_SOFTPLUS100
         if last:
             W, b = W[:1], b[:1]
+            if negate:
+                W, b = -W, -b
         if li == 0:
             layers.append(dict(w_in=W, w_act=None, bias=b, act=act))
         elif li in skips:
@@ -422,7 +424,14 @@ def pack_geo_occupancy(weights, biases, skips, d_pe, x3=False):
             layers.append(dict(w_in=W[:, d_x:] * inv, w_act=W[:, :d_x] * inv, bias=b, act=act))
         else:
             layers.append(dict(w_in=None, w_act=W, bias=b, act=act))
-    return pack_layers(layers, ka, 0, 1, hip.OUT_OCC, weights[0].device, x3=x3)
+    return pack_layers(layers, ka, 0, 1, out_act, weights[0].device, x3=x3)
+
+
+def pack_geo_logit(weights, biases, skips, d_pe):
+    """The occupancy network's NEGATED logit (network.py:forward(return_logits=True) = -1 * logit; the value function of the mesh
+    extraction, stage1/model/extracting.py:137-155) on the lean engine: pack_geo_occupancy without the final sigmoid, the sign
+    folded into the last layer's row and bias (the negation of every product and of the bias negates the rounded sum exactly)."""
+    return pack_geo_occupancy(weights, biases, skips, d_pe, out_act=hip.OUT_NONE, negate=True)
 
 
 def pack_relu_bwd(weights, skip_at, width=256, bits=False, x3=False):

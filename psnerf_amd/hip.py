@@ -204,6 +204,12 @@ SIGNATURES = {
     'psn_mlp_infer_x3_occ': (i32, [ctypes.POINTER(PsnBf16Desc), c_f, c_f, c_f, c_f, i64, c_f, c_f, i32, f32, i32, i32, c_f, c_f]),
     'psn_march_sweep_x3': (i32, [ctypes.POINTER(PsnBf16Desc), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, f32, i64, i32, f32, i32, f32, i32, i32,
                                  c_f, c_f, c_f, c_f]),
+    'psn_mise_collect': (i32, [c_f, i32, f32, i64, c_f, c_f, c_f, c_f]),
+    'psn_mise_refine': (i32, [c_f, c_f, c_f, i32, i32, ctypes.c_double, c_f, c_f]),
+    'psn_grid_ffill': (i32, [c_f, i32, c_f]),
+    'psn_mc_blocks': (i64, [i32]),
+    'psn_mc_count': (i32, [c_f, i32, ctypes.c_double, c_f, c_f, c_f, c_f]),
+    'psn_mc_emit': (i32, [c_f, i32, ctypes.c_double, c_f, c_f, c_f, i64, i64, ctypes.c_double, c_f, c_f, c_f, c_f]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(_lib, _name)  # AttributeError here = library out of date: fail loudly
@@ -1547,3 +1553,79 @@ def march_sweep_x3(desc, packed_w, bias_steps, final_bias, origin, direction, fa
                                        None if skip is None else skip.data_ptr(), occ.data_ptr(), None if count is None else count.data_ptr(),
                                        _stream()), 'march_sweep_x3')
     return occ, skip
+
+
+# --------------------------------------------------------------------------- stage-1 mesh extraction (csrc/mesh.hip)
+MESH_MAX_RESOLUTION = 1024
+
+
+def _tptr(t, name, dtype):
+    """Device pointer of a contiguous tensor of the given dtype."""
+    if t is None or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError('%s: must be a contiguous %s HIP device tensor' % (name, dtype))
+    return t.data_ptr()
+
+
+def mise_flags(resolution, device):
+    """Zeroed flag bytes of a (resolution + 1)^3 grid, padded to whole 4-byte words (psn_mise_collect / psn_mise_refine)."""
+    n3 = (resolution + 1) ** 3
+    return torch.zeros((n3 + 3) // 4 * 4, dtype=torch.uint8, device=device)
+
+
+def mise_collect(flags, resolution, box_size, capacity, count):
+    """Pending grid points -> (rows int64 [capacity], points float32 [capacity, 3]); count (int64 [1] on the device) receives their
+    number; the points become known (psn_mise_collect)."""
+    assert flags.numel() == ((resolution + 1) ** 3 + 3) // 4 * 4 and count.numel() == 1
+    rows = torch.empty(capacity, dtype=torch.int64, device=flags.device)
+    points = torch.empty(capacity, 3, dtype=torch.float32, device=flags.device)
+    _check(_lib.psn_mise_collect(_tptr(flags, 'flags', torch.uint8), int(resolution), float(box_size), int(capacity), rows.data_ptr(),
+                                 points.data_ptr(), _tptr(count, 'count', torch.int64), _stream()), 'mise_collect')
+    return rows, points
+
+
+def mise_refine(grid, flags, vox, resolution0, depth, threshold, pending):
+    """One refinement round in place (psn_mise_refine); pending (int64 [1] on the device) receives the number of new grid points."""
+    res = resolution0 << depth
+    assert grid.numel() == (res + 1) ** 3 and flags.numel() == ((res + 1) ** 3 + 3) // 4 * 4 and pending.numel() == 1
+    assert vox.numel() == sum((resolution0 << l) ** 3 for l in range(depth))
+    _check(_lib.psn_mise_refine(_ptr(grid, 'grid'), _tptr(flags, 'flags', torch.uint8), _tptr(vox, 'vox', torch.uint8), int(resolution0),
+                                int(depth), float(threshold), _tptr(pending, 'pending', torch.int64), _stream()), 'mise_refine')
+
+
+def grid_ffill(grid):
+    """MISE.to_dense's hole filling, in place on a cubic [n, n, n] grid whose holes are NaN (psn_grid_ffill)."""
+    n = grid.shape[0]
+    assert grid.shape == (n, n, n)
+    with _Prof('grid_ffill', 8 * grid.numel()):
+        _check(_lib.psn_grid_ffill(_ptr(grid, 'grid'), n, _stream()), 'grid_ffill')
+    return grid
+
+
+def marching_cubes(grid, threshold, box_size=0.0):
+    """Marching cubes over a cubic [n, n, n] grid padded (virtually) with -1e6 (psn_mc_count, psn_mc_emit) ->
+    (vertices float64 [V, 3], faces int64 [F, 3]) on the device.  box_size > 0: vertices in world units
+    (stage1/model/extracting.py:175-181); otherwise in units of the padded lattice.  One host synchronisation (the two totals)."""
+    n = grid.shape[0]
+    assert grid.shape == (n, n, n)
+    dev = grid.device
+    nb = int(_lib.psn_mc_blocks(n))
+    if nb == 0:
+        raise RuntimeError('marching_cubes: %d points per axis are not supported (2 .. %d)' % (n, MESH_MAX_RESOLUTION + 1))
+    n_cells = (n + 1) ** 3
+    code = torch.empty(n_cells, dtype=torch.uint8, device=dev)
+    blk = torch.empty(2, nb, dtype=torch.int32, device=dev)
+    with _Prof('mc_count', 4 * grid.numel()):
+        _check(_lib.psn_mc_count(_ptr(grid, 'grid'), n, float(threshold), code.data_ptr(), blk[0].data_ptr(), blk[1].data_ptr(), _stream()),
+               'mc_count')
+    incl = torch.cumsum(blk, dim=1, dtype=torch.int64)
+    base = (incl - blk).contiguous()
+    n_v, n_f = (int(x) for x in incl[:, -1].tolist())
+    vertices = torch.empty(n_v, 3, dtype=torch.float64, device=dev)
+    faces = torch.empty(n_f, 3, dtype=torch.int64, device=dev)
+    if n_v == 0:
+        return vertices, faces
+    v_off = torch.empty(n_cells, dtype=torch.int32, device=dev)
+    with _Prof('mc_emit', 24 * n_v + 24 * n_f):
+        _check(_lib.psn_mc_emit(_ptr(grid, 'grid'), n, float(threshold), code.data_ptr(), base[0].data_ptr(), base[1].data_ptr(), n_v, n_f,
+                                float(box_size), v_off.data_ptr(), vertices.data_ptr(), faces.data_ptr(), _stream()), 'mc_emit')
+    return vertices, faces

@@ -5,4 +5,5 @@ from .network import NeuralNetwork, WNLinear
 from .rendering import Renderer
 from .losses import Loss
 from .training import Trainer
+from .extracting import Extractor3D, Mesh
 from . import config

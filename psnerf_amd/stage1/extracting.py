@@ -1,0 +1,469 @@
+"""Mesh extraction from the stage-1 occupancy field with the reference's ``Extractor3D`` interface
+(stage1/model/extracting.py:15-235; utils/libmise/mise.pyx; utils/libmcubes/marchingcubes.h:23-193).
+
+Two implementations of one definition:
+  * device tensors -> csrc/mesh.hip.  Value grid, point flags and voxel states stay on the device for the whole extraction; a
+    round is psn_mise_collect (pending points -> compact list), the evaluation of that list scattered into the grid, and
+    psn_mise_refine (split the active leaves, mark the new points); the host reads one 8-byte count per round.  Then
+    psn_grid_ffill (to_dense), psn_mc_count / psn_mc_emit.  A ``NeuralNetwork`` whose geometry net the lean register-resident
+    engine holds is evaluated by that engine straight from the list (fused.pack_geo_logit); any other callable with the
+    reference's signature is called in ``points_batch_size`` batches.
+  * CPU tensors -> the vectorised numpy functions below (``host_*``), which are also the pinned restatement of the semantics
+    the device path is tested against.
+
+Semantics (restated from the reference, see the functions for the line numbers):
+  value(p) = -logit(p) = model(p[None], None, return_logits=True); iso value log(t) - log(1 - t) in double.
+  Grid point (i, j, k) of the (R + 1)^3 lattice, R = resolution0 << upsampling_steps, is the point
+  box_size * ((float)i / (float)R - 0.5f) per axis in float32, box_size = 2 + padding.
+  MISE: leaf voxels that see a known value >= iso and one <= iso in their closed cube are split until nothing new appears
+  (a least fixed point: the order of the tests within a round does not change the final set of evaluated points).
+  to_dense: holes take their predecessor's value along x, then y, then z.  Marching cubes runs on the grid padded with -1e6,
+  with the case table of csrc/mc_table.h (tools/gen_mc_table.py); vertices are float64.
+Not implemented, and refused loudly: ``refinement_step > 0`` (RMSprop vertex refinement, extracting.py:237-323) and
+``mask_loader`` (needs skimage morphology, extracting.py:326-377).
+"""
+import os
+import re
+import time
+
+import numpy as np
+import torch
+
+PAD_VALUE = -1e6
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_TABLE = None
+
+# the lattice edge cube edge e lies on: owning corner offset (dx, dy, dz) and axis
+EDGE_OWNER = np.array([[0, 0, 0, 0], [1, 0, 0, 1], [0, 1, 0, 0], [0, 0, 0, 1], [0, 0, 1, 0], [1, 0, 1, 1],
+                       [0, 1, 1, 0], [0, 0, 1, 1], [0, 0, 0, 2], [1, 0, 0, 2], [1, 1, 0, 2], [0, 1, 0, 2]], dtype=np.int64)
+CORNERS = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]], dtype=np.int64)
+
+
+def mc_table():
+    """(n_tri uint8 [256], tri int8 [256, 16]) parsed from csrc/mc_table.h -- the one table both paths use."""
+    global _TABLE
+    if _TABLE is None:
+        text = open(os.path.join(_HERE, '..', 'csrc', 'mc_table.h')).read()
+        text = re.sub(r'//[^\n]*', '', text)
+        m1 = re.search(r'PSN_MC_NTRI\[256\]\s*=\s*\{(.*?)\};', text, re.S)
+        m2 = re.search(r'PSN_MC_TRI\[256\]\[16\]\s*=\s*\{(.*)\};', text, re.S)
+        ntri = np.array([int(x) for x in re.findall(r'-?\d+', m1.group(1))], dtype=np.uint8)
+        tri = np.array([int(x) for x in re.findall(r'-?\d+', m2.group(1))], dtype=np.int8).reshape(256, 16)
+        assert ntri.shape == (256,) and all(int((tri[c] >= 0).sum()) == 3 * int(ntri[c]) for c in range(256))
+        _TABLE = (ntri, tri)
+    return _TABLE
+
+
+def iso_value(threshold):
+    """extracting.py:83: the logit of the occupancy threshold, in double."""
+    return float(np.log(threshold) - np.log(1. - threshold))
+
+
+def grid_points_host(idx, resolution, box_size):
+    """extracting.py:105-108 for integer lattice points [Q, 3] -> float32 points [Q, 3]."""
+    p = torch.as_tensor(np.asarray(idx)).to(torch.float32)
+    p = p / np.float32(resolution)
+    return np.float32(box_size) * (p - 0.5)
+
+
+# ------------------------------------------------------------------------------------------------ host path: MISE
+class HostMISE(object):
+    """mise.pyx restated on dense numpy arrays: ``flags`` [n, n, n] (0 no grid point, 1 pending, 2 known), ``values`` float32
+    [n, n, n] (NaN = hole), one state array per level < depth (0 absent, 1 leaf, 2 split).  query() / update() as the reference;
+    a round tests the levels finest first, so voxels created in a round are first tested in the next one."""
+
+    def __init__(self, resolution0, depth, threshold):
+        self.resolution0, self.depth, self.threshold = int(resolution0), int(depth), float(threshold)
+        self.resolution = self.resolution0 << self.depth
+        n = self.resolution + 1
+        self.values = np.full((n, n, n), np.nan, dtype=np.float32)
+        self.flags = np.zeros((n, n, n), dtype=np.uint8)
+        s = 1 << self.depth
+        self.flags[::s, ::s, ::s] = 1                                              # mise.pyx:76-86
+        self.vox = [np.zeros((self.resolution0 << l,) * 3, dtype=np.uint8) for l in range(self.depth)]
+        if self.depth > 0:
+            self.vox[0][:] = 1                                                     # mise.pyx:58-73
+
+    def query(self):
+        """mise.pyx:107-129: the grid points without a value, int64 [Q, 3]."""
+        return np.argwhere(self.flags == 1).astype(np.int64)
+
+    def update(self, points, values):
+        """mise.pyx:88-105: set the values, then subdivide the active voxels."""
+        points = np.asarray(points)
+        self.values[points[:, 0], points[:, 1], points[:, 2]] = np.asarray(values, dtype=np.float32)
+        self.flags[points[:, 0], points[:, 1], points[:, 2]] = 2
+        self.refine()
+
+    @staticmethod
+    def _window_any(a, s):
+        """any() over the closed windows [i s, i s + s] along every axis of a boolean (m s + 1)^3 array -> [m, m, m]."""
+        for axis in range(3):
+            a = np.moveaxis(a, axis, 0)
+            m = (a.shape[0] - 1) // s
+            body = a[:-1].reshape((m, s) + a.shape[1:]).any(axis=1)
+            a = np.moveaxis(body | a[s::s], 0, axis)
+        return a
+
+    def refine(self):
+        """mise.pyx:185-282.  Returns the number of grid points that became pending."""
+        known = self.flags == 2
+        v = self.values.astype(np.float64)
+        with np.errstate(invalid='ignore'):
+            ge = known & (v >= self.threshold)                                     # mise.pyx:216-219, both non-strict
+            le = known & (v <= self.threshold)
+        new = 0
+        for l in range(self.depth - 1, -1, -1):
+            s = 1 << (self.depth - l)
+            active = (self.vox[l] == 1) & self._window_any(ge, s) & self._window_any(le, s)
+            if not active.any():
+                continue
+            self.vox[l][active] = 2
+            if l + 1 < self.depth:
+                child = np.repeat(np.repeat(np.repeat(active, 2, 0), 2, 1), 2, 2)
+                self.vox[l + 1][child] = 1
+            h = s >> 1
+            base = np.argwhere(active) * s
+            for d in range(27):                                                    # mise.pyx:269-281
+                q = base + np.array([d // 9, (d // 3) % 3, d % 3]) * h
+                f = self.flags[q[:, 0], q[:, 1], q[:, 2]]
+                q = q[f == 0]
+                new += int(len(np.unique(q, axis=0))) if len(q) else 0
+                self.flags[q[:, 0], q[:, 1], q[:, 2]] = 1
+        return new
+
+    def to_dense(self):
+        return host_ffill(self.values.copy())
+
+
+def host_ffill(grid):
+    """mise.pyx:143-164: holes (NaN) take their predecessor's value along x, then along y, then along z.  In place."""
+    n = grid.shape[0]
+    for axis in range(3):
+        g = np.moveaxis(grid, axis, 0)
+        for q in range(1, n):
+            hole = np.isnan(g[q])
+            g[q][hole] = g[q - 1][hole]
+    return grid
+
+
+# ------------------------------------------------------------------------------------------------ host path: marching cubes
+def host_marching_cubes(grid, threshold):
+    """marchingcubes.h:23-193 on ``grid`` padded with -1e6 (extracting.py:170-171) -> (vertices float64 [V, 3] in units of the
+    padded lattice, faces int64 [F, 3]).  Vertices ascending by (owning lattice point x-major, axis), faces by (cell x-major,
+    table order).  The iso crossing is formed in double as marchingcubes.cpp:290-297 does, x edges from their upper end
+    (marchingcubes.h:78), y and z edges from their lower end (:84, :90)."""
+    ntri_tab, tri_tab = mc_table()
+    thr = float(threshold)
+    P = np.pad(np.asarray(grid, dtype=np.float64), 1, 'constant', constant_values=PAD_VALUE)
+    N = P.shape[0]
+    M = N - 1
+    inside = P <= thr
+    cube = np.zeros((M, M, M), dtype=np.int64)
+    for c in range(8):
+        dx, dy, dz = CORNERS[c]
+        cube |= inside[dx:dx + M, dy:dy + M, dz:dz + M].astype(np.int64) << c
+    b0 = cube & 1
+    vmask = (((cube >> 1) & 1) != b0) * 1 + (((cube >> 3) & 1) != b0) * 2 + (((cube >> 4) & 1) != b0) * 4
+    vcount = ((vmask & 1) + ((vmask >> 1) & 1) + ((vmask >> 2) & 1)).ravel()
+    voff = np.cumsum(vcount) - vcount
+    n_v = int(vcount.sum())
+    vertices = np.zeros((n_v, 3), dtype=np.float64)
+    vm = vmask.ravel()
+    for a in range(3):
+        sel = np.nonzero((vm >> a) & 1)[0]
+        p = np.stack(np.unravel_index(sel, (M, M, M)), axis=1)
+        q = p.copy()
+        q[:, a] += 1
+        f0, fq = P[p[:, 0], p[:, 1], p[:, 2]], P[q[:, 0], q[:, 1], q[:, 2]]
+        lo, hi = p[:, a].astype(np.float64), q[:, a].astype(np.float64)
+        (x1, x2, f1, f2) = (hi, lo, fq, f0) if a == 0 else (lo, hi, f0, fq)
+        pos = (x2 - x1) * (thr - f1) / (f2 - f1) + x1
+        at = voff[sel] + (((vm[sel] & ((1 << a) - 1)) & 1) + ((vm[sel] & ((1 << a) - 1)) >> 1))
+        out = p.astype(np.float64)
+        out[:, a] = pos
+        vertices[at] = out
+    ntri = ntri_tab[cube.ravel()].astype(np.int64)
+    toff = np.cumsum(ntri) - ntri
+    faces = np.zeros((int(ntri.sum()), 3), dtype=np.int64)
+    cflat = cube.ravel()
+    for t in range(int(ntri.max()) if ntri.size else 0):
+        sel = np.nonzero(ntri > t)[0]
+        p = np.stack(np.unravel_index(sel, (M, M, M)), axis=1)
+        for c in range(3):
+            e = tri_tab[cflat[sel], 3 * t + c].astype(np.int64)
+            o = p + EDGE_OWNER[e, :3]
+            oc = (o[:, 0] * M + o[:, 1]) * M + o[:, 2]
+            low = vm[oc] & ((1 << EDGE_OWNER[e, 3]) - 1)
+            faces[toff[sel] + t, c] = voff[oc] + (low & 1) + (low >> 1)
+    return vertices, faces
+
+
+def to_world(vertices, n, box_size):
+    """extracting.py:175-181 for vertices in units of the padded lattice (the reference's own +0.5 is cancelled by its -0.5)."""
+    v = vertices - 1.0
+    v = v / np.array([n - 1, n - 1, n - 1], dtype=np.float64)
+    return box_size * (v - 0.5)
+
+
+# ------------------------------------------------------------------------------------------------ mesh container
+class Mesh(object):
+    """What the extraction returns: vertices float64 [V, 3], faces int64 [F, 3], optional vertex normals.  Stands in for
+    trimesh.Trimesh(vertices, faces, vertex_normals=normals, process=False) as far as extract_mesh.py uses it."""
+
+    def __init__(self, vertices, faces, vertex_normals=None):
+        self.vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+        self.faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+        self.vertex_normals = None if vertex_normals is None else np.asarray(vertex_normals).reshape(-1, 3)
+
+    @property
+    def is_empty(self):
+        return self.vertices.shape[0] == 0
+
+    def export(self, path):
+        ext = os.path.splitext(path)[1].lower()
+        if ext == '.obj':
+            with open(path, 'w') as f:
+                for v in self.vertices:
+                    f.write('v %.17g %.17g %.17g\n' % tuple(v))
+                if self.vertex_normals is not None:
+                    for v in self.vertex_normals:
+                        f.write('vn %.9g %.9g %.9g\n' % tuple(v))
+                for t in self.faces + 1:
+                    if self.vertex_normals is not None:
+                        f.write('f %d//%d %d//%d %d//%d\n' % (t[0], t[0], t[1], t[1], t[2], t[2]))
+                    else:
+                        f.write('f %d %d %d\n' % tuple(t))
+        elif ext == '.ply':
+            props = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if self.vertex_normals is not None else [])
+            head = ['ply', 'format binary_little_endian 1.0', 'element vertex %d' % self.vertices.shape[0]]
+            head += ['property float %s' % p for p in props]
+            head += ['element face %d' % self.faces.shape[0], 'property list uchar int vertex_indices', 'end_header']
+            vert = self.vertices.astype('<f4')
+            if self.vertex_normals is not None:
+                vert = np.concatenate([vert, self.vertex_normals.astype('<f4')], axis=1)
+            rec = np.empty(self.faces.shape[0], dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+            rec['n'] = 3
+            rec['i'] = self.faces
+            with open(path, 'wb') as f:
+                f.write(('\n'.join(head) + '\n').encode('ascii'))
+                f.write(np.ascontiguousarray(vert).tobytes())
+                f.write(rec.tobytes())
+        else:
+            raise NotImplementedError('Mesh.export: %r (supported: .obj, .ply)' % ext)
+        return path
+
+
+class _Phase(object):
+    """``with _Phase(log, name):`` brackets device work with HIP events when ``log`` is a list (tools/bench_mesh.py)."""
+
+    def __init__(self, log, name):
+        self.log, self.name = log, name
+
+    def __enter__(self):
+        if self.log is not None:
+            self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.e0.record()
+        return self
+
+    def __exit__(self, *exc):
+        if self.log is not None and exc[0] is None:
+            self.e1.record()
+            self.log.append((self.name, self.e0, self.e1))
+        return False
+
+
+# ------------------------------------------------------------------------------------------------ the extractor
+class Extractor3D(object):
+    """extracting.py:15-52, same constructor and methods."""
+
+    def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0, device=None, resolution0=16,
+                 upsampling_steps=3, with_normals=False, padding=0.4, refine_max_faces=10000):
+        if device is None and isinstance(model, torch.nn.Module):
+            device = next(model.parameters()).device   # (the reference leaves the model where it is; so do we, and follow it)
+        self.model = model.to(device) if (model is not None and hasattr(model, 'to')) else model
+        self.points_batch_size = points_batch_size
+        self.refinement_step = refinement_step
+        self.threshold = threshold
+        self.device = torch.device(device) if device is not None else torch.device('cpu')
+        self.resolution0 = resolution0
+        self.upsampling_steps = upsampling_steps
+        self.with_normals = with_normals
+        self.padding = padding
+        self.refine_max_faces = refine_max_faces
+        self.last_grid = None   # the dense value grid of the last generate_* call (device tensor or numpy array)
+        self.phase_events = None  # a list: (phase, start event, end event) of the device phases are appended (measurement runs)
+        self.last_known = None  # which of its points were evaluated (bool, same shape; None without upsampling: all of them)
+
+    # -- reference API ------------------------------------------------------------------------------------------------
+    def generate_mesh(self, data=None, return_stats=True, mask_loader=None, clip=False):
+        """extracting.py:54-72 -> (mesh, stats_dict)."""
+        if hasattr(self.model, 'eval'):
+            self.model.eval()
+        stats_dict = {}
+        mesh = self.generate_from_latent(None, stats_dict=stats_dict, data=None, mask_loader=mask_loader, clip=clip)
+        return mesh, stats_dict
+
+    def generate_from_latent(self, c=None, stats_dict=None, data=None, mask_loader=None, **kwargs):
+        """extracting.py:75-135."""
+        stats_dict = {} if stats_dict is None else stats_dict
+        if self.refinement_step > 0:
+            raise NotImplementedError('Extractor3D: refinement_step > 0 (RMSprop refinement of the vertices, reference '
+                                      'extracting.py:237-323) is not implemented; every shipped config uses 0')
+        if mask_loader is not None:
+            raise NotImplementedError('Extractor3D: mask_loader (carving by dilated image masks, reference extracting.py:120-127, '
+                                      '326-377) is not implemented: it needs skimage.morphology')
+        kwargs.setdefault('clip', False)
+        threshold = iso_value(self.threshold)
+        box_size = 2 + self.padding
+        on_device = self.device.type == 'cuda'
+        t0 = time.time()
+        self.last_known = None
+        if self.upsampling_steps == 0:                                             # extracting.py:90-96
+            nx = self.resolution0
+            pointsf = box_size * _make_3d_grid(nx)
+            values = self.eval_points(pointsf.to(self.device), c, **kwargs)
+            value_grid = values.reshape(nx, nx, nx).to(torch.float32)
+            value_grid = value_grid.contiguous() if on_device else value_grid.cpu().numpy()
+            stats_dict['n_points_evaluated'], stats_dict['n_rounds'] = nx ** 3, 1
+        elif on_device:
+            value_grid = self._mise_device(threshold, box_size, stats_dict, **kwargs)
+        else:
+            value_grid = self._mise_host(threshold, box_size, stats_dict, **kwargs)
+        if on_device:
+            torch.cuda.synchronize(self.device)
+        stats_dict['time (eval points)'] = time.time() - t0
+        if kwargs['clip']:                                                         # extracting.py:130-132
+            n = value_grid.shape[0]
+            z = box_size * torch.linspace(-0.5, 0.5, n)                            # the z coordinate of make_3d_grid
+            below = z < -1
+            if on_device:
+                value_grid[:, :, below.to(self.device)] = -30.0
+            else:
+                value_grid[:, :, below.numpy()] = -30.0
+        self.last_grid = value_grid
+        return self.extract_mesh(value_grid, c, stats_dict=stats_dict)
+
+    def eval_points(self, p, c=None, **kwargs):
+        """extracting.py:137-155: the model's negated logits at p [Q, 3], in batches; returned on p's device."""
+        outs = []
+        pack = self._lean_pack() if self.device.type == 'cuda' else None
+        for pi in torch.split(p, self.points_batch_size):
+            if pack is not None:   # the lean engine on the batch (no scatter: the caller wants the values in order)
+                outs.append(pack.on_points(pi.to(self.device).contiguous(), self.model.octaves_pe, 1.0 / self.model.rescale).reshape(-1))
+                continue
+            with torch.no_grad():
+                occ_hat = self.model(pi.unsqueeze(0).to(self.device), None, return_logits=True, **kwargs).squeeze(-1)
+            outs.append(occ_hat.squeeze(0).detach())
+        return torch.cat(outs, dim=0) if outs else torch.zeros(0, device=self.device)
+
+    def extract_mesh(self, occ_hat, c=None, stats_dict=None):
+        """extracting.py:157-206: marching cubes on the padded grid, vertices to world units, optional normals."""
+        stats_dict = {} if stats_dict is None else stats_dict
+        box_size = 2 + self.padding
+        threshold = iso_value(self.threshold)
+        n = occ_hat.shape[0]
+        assert tuple(occ_hat.shape) == (n, n, n), 'cubic value grids only'
+        t0 = time.time()
+        if torch.is_tensor(occ_hat) and occ_hat.is_cuda:
+            from .. import hip
+            with _Phase(self.phase_events, 'marching cubes'):
+                v, f = hip.marching_cubes(occ_hat.contiguous(), threshold, box_size)
+            with _Phase(self.phase_events, 'copy-back'):
+                vertices, faces = v.cpu().numpy(), f.cpu().numpy()
+        else:
+            grid = occ_hat.numpy() if torch.is_tensor(occ_hat) else np.asarray(occ_hat)
+            vertices, faces = host_marching_cubes(grid, threshold)
+            vertices = to_world(vertices, n, box_size)
+        stats_dict['time (marching cubes)'] = time.time() - t0
+        normals = None
+        if self.with_normals and vertices.shape[0] != 0:
+            t0 = time.time()
+            normals = self.estimate_normals(vertices, c)
+            stats_dict['time (normals)'] = time.time() - t0
+        return Mesh(vertices, faces, vertex_normals=normals)
+
+    def estimate_normals(self, vertices, c=None):
+        """extracting.py:209-235: -grad occupancy-logit / |.| at the vertices, through the model's ``gradient``."""
+        normals = []
+        for vi in torch.split(torch.as_tensor(np.asarray(vertices), dtype=torch.float32), self.points_batch_size):
+            g = self.model.gradient(vi.unsqueeze(0).to(self.device), tflag=False).reshape(-1, 3)
+            ni = -g
+            ni = ni / torch.norm(ni, dim=-1, keepdim=True)
+            normals.append(ni.cpu().numpy())
+        return np.concatenate(normals, axis=0)
+
+    # -- the two MISE drivers -------------------------------------------------------------------------------------------
+    def _mise_host(self, threshold, box_size, stats_dict, **kwargs):
+        mise = HostMISE(self.resolution0, self.upsampling_steps, threshold)
+        n_eval = n_rounds = 0
+        points = mise.query()
+        while points.shape[0] != 0:                                                # extracting.py:101-116
+            pointsf = grid_points_host(points, mise.resolution, box_size)
+            values = self.eval_points(pointsf, None, **kwargs).cpu().numpy()
+            mise.update(points, values)
+            n_eval += points.shape[0]
+            n_rounds += 1
+            points = mise.query()
+        stats_dict['n_points_evaluated'], stats_dict['n_rounds'] = n_eval, n_rounds
+        self.last_known = mise.flags == 2
+        return mise.to_dense()
+
+    def _lean_pack(self):
+        """The negated-logit pack of the lean engine if the model is a NeuralNetwork that engine holds, else None."""
+        from .network import NeuralNetwork
+        from .. import ops
+        m = self.model
+        if not isinstance(m, NeuralNetwork):
+            return None
+        if m._hidden_is_256() and m.d_pe <= 64 and m.lin0.weight_v.is_cuda:
+            return m._logit_packed()
+        ops.fallback('stage1 mesh extraction -> batched model calls', m.lin0.weight_v, 'hidden width is not 256')
+        return None
+
+    def _mise_device(self, threshold, box_size, stats_dict, **kwargs):
+        from .. import hip
+        dev = self.device
+        res0, depth = int(self.resolution0), int(self.upsampling_steps)
+        res = res0 << depth
+        if res > hip.MESH_MAX_RESOLUTION:
+            raise RuntimeError('Extractor3D: resolution %d > %d is not supported' % (res, hip.MESH_MAX_RESOLUTION))
+        n = res + 1
+        pack = self._lean_pack()
+        grid = torch.full((n * n * n,), float('nan'), dtype=torch.float32, device=dev)
+        flags = hip.mise_flags(res, dev)
+        s = 1 << depth
+        flags[:n * n * n].view(n, n, n)[::s, ::s, ::s] = 1
+        vox = torch.zeros(sum((res0 << l) ** 3 for l in range(depth)), dtype=torch.uint8, device=dev)
+        vox[:res0 ** 3] = 1
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        n_pending = (res0 + 1) ** 3
+        n_eval = n_rounds = 0
+        while n_pending > 0:
+            with _Phase(self.phase_events, 'collect + evaluate'):
+                rows, points = hip.mise_collect(flags, res, box_size, n_pending, counts[0:1])
+                if pack is not None:
+                    pack.on_points(points, self.model.octaves_pe, 1.0 / self.model.rescale, out=grid, n_rows_dev=counts[0:1],
+                                   out_rows=rows)
+                else:
+                    grid[rows] = self.eval_points(points, None, **kwargs).to(torch.float32)
+            with _Phase(self.phase_events, 'refine'):
+                hip.mise_refine(grid, flags, vox, res0, depth, threshold, counts[1:2])
+            n_eval += n_pending
+            n_rounds += 1
+            n_pending = int(counts[1].item())                                      # the round's only host synchronisation
+        stats_dict['n_points_evaluated'], stats_dict['n_rounds'] = n_eval, n_rounds
+        grid = grid.view(n, n, n)
+        self.last_known = (flags[:n * n * n] == 2).view(n, n, n)
+        with _Phase(self.phase_events, 'fill'):
+            hip.grid_ffill(grid)
+        return grid
+
+
+def _make_3d_grid(nx):
+    """common.py make_3d_grid((-0.5,)*3, (0.5,)*3, (nx,)*3): [nx^3, 3], x-major."""
+    ax = torch.linspace(-0.5, 0.5, nx)
+    px = ax.view(-1, 1, 1).expand(nx, nx, nx).contiguous().view(-1)
+    py = ax.view(1, -1, 1).expand(nx, nx, nx).contiguous().view(-1)
+    pz = ax.view(1, 1, -1).expand(nx, nx, nx).contiguous().view(-1)
+    return torch.stack([px, py, pz], dim=1)

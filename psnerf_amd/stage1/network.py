@@ -223,6 +223,18 @@ class NeuralNetwork(nn.Module):
             self._packed_key = key
         return self._packed
 
+    def _logit_packed(self):
+        """The negated-logit pack of the exact-fp32 lean engine (fused.pack_geo_logit): the value function of the mesh extraction
+        (stage1/extracting.py), cached by parameter version like the occupancy pack."""
+        key = self._params_key()
+        if getattr(self, '_packed_logit', None) is None or self._packed_logit_key != key:
+            with torch.no_grad():
+                Ws = self._effective('lin', self.n_geo, [1.0] * self.n_geo)
+                bs = [getattr(self, 'lin%d' % l).bias for l in range(self.n_geo)]
+                self._packed_logit = fused.pack_geo_logit(Ws, bs, self.skips, self.d_pe)
+            self._packed_logit_key = key
+        return self._packed_logit
+
     def _occupancy_packed_x3(self):
         """The occupancy network for the split-bf16 engine (opt-in: ``inference_precision = 'bf16x6'``; gradient-free queries
         only -- shadow rays, ray march, shape_extract; rendering.py:378-523): fp32-class arithmetic on the bf16 matrix pipe."""

@@ -1,0 +1,67 @@
+#!/usr/bin/env python
+"""Extract the surface of a trained stage-1 model as a mesh: the reference's stage1/extract_mesh.py with its arguments.
+
+    python tools/extract_mesh.py --obj_name bear --expname test_1 [--exp_folder out] [--test_out_dir test_out]
+                                 [--load_iter N] [--upsampling-steps S] [--mesh_extension obj|ply] [--clip]
+
+reads <exp_folder>/<obj_name>/<expname>/config.yaml and models/model[_N].pt, writes <test_out_dir>/<obj_name>/<expname>/mesh.<ext>.
+On a GPU the whole extraction runs on the device (psnerf_amd/stage1/extracting.py); --no-cuda takes the numpy host path with the
+model evaluated by the CPU oracle."""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description='Extract meshes from occupancy process.')
+    parser.add_argument('--gpu', default=0, type=int, help='gpu')
+    parser.add_argument('--no-cuda', action='store_true', help='Do not use cuda.')
+    parser.add_argument('--upsampling-steps', type=int, default=-1, help='Overrites the default upsampling steps in config')
+    parser.add_argument('--refinement-step', type=int, default=-1, help='Overrites the default refinement steps in config')
+    parser.add_argument('--obj_name', type=str, default='bunny')
+    parser.add_argument('--expname', type=str, default='test_1')
+    parser.add_argument('--exp_folder', type=str, default='out')
+    parser.add_argument('--test_out_dir', type=str, default='test_out')
+    parser.add_argument('--load_iter', type=int, default=None)
+    parser.add_argument('--mesh_extension', type=str, default='obj')
+    parser.add_argument('--clip', action='store_true', default=False, help='clip the bottom area')
+    args = parser.parse_args(argv)
+
+    torch.manual_seed(0)
+    from psnerf_amd.checkpoints import CheckpointIO
+    from psnerf_amd.stage1 import config
+    from psnerf_amd.stage1.extracting import Extractor3D
+    out_dir = os.path.join(args.exp_folder, args.obj_name, args.expname)
+    cfg = config.load_config(os.path.join(out_dir, 'config.yaml'))
+    is_cuda = torch.cuda.is_available() and not args.no_cuda
+    device = torch.device('cuda:%d' % args.gpu if is_cuda else 'cpu')
+    if args.upsampling_steps != -1:
+        cfg['extraction']['upsampling_steps'] = args.upsampling_steps
+    if is_cuda:
+        from psnerf_amd.stage1 import NeuralNetwork
+    else:
+        from oracle.stage1 import NeuralNetwork  # the same state_dict keys, plain torch on the host
+    model = NeuralNetwork(cfg)
+    CheckpointIO(os.path.join(out_dir, 'models'), model=model).load('model_%d.pt' % args.load_iter if args.load_iter else 'model.pt')
+    generator = Extractor3D(model, resolution0=cfg['extraction']['resolution'], upsampling_steps=cfg['extraction']['upsampling_steps'],
+                            refinement_step=max(args.refinement_step, 0), device=device)
+    model.eval()
+    test_out_path = os.path.join(args.test_out_dir, args.obj_name, args.expname)
+    os.makedirs(test_out_path, exist_ok=True)
+    t0 = time.time()
+    mesh, stats = generator.generate_mesh(mask_loader=None, clip=args.clip)
+    mesh_out_file = os.path.join(test_out_path, 'mesh.%s' % args.mesh_extension)
+    mesh.export(mesh_out_file)
+    print('%s: %d vertices, %d faces, %d points evaluated in %d rounds, %.2f s' % (
+        mesh_out_file, len(mesh.vertices), len(mesh.faces), stats['n_points_evaluated'], stats['n_rounds'], time.time() - t0))
+    return mesh_out_file
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,149 @@
+#!/usr/bin/env python
+"""Write the mesh-extraction fixtures under tests/golden/ from the REFERENCE's own native libraries.
+
+Needs the reference checkout (argument or $PSNERF_REFERENCE), a C++ compiler and Cython.  The sources of its two libraries
+(stage1/utils/libmise: multi-resolution iso-surface refinement; stage1/utils/libmcubes: marching cubes) are copied to a
+temporary directory OUTSIDE this repository, built there, run on the fields of tests/mesh_fields.py, and only their RESULTS
+are stored:
+  mesh_mc_cases.npz   vertices / faces of marching_cubes for the 256 sign patterns of one 2 x 2 x 2 volume (values -+1)
+  mesh_mise_r32.npz   resolution0 8, depth 2: known points, to_dense grid (float32), vertices (float64) and faces of the padded
+                      marching cubes; plus the marching cubes of a random +- grid (mesh_fields.checker) that visits every
+                      ambiguous-face configuration
+  mesh_mise_r64.json  resolution0 16, depth 2: digests only
+
+    python tools/gen_golden_mesh.py /path/to/reference
+"""
+import hashlib
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GOLDEN = os.path.join(ROOT, 'tests', 'golden')
+
+SETUP = '''
+import numpy
+from setuptools import setup, Extension
+from Cython.Build import cythonize
+defs = [('PyArray_DOUBLE', 'NPY_DOUBLE'), ('PyArray_ULONG', 'NPY_ULONG'), ('PyArray_LONG', 'NPY_LONG'), ('PyArray_INT', 'NPY_INT'),
+        ('PyArray_FLOAT', 'NPY_FLOAT'), ('PyArray_UINT', 'NPY_UINT'), ('PyArray_BOOL', 'NPY_BOOL')]
+args = ['-std=c++11', '-fpermissive', '-ffp-contract=off', '-w']
+exts = [Extension('utils.libmise.mise', ['utils/libmise/mise.pyx'], language='c++', include_dirs=[numpy.get_include()], extra_compile_args=args),
+        Extension('utils.libmcubes.mcubes', ['utils/libmcubes/mcubes.pyx', 'utils/libmcubes/pywrapper.cpp', 'utils/libmcubes/marchingcubes.cpp'],
+                  language='c++', include_dirs=[numpy.get_include(), 'utils/libmcubes'], define_macros=defs, extra_compile_args=args)]
+setup(name='ref_mesh', ext_modules=cythonize(exts, language_level=3), script_args=['build_ext', '--inplace'])
+'''
+
+
+def build_reference(ref):
+    tmp = tempfile.mkdtemp(prefix='psnerf_ref_mesh_')
+    assert not os.path.abspath(tmp).startswith(ROOT + os.sep)
+    os.makedirs(os.path.join(tmp, 'utils'))
+    open(os.path.join(tmp, 'utils', '__init__.py'), 'w').close()
+    for lib in ('libmise', 'libmcubes'):
+        src = os.path.join(ref, 'stage1', 'utils', lib)
+        dst = os.path.join(tmp, 'utils', lib)
+        os.makedirs(dst)
+        for name in os.listdir(src):
+            if name.endswith(('.pyx', '.cpp', '.h', '.py')) and name not in ('setup.py', 'mcubes.cpp', 'test.py'):
+                shutil.copy(os.path.join(src, name), dst)
+    with open(os.path.join(tmp, 'build_ref.py'), 'w') as f:
+        f.write(SETUP)
+    subprocess.check_call([sys.executable, 'build_ref.py'], cwd=tmp)
+    sys.path.insert(0, tmp)
+    return tmp
+
+
+def reference_extract(field, resolution0, depth, thr=0.0):
+    """extracting.py:98-119 + 170-178 with the reference's libraries and a look-up of ``field`` -> dict of results."""
+    from utils.libmise import MISE
+    from utils import libmcubes
+    mise = MISE(resolution0, depth, thr)
+    rounds, known = [], []
+    points = mise.query()
+    while points.shape[0] != 0:
+        values = field[points[:, 0], points[:, 1], points[:, 2]].astype(np.float64)
+        mise.update(points, values)
+        rounds.append(int(points.shape[0]))
+        known.append(points)
+        points = mise.query()
+    dense = mise.to_dense()
+    assert np.array_equal(dense, dense.astype(np.float32).astype(np.float64))
+    v, f = reference_mc(dense, thr)
+    return dict(rounds=rounds, known=np.concatenate(known, 0), dense=dense.astype(np.float32), vertices=v, faces=f)
+
+
+def reference_mc(grid, thr=0.0, pad=True):
+    """libmcubes.marching_cubes on the padded grid, its +0.5 shift removed: vertices in units of the (padded) lattice."""
+    from utils import libmcubes
+    g = np.asarray(grid, dtype=np.float64)
+    if pad:
+        g = np.pad(g, 1, 'constant', constant_values=-1e6)
+    v, f = libmcubes.marching_cubes(np.ascontiguousarray(g), thr)
+    return v - 0.5, f.astype(np.int64)
+
+
+def cube_histogram(grid, thr=0.0):
+    from psnerf_amd.stage1.extracting import CORNERS
+    P = np.pad(np.asarray(grid, dtype=np.float64), 1, 'constant', constant_values=-1e6)
+    M = P.shape[0] - 1
+    cube = np.zeros((M, M, M), dtype=np.int64)
+    for c in range(8):
+        dx, dy, dz = CORNERS[c]
+        cube |= (P[dx:dx + M, dy:dy + M, dz:dz + M] <= thr).astype(np.int64) << c
+    return np.bincount(cube.ravel(), minlength=256)
+
+
+def main():
+    ref = sys.argv[1] if len(sys.argv) > 1 else os.environ.get('PSNERF_REFERENCE')
+    assert ref and os.path.isdir(ref), 'usage: gen_golden_mesh.py /path/to/reference'
+    tmp = build_reference(ref)
+    try:
+        from tests import mesh_fields as mf
+        from psnerf_amd.stage1.extracting import CORNERS
+        # -- the 256 single-cell cases
+        vs, fs, voff, foff = [], [], [0], [0]
+        for case in range(256):
+            vol = np.ones((2, 2, 2), dtype=np.float64)
+            for m in range(8):
+                if (case >> m) & 1:
+                    vol[tuple(CORNERS[m])] = -1.0
+            v, f = reference_mc(vol, 0.0, pad=False)
+            vs.append(v.reshape(-1, 3)); fs.append(f.reshape(-1, 3))
+            voff.append(voff[-1] + len(vs[-1])); foff.append(foff[-1] + len(fs[-1]))
+        np.savez_compressed(os.path.join(GOLDEN, 'mesh_mc_cases.npz'), vertices=np.concatenate(vs, 0), faces=np.concatenate(fs, 0).astype(np.int32),
+                            v_off=np.array(voff, dtype=np.int32), f_off=np.array(foff, dtype=np.int32))
+        # -- R = 32, full
+        r = reference_extract(mf.sphere_rod_torus(32), 8, 2)
+        hist = cube_histogram(r['dense'])
+        print('R=32: rounds', r['rounds'], 'known', len(r['known']), 'of', 33 ** 3, 'vertices', len(r['vertices']), 'faces', len(r['faces']))
+        print('R=32: cube indices visited: %d of 256; missing %s' % ((hist > 0).sum(), np.nonzero(hist == 0)[0].tolist()))
+        chk = mf.checker(12)
+        cv, cf = reference_mc(chk)
+        print('checker: cube indices visited: %d of 256' % (cube_histogram(chk) > 0).sum())
+        np.savez_compressed(os.path.join(GOLDEN, 'mesh_mise_r32.npz'), known=r['known'].astype(np.int16), dense=r['dense'],
+                            vertices=r['vertices'], faces=r['faces'].astype(np.int32), rounds=np.array(r['rounds'], dtype=np.int32),
+                            checker_vertices=cv, checker_faces=cf.astype(np.int32))
+        # -- R = 64, digests
+        r = reference_extract(mf.sphere_rod_torus(64), 16, 2)
+        area, volume = mf.area_volume(r['vertices'], r['faces'])
+        dig = dict(resolution0=16, depth=2, rounds=r['rounds'], n_known=int(len(r['known'])),
+                   dense_sha256=hashlib.sha256(np.ascontiguousarray(r['dense'].astype('<f4')).tobytes()).hexdigest(),
+                   n_vertices=int(len(r['vertices'])), n_faces=int(len(r['faces'])), edges_sha256=mf.edges_digest(r['vertices']),
+                   area=area, signed_volume=volume)
+        print('R=64:', dig)
+        with open(os.path.join(GOLDEN, 'mesh_mise_r64.json'), 'w') as f:
+            json.dump(dig, f, indent=1, sort_keys=True)
+            f.write('\n')
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == '__main__':
+    main()
