@@ -804,6 +804,51 @@ int psn_mc_count(const float* grid, int n, double threshold, unsigned char* code
 int psn_mc_emit(const float* grid, int n, double threshold, const unsigned char* code, const int64_t* v_base, const int64_t* t_base,
                 int64_t n_vertices, int64_t n_faces, double box_size, int* v_off, double* vertices, int64_t* faces, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Mesh evaluation: the point-to-mesh query behind the reference's Chamfer distance (chamfer_dist.py:19-35,
+ * stage2/utils/metrics.py:79-113), i.e. what it asks of trimesh.proximity.closest_point (an r-tree on the host).  Here: a
+ * uniform grid of triangle lists over the mesh's bounding box, built and queried on the device, float64 throughout.
+ *   vertices  float64 [V, 3];  faces  int64 [F, 3], every index in 0 .. V - 1 (NOT checked here: the caller's duty),
+ *             1 <= F <= PSN_TRI_GRID_MAX_FACES.  Zero-area and duplicated triangles are allowed and take part with their true
+ *             distance (segment / point); no NaN arises from them.
+ *   PsnTriGrid (host memory): lo / hi = the exact minimum / maximum of the vertices per axis (mesh units); cell = edge of the
+ *             cubic cells (> 0, mesh units); n[a] = cells per axis, 1 .. PSN_TRI_GRID_MAX_CELLS_PER_AXIS, with
+ *             lo[a] + n[a] cell >= hi[a]; cell (i, j, k) has the linear index (i n[1] + j) n[2] + k.  max_span >= 1: a triangle
+ *             whose bounding box overlaps more cells than this is kept in the oversize list instead of the cell lists.
+ *   lists     int32 triangle ids.  The order within a cell's list and within the oversize list is not defined (atomics); the
+ *             query's result does not depend on it.
+ *
+ * psn_tri_grid_count: cell_count [cells] int32 (zeroed here) = per cell, the triangles whose bounding box overlaps it;
+ *   over_list [F] receives the oversize triangles, n_over[0] (set here) their number.
+ * psn_tri_grid_fill: cursor [cells] int32 = the exclusive scan of those counts (advanced here to the inclusive scan);
+ *   list [n_entries], n_entries = their total (< 2^31).
+ * psn_closest_point: cell_start [cells + 1] int32 = the exclusive scan with the total appended.  points float64 [Q, 3]; order =
+ *   null or a permutation of 0 .. Q - 1 in which the points are worked on (sorted by home cell keeps a wave's lanes in
+ *   neighbouring cells; outputs are written at the point's own row either way).  closest float64 [Q, 3], dist float64 [Q]
+ *   (Euclidean, mesh units), tri int64 [Q]: the minimum over ALL triangles of the distance to the triangle as the closed
+ *   convex hull of its corners, ties to the lowest triangle index -- bitwise reproducible.  The search walks shells of cells
+ *   around the point's (clamped) home cell and stops by an exact bound (csrc/meshdist.hip), also for points outside the
+ *   bounding box.  A point with a NaN coordinate gets NaN, NaN, -1.  n_tests: null, or an int64 counter to which the number
+ *   of point-triangle tests is added.  Q = 0 is a no-op.
+ * Errors: PSN_E_ARG for null pointers, F or Q out of range, a bad PsnTriGrid, n_entries >= 2^31; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_TRI_GRID_MAX_CELLS_PER_AXIS 256
+#define PSN_TRI_GRID_MAX_FACES 2147483646LL
+typedef struct {
+    double lo[3];
+    double hi[3];
+    double cell;
+    int n[3];
+    int max_span;
+} PsnTriGrid;
+int psn_tri_grid_count(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, int* cell_count,
+                       int* over_list, long long* n_over, void* stream);
+int psn_tri_grid_fill(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, int* cursor,
+                      int64_t n_entries, int* list, void* stream);
+int psn_closest_point(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
+                      const int* list, const int* over_list, int64_t n_over, const double* points, const int64_t* order,
+                      int64_t n_points, double* closest, double* dist, int64_t* tri, long long* n_tests, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

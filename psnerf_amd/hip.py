@@ -114,6 +114,10 @@ class PsnRowAdamItem(ctypes.Structure):
                 ('rows', i64), ('cols', i32), ('one_minus_beta1', f32), ('one_minus_beta2', f32), ('eps', f32), ('step_size', f32)]
 
 
+class PsnTriGrid(ctypes.Structure):
+    _fields_ = [('lo', ctypes.c_double * 3), ('hi', ctypes.c_double * 3), ('cell', ctypes.c_double), ('n', i32 * 3), ('max_span', i32)]
+
+
 MAX_GROUP = 12
 
 # every exported symbol of include/psnerf_hip.h with its signature
@@ -210,6 +214,9 @@ SIGNATURES = {
     'psn_mc_blocks': (i64, [i32]),
     'psn_mc_count': (i32, [c_f, i32, ctypes.c_double, c_f, c_f, c_f, c_f]),
     'psn_mc_emit': (i32, [c_f, i32, ctypes.c_double, c_f, c_f, c_f, i64, i64, ctypes.c_double, c_f, c_f, c_f, c_f]),
+    'psn_tri_grid_count': (i32, [c_f, c_f, c_f, i64, c_f, c_f, c_f, c_f]),
+    'psn_tri_grid_fill': (i32, [c_f, c_f, c_f, i64, c_f, i64, c_f, c_f]),
+    'psn_closest_point': (i32, [c_f, c_f, c_f, i64, c_f, c_f, c_f, i64, c_f, c_f, i64, c_f, c_f, c_f, c_f, c_f]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(_lib, _name)  # AttributeError here = library out of date: fail loudly
@@ -1629,3 +1636,73 @@ def marching_cubes(grid, threshold, box_size=0.0):
         _check(_lib.psn_mc_emit(_ptr(grid, 'grid'), n, float(threshold), code.data_ptr(), base[0].data_ptr(), base[1].data_ptr(), n_v, n_f,
                                 float(box_size), v_off.data_ptr(), vertices.data_ptr(), faces.data_ptr(), _stream()), 'mc_emit')
     return vertices, faces
+
+
+# --------------------------------------------------------------------------- point-to-mesh distance (csrc/meshdist.hip)
+TRI_GRID_MAX_CELLS_PER_AXIS = 256
+
+
+def tri_grid(lo, hi, cell, n, max_span):
+    """The host-side descriptor of the triangle grid (PsnTriGrid): bounding box, cell edge, cells per axis, oversize limit."""
+    g = PsnTriGrid()
+    for a in range(3):
+        g.lo[a], g.hi[a], g.n[a] = float(lo[a]), float(hi[a]), int(n[a])
+    g.cell, g.max_span = float(cell), int(max_span)
+    return g
+
+
+def _mesh_ptrs(vertices, faces):
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError('mesh: vertices [V, 3] and faces [F, 3] expected, got %s / %s' % (tuple(vertices.shape), tuple(faces.shape)))
+    return _tptr(vertices, 'vertices', torch.float64), _tptr(faces, 'faces', torch.int64)
+
+
+def tri_grid_count(grid, vertices, faces, n_over):
+    """Index build, first pass (psn_tri_grid_count) -> (cell_count int32 [cells], over_list int32 [F]); n_over (int64 [1] on the
+    device) receives the length of the oversize list."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    cells = grid.n[0] * grid.n[1] * grid.n[2]
+    assert n_over.numel() == 1
+    cell_count = torch.empty(cells, dtype=torch.int32, device=vertices.device)
+    over_list = torch.empty(faces.shape[0], dtype=torch.int32, device=vertices.device)
+    with _Prof('tri_grid_count', 96 * faces.shape[0]):
+        _check(_lib.psn_tri_grid_count(ctypes.byref(grid), vp, fp, faces.shape[0], cell_count.data_ptr(), over_list.data_ptr(),
+                                       _tptr(n_over, 'n_over', torch.int64), _stream()), 'tri_grid_count')
+    return cell_count, over_list
+
+
+def tri_grid_fill(grid, vertices, faces, cursor, n_entries):
+    """Index build, second pass (psn_tri_grid_fill): cursor (int32 [cells], the exclusive scan of the counts; advanced in place) ->
+    list int32 [n_entries]."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    assert cursor.numel() == grid.n[0] * grid.n[1] * grid.n[2]
+    lst = torch.empty(int(n_entries), dtype=torch.int32, device=vertices.device)
+    with _Prof('tri_grid_fill', 96 * faces.shape[0]):
+        _check(_lib.psn_tri_grid_fill(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cursor, 'cursor', torch.int32), int(n_entries),
+                                      lst.data_ptr(), _stream()), 'tri_grid_fill')
+    return lst
+
+
+def closest_point(grid, vertices, faces, cell_start, lst, over_list, n_over, points, order=None, n_tests=None):
+    """psn_closest_point: points float64 [Q, 3] -> (closest float64 [Q, 3], distance float64 [Q], triangle id int64 [Q]) over the whole
+    mesh; order = the permutation in which the points are worked on (or None); n_tests (int64 [1]) accumulates the number of
+    point-triangle tests."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError('closest_point: points [Q, 3] expected, got %s' % (tuple(points.shape),))
+    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
+    q = points.shape[0]
+    assert order is None or order.numel() == q
+    dev = vertices.device
+    closest = torch.empty(q, 3, dtype=torch.float64, device=dev)
+    dist = torch.empty(q, dtype=torch.float64, device=dev)
+    tri = torch.empty(q, dtype=torch.int64, device=dev)
+    if q == 0:
+        return closest, dist, tri
+    with _Prof('closest_point', q):
+        _check(_lib.psn_closest_point(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cell_start, 'cell_start', torch.int32),
+                                      _tptr(lst, 'list', torch.int32), _tptr(over_list, 'over_list', torch.int32), int(n_over),
+                                      _tptr(points, 'points', torch.float64), None if order is None else _tptr(order, 'order', torch.int64), q,
+                                      closest.data_ptr(), dist.data_ptr(), tri.data_ptr(),
+                                      None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'closest_point')
+    return closest, dist, tri

@@ -1,0 +1,478 @@
+"""Mesh evaluation: surface sampling, point-to-mesh distance and the reference's Chamfer distance (chamfer_dist.py:19-35 at the top
+of the reference tree; stage2/utils/metrics.py:79-113 is the same function with its raw outputs, and the one-sided
+``get_surface_dist``).  The reference does this with trimesh.sample.sample_surface + trimesh.proximity.closest_point (trimesh and
+rtree); neither is needed here.
+
+Two implementations of one definition, as in stage1/extracting.py:
+  * CPU inputs -> the vectorised numpy functions below (``host_*``), float64; they are the definition, and what the device path is
+    tested against.
+  * device tensors (or ``device='cuda'``) -> csrc/meshdist.hip through ``MeshIndex``: a uniform grid of triangle lists over the
+    mesh's bounding box (psn_tri_grid_count -> torch.cumsum -> psn_tri_grid_fill), then psn_closest_point, which walks shells of
+    cells around each query's home cell and stops by an exact bound.  Meshes, samples and distances stay on the device; the uniforms
+    of the sampler are drawn on the host from the caller's ``np.random.RandomState`` in the host path's order and uploaded, so both
+    paths consume the same stream.
+
+Definition.  distance(p, mesh) = min over ALL triangles of the Euclidean distance from p to the triangle as the closed convex
+hull of its three corners (Ericson, Real-Time Collision Detection, 5.1.5: the Voronoi-region test, which needs no division by the
+area).  Ties on the distance go to the lowest triangle index.
+Stated difference from the reference: trimesh yields NaN for degenerate (zero-area) triangles and the reference zeroes those
+distances (chamfer_dist.py:27-28); here such a triangle is the segment or point it degenerates to and takes part with its true
+distance, so no NaN arises and nothing is zeroed.
+Sampling is trimesh.sample.sample_surface as documented: faces with probability proportional to their area, a uniform point in
+the face from two uniforms with the reflection u + v > 1 -> (1 - u, 1 - v).  The distribution is the contract; the order of the
+draws (all face picks, then all (u, v) pairs) is this module's own.
+"""
+import os
+
+import numpy as np
+import torch
+
+from .stage1.extracting import Mesh
+
+_PAIRS_PER_CHUNK = 1 << 20   # host path: point-triangle pairs evaluated at a time (some forty float64 temporaries of that size)
+
+
+# ------------------------------------------------------------------------------------------------ host path: the definition
+def _dot(ax, ay, az, bx, by, bz):
+    return ax * bx + ay * by + az * bz
+
+
+def _segment(p, a, b):
+    """The point of segment [a, b] closest to p, per component (a zero-length segment is the point a)."""
+    e = [b[i] - a[i] for i in range(3)]
+    num = _dot(e[0], e[1], e[2], p[0] - a[0], p[1] - a[1], p[2] - a[2])
+    den = _dot(e[0], e[1], e[2], e[0], e[1], e[2])
+    s = np.where(den > 0.0, num / np.where(den > 0.0, den, 1.0), 0.0)
+    s = np.where(s < 0.0, 0.0, np.where(s > 1.0, 1.0, s))
+    return [a[i] + s * e[i] for i in range(3)]
+
+
+def _dist2(p, q):
+    dx, dy, dz = p[0] - q[0], p[1] - q[1], p[2] - q[2]
+    return dx * dx + dy * dy + dz * dz
+
+
+def _closest_on_triangles(p, a, b, c):
+    """Closest point of triangles (a, b, c) to points p; every argument a list of three broadcastable float64 arrays (x, y, z).
+    Ericson 5.1.5, operation for operation as csrc/meshdist.hip:md_closest -> list of three arrays."""
+    with np.errstate(all='ignore'):
+        ab = [b[i] - a[i] for i in range(3)]
+        ac = [c[i] - a[i] for i in range(3)]
+        ap = [p[i] - a[i] for i in range(3)]
+        d1, d2 = _dot(*ab, *ap), _dot(*ac, *ap)
+        bp = [p[i] - b[i] for i in range(3)]
+        d3, d4 = _dot(*ab, *bp), _dot(*ac, *bp)
+        cp = [p[i] - c[i] for i in range(3)]
+        d5, d6 = _dot(*ab, *cp), _dot(*ac, *cp)
+        vc = d1 * d4 - d3 * d2
+        vb = d5 * d2 - d1 * d6
+        va = d3 * d6 - d5 * d4
+        e43, e56 = d4 - d3, d5 - d6
+        r_a = (d1 <= 0.0) & (d2 <= 0.0)
+        r_b = (d3 >= 0.0) & (d4 <= d3)
+        r_c = (d6 >= 0.0) & (d5 <= d6)
+        # (an edge of zero length -- a repeated corner -- is no edge region: its test would pass trivially and return the corner)
+        r_ab = (vc <= 0.0) & (d1 >= 0.0) & (d3 <= 0.0) & (d1 - d3 > 0.0)
+        r_ac = (vb <= 0.0) & (d2 >= 0.0) & (d6 <= 0.0) & (d2 - d6 > 0.0)
+        r_bc = (va <= 0.0) & (e43 >= 0.0) & (e56 >= 0.0) & (e43 + e56 > 0.0)
+        v_ab = d1 / (d1 - d3)
+        w_ac = d2 / (d2 - d6)
+        w_bc = e43 / (e43 + e56)
+        s = va + vb + vc
+        v, w = vb / s, vc / s
+        r_in = (s > 0.0) & (v >= 0.0) & (w >= 0.0) & (v + w <= 1.0)
+        # the fall-back for what rounding lets through every test: the best of the three edges
+        q1, q2, q3 = _segment(p, a, b), _segment(p, a, c), _segment(p, b, c)
+        e1, e2, e3 = _dist2(p, q1), _dist2(p, q2), _dist2(p, q3)
+        use2 = e2 < e1
+        best = np.where(use2, e2, e1)
+        use3 = e3 < best
+        out = []
+        for i in range(3):
+            fb = np.where(use3, q3[i], np.where(use2, q2[i], q1[i]))
+            out.append(np.select([r_a, r_b, r_c, r_ab, r_ac, r_bc, r_in],
+                                 [a[i], b[i], c[i], a[i] + v_ab * ab[i], a[i] + w_ac * ac[i],
+                                  b[i] + w_bc * (c[i] - b[i]), a[i] + ab[i] * v + ac[i] * w], fb))
+        return out
+
+
+def _as_mesh_arrays(vertices, faces):
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+    if f.shape[0] and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError('mesh: a face refers to vertex %d of %d' % (int(f.max() if f.max() >= v.shape[0] else f.min()), v.shape[0]))
+    return v, f
+
+
+def host_point_triangle(vertices, faces, points, triangle_id):
+    """Closest point and distance from points [Q, 3] to the triangles triangle_id [Q] (one triangle per point) ->
+    (closest float64 [Q, 3], distance float64 [Q])."""
+    v, f = _as_mesh_arrays(vertices, faces)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    t = f[np.asarray(triangle_id, dtype=np.int64)]
+    p = [pts[:, i] for i in range(3)]
+    q = _closest_on_triangles(p, *[[v[t[:, k], i] for i in range(3)] for k in range(3)])
+    return np.stack(q, axis=1), np.sqrt(_dist2(p, q))
+
+
+def host_closest_point(vertices, faces, points):
+    """The return triple of trimesh.proximity.closest_point(mesh, points): (closest float64 [Q, 3], distance float64 [Q],
+    triangle_id int64 [Q]) by brute force over all triangles, in chunks of queries so that memory stays bounded.  Ties on the
+    distance go to the lowest triangle index.  Unlike trimesh, zero-area triangles take part with their true (segment / point)
+    distance and no NaN arises (see the module docstring)."""
+    v, f = _as_mesh_arrays(vertices, faces)
+    if f.shape[0] == 0:
+        raise ValueError('host_closest_point: the mesh has no faces')
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+    n_q = pts.shape[0]
+    tri_id = np.zeros(n_q, dtype=np.int64)
+    corners = [[v[f[:, k], i][None, :] for i in range(3)] for k in range(3)]
+    step = max(1, _PAIRS_PER_CHUNK // f.shape[0])
+    for q0 in range(0, n_q, step):
+        p = [pts[q0:q0 + step, i][:, None] for i in range(3)]
+        d2 = _dist2(p, _closest_on_triangles(p, *corners))
+        tri_id[q0:q0 + step] = np.argmin(d2, axis=1)            # (the first minimum: the lowest index)
+    closest, dist = host_point_triangle(v, f, pts, tri_id)
+    return closest, dist, tri_id
+
+
+def host_face_areas(vertices, faces):
+    v, f = _as_mesh_arrays(vertices, faces)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    ab, ac = b - a, c - a
+    nx = ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1]
+    ny = ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2]
+    nz = ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]
+    return 0.5 * np.sqrt(nx * nx + ny * ny + nz * nz)
+
+
+def _draw(rng, count):
+    """The uniforms of one sample_surface call, in this module's order: ``count`` face picks, then ``count`` (u, v) pairs."""
+    rng = np.random if rng is None else rng
+    pick = rng.random_sample(count)
+    uv = rng.random_sample((count, 2))
+    return pick, uv
+
+
+def host_sample_surface(vertices, faces, count, rng=None, return_cumulative=False):
+    """trimesh.sample.sample_surface(mesh, count) -> (points float64 [count, 3], face_index int64 [count]): faces drawn with
+    probability proportional to their area, a uniform point per draw.  ``rng``: an np.random.RandomState (default: the global
+    np.random, as the reference)."""
+    v, f = _as_mesh_arrays(vertices, faces)
+    if f.shape[0] == 0:
+        raise ValueError('host_sample_surface: the mesh has no faces')
+    pick, uv = _draw(rng, int(count))
+    area_cum = np.cumsum(host_face_areas(v, f))
+    face_index = np.minimum(np.searchsorted(area_cum, pick * area_cum[-1]), f.shape[0] - 1).astype(np.int64)
+    u, w = uv[:, 0], uv[:, 1]
+    flip = u + w > 1.0
+    u, w = np.where(flip, 1.0 - u, u), np.where(flip, 1.0 - w, w)
+    a, b, c = v[f[face_index, 0]], v[f[face_index, 1]], v[f[face_index, 2]]
+    points = a + u[:, None] * (b - a) + w[:, None] * (c - a)
+    return (points, face_index, area_cum) if return_cumulative else (points, face_index)
+
+
+# ------------------------------------------------------------------------------------------------ device path
+MAX_SPAN = 256      # a triangle whose bounding box overlaps more cells than this goes to the oversize list
+CELLS_PER_AXIS = 192   # at most 192^3 = 7.1 M cells: a 28 MB table of list starts
+
+
+class MeshIndex(object):
+    """A mesh on the device with its triangle grid: ``MeshIndex(vertices, faces).closest_point(points)``; one index serves any
+    number of queries.  vertices float64 [V, 3] / faces int64 [F, 3]: device tensors, or numpy arrays / CPU tensors that are moved
+    to ``device`` once.  Cell edge = max(mean triangle edge, largest box extent / CELLS_PER_AXIS); triangles that span more than
+    MAX_SPAN cells (a few long slivers of a scan) are kept in a short list that every query tests directly, so they neither fail
+    nor inflate the cell lists.  Two host reads while building: (bounding box, mean edge, index range) and the list totals."""
+
+    def __init__(self, vertices, faces, device=None, name='mesh', profile=False):
+        from . import hip
+        if not torch.is_tensor(vertices):
+            vertices = torch.as_tensor(np.asarray(vertices, dtype=np.float64))
+        if not torch.is_tensor(faces):
+            faces = torch.as_tensor(np.asarray(faces, dtype=np.int64))
+        if device is None:
+            device = vertices.device if vertices.is_cuda else torch.device('cuda')
+        self.vertices = vertices.to(device=device, dtype=torch.float64).reshape(-1, 3).contiguous()
+        self.faces = faces.to(device=device, dtype=torch.int64).reshape(-1, 3).contiguous()
+        if self.faces.shape[0] == 0 or self.vertices.shape[0] == 0:
+            raise ValueError('%s is empty (%d vertices, %d faces)' % (name, self.vertices.shape[0], self.faces.shape[0]))
+        v, f = self.vertices, self.faces
+        a, b, c = v[f[:, 0].clamp(0, v.shape[0] - 1)], v[f[:, 1].clamp(0, v.shape[0] - 1)], v[f[:, 2].clamp(0, v.shape[0] - 1)]
+        edge = ((b - a).norm(dim=1) + (c - b).norm(dim=1) + (a - c).norm(dim=1)).mean() / 3.0
+        head = torch.cat([v.min(dim=0).values, v.max(dim=0).values, edge.reshape(1), f.min().to(torch.float64).reshape(1),
+                          f.max().to(torch.float64).reshape(1)]).tolist()
+        lo, hi, mean_edge, f_min, f_max = head[0:3], head[3:6], head[6], int(head[7]), int(head[8])
+        if f_min < 0 or f_max >= v.shape[0]:
+            raise ValueError('%s: a face refers to vertex %d of %d' % (name, f_max if f_max >= v.shape[0] else f_min, v.shape[0]))
+        if not all(np.isfinite(lo + hi)):
+            raise ValueError('%s: a vertex coordinate is not finite' % name)
+        extent = [hi[i] - lo[i] for i in range(3)]
+        cell = max(mean_edge if np.isfinite(mean_edge) else 0.0, max(extent) / CELLS_PER_AXIS)
+        if not cell > 0.0:
+            cell = 1.0   # every vertex in one point
+        n = [int(min(CELLS_PER_AXIS, max(1, np.ceil(extent[i] / cell)))) for i in range(3)]
+        self.lo, self.hi, self.cell, self.n = lo, hi, cell, n
+        self.grid = hip.tri_grid(lo, hi, cell, n, MAX_SPAN)
+        self.build_events = [] if profile else None   # (phase, start event, end event) of the build (tools/bench_chamfer.py)
+        counts = torch.zeros(2, dtype=torch.int64, device=device)
+        with self._phase('count'):
+            cell_count, over_list = hip.tri_grid_count(self.grid, v, f, counts[0:1])
+        with self._phase('scan'):
+            incl = torch.cumsum(cell_count, dim=0, dtype=torch.int64)
+            counts[1] = incl[-1]
+        n_over, n_entries = (int(x) for x in counts.tolist())
+        if n_entries >= 2 ** 31:
+            raise RuntimeError('%s: %d cell-list entries do not fit 32-bit positions' % (name, n_entries))
+        with self._phase('scan'):
+            self.cell_start = torch.zeros(cell_count.numel() + 1, dtype=torch.int32, device=device)
+            self.cell_start[1:] = incl
+            cursor = self.cell_start[:-1].clone()
+        with self._phase('fill'):
+            self.list = hip.tri_grid_fill(self.grid, v, f, cursor, n_entries)
+        self.over_list, self.n_over, self.n_entries = over_list[:n_over].clone(), n_over, n_entries
+
+    def _phase(self, name):
+        from .stage1.extracting import _Phase
+        return _Phase(self.build_events, name)
+
+    @property
+    def index_bytes(self):
+        return 4 * (self.cell_start.numel() + self.list.numel() + self.over_list.numel())
+
+    def home_order(self, points):
+        """The permutation that sorts the points by their (clamped) home cell: plumbing that keeps a wave's lanes in neighbouring
+        cells.  It only orders the work; the kernel forms the home cell itself."""
+        lo = torch.tensor(self.lo, dtype=torch.float64, device=points.device)
+        top = torch.tensor(self.n, dtype=torch.float64, device=points.device) - 1.0
+        c = torch.nan_to_num(torch.floor((points - lo) / self.cell), nan=0.0)
+        c = torch.minimum(torch.clamp(c, min=0.0), top).to(torch.int64)
+        key = (c[:, 0] * self.n[1] + c[:, 1]) * self.n[2] + c[:, 2]
+        return torch.sort(key).indices
+
+    def closest_point(self, points, n_tests=None):
+        """points float64 [Q, 3] on the index's device -> (closest [Q, 3], distance [Q], triangle_id int64 [Q]), device tensors.
+        n_tests: an int64 [1] device tensor to which the number of point-triangle tests is added."""
+        from . import hip
+        if not (torch.is_tensor(points) and points.is_cuda):
+            raise RuntimeError('MeshIndex.closest_point: points must be a device tensor (host arrays: host_closest_point)')
+        points = points.to(torch.float64).reshape(-1, 3).contiguous()
+        order = self.home_order(points) if points.shape[0] > 64 else None   # (one wave: nothing to order)
+        return hip.closest_point(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over, points,
+                                 order=order, n_tests=n_tests)
+
+    def face_areas_cumulative(self):
+        v, f = self.vertices, self.faces
+        a = v[f[:, 0]]
+        ab, ac = v[f[:, 1]] - a, v[f[:, 2]] - a
+        nx = ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1]
+        ny = ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2]
+        nz = ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]
+        return torch.cumsum(0.5 * torch.sqrt(nx * nx + ny * ny + nz * nz), dim=0)
+
+    def sample_surface(self, count, rng=None, return_cumulative=False):
+        """host_sample_surface on the device: the uniforms are drawn on the host from ``rng`` in the host path's order and uploaded
+        (3 x count doubles); areas, their cumulative sum, the search and the barycentric step run on the device."""
+        pick, uv = _draw(rng, int(count))
+        dev = self.vertices.device
+        pick, uv = torch.from_numpy(pick).to(dev), torch.from_numpy(uv).to(dev)
+        area_cum = self.face_areas_cumulative()
+        face_index = torch.clamp(torch.searchsorted(area_cum, pick * area_cum[-1]), max=self.faces.shape[0] - 1)
+        u, w = uv[:, 0], uv[:, 1]
+        flip = u + w > 1.0
+        u, w = torch.where(flip, 1.0 - u, u), torch.where(flip, 1.0 - w, w)
+        t = self.faces[face_index]
+        a, b, c = self.vertices[t[:, 0]], self.vertices[t[:, 1]], self.vertices[t[:, 2]]
+        points = a + u[:, None] * (b - a) + w[:, None] * (c - a)
+        return (points, face_index, area_cum) if return_cumulative else (points, face_index)
+
+
+class _HostMesh(object):
+    """The host twin of MeshIndex (same three methods), so that the Chamfer functions below are written once."""
+
+    def __init__(self, vertices, faces, name='mesh'):
+        self.vertices, self.faces = _as_mesh_arrays(vertices, faces)
+        if self.faces.shape[0] == 0 or self.vertices.shape[0] == 0:
+            raise ValueError('%s is empty (%d vertices, %d faces)' % (name, self.vertices.shape[0], self.faces.shape[0]))
+
+    def sample_surface(self, count, rng=None):
+        return host_sample_surface(self.vertices, self.faces, count, rng)
+
+    def closest_point(self, points):
+        return host_closest_point(self.vertices, self.faces, points)
+
+
+def _prepare(mesh, device, name):
+    """A mesh (anything with .vertices and .faces; a MeshIndex is taken as it is) -> MeshIndex or _HostMesh."""
+    if isinstance(mesh, (MeshIndex, _HostMesh)):
+        return mesh
+    v, f = mesh.vertices, mesh.faces
+    on_device = torch.is_tensor(v) and v.is_cuda
+    if device is not None and torch.device(device).type == 'cuda':
+        return MeshIndex(v, f, device=v.device if on_device else torch.device(device), name=name)
+    if on_device:
+        if device is not None:   # device='cpu' with device tensors: the caller asked for the host path
+            return _HostMesh(v.cpu().numpy(), f.cpu().numpy(), name)
+        return MeshIndex(v, f, name=name)
+    return _HostMesh(v.numpy() if torch.is_tensor(v) else v, f.numpy() if torch.is_tensor(f) else f, name)
+
+
+def get_chamfer_dist(src_mesh, tgt_mesh, num_samples=10000, rng=None, device=None):
+    """stage2/utils/metrics.py:79-101 (chamfer_dist.py:19-35 returns the first value only) -> (chamfer, raw): the mean distance
+    of ``num_samples`` surface samples of each mesh to the other mesh, averaged over the two directions; raw = the samples and
+    the per-sample distances under the reference's keys.  A mesh is anything with ``.vertices`` and ``.faces``.  Device tensors,
+    or ``device='cuda'``, take the device path (raw then holds device tensors; nothing is copied back but the result);
+    otherwise the host path.  ``rng``: np.random.RandomState (default: the global np.random, as the reference)."""
+    src, tgt = _prepare(src_mesh, device, 'src_mesh'), _prepare(tgt_mesh, device, 'tgt_mesh')
+    src_surf_pts, _ = src.sample_surface(num_samples, rng)
+    tgt_surf_pts, _ = tgt.sample_surface(num_samples, rng)
+    _, src_tgt_dist, _ = tgt.closest_point(src_surf_pts)
+    _, tgt_src_dist, _ = src.closest_point(tgt_surf_pts)
+    chamfer_dist = (src_tgt_dist.mean() + tgt_src_dist.mean()) / 2
+    raw = {'tgt_surf_pts': tgt_surf_pts, 'src_surf_pts': src_surf_pts, 'src_tgt_dist': src_tgt_dist, 'tgt_src_dist': tgt_src_dist}
+    return float(chamfer_dist), raw
+
+
+def get_surface_dist(src_mesh, tgt_mesh, num_samples=10000, rng=None, device=None):
+    """stage2/utils/metrics.py:103-113: the mean distance of ``num_samples`` surface samples of src_mesh to tgt_mesh."""
+    src, tgt = _prepare(src_mesh, device, 'src_mesh'), _prepare(tgt_mesh, device, 'tgt_mesh')
+    src_surf_pts, _ = src.sample_surface(num_samples, rng)
+    _, src_tgt_dist, _ = tgt.closest_point(src_surf_pts)
+    return float(src_tgt_dist.mean())
+
+
+# ------------------------------------------------------------------------------------------------ reading meshes
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def _fan(polygons):
+    """Polygons (lists of vertex indices) -> triangles, a fan around the first corner."""
+    out = []
+    for p in polygons:
+        if len(p) < 3:
+            raise ValueError('a face with %d corners' % len(p))
+        out.extend((p[0], p[k], p[k + 1]) for k in range(1, len(p) - 1))
+    return np.asarray(out, dtype=np.int64).reshape(-1, 3)
+
+
+def _load_obj(path):
+    vertices, normals, polygons = [], [], []
+    with open(path, 'r') as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok or tok[0].startswith('#'):
+                continue
+            if tok[0] == 'v':
+                vertices.append([float(x) for x in tok[1:4]])
+            elif tok[0] == 'vn':
+                normals.append([float(x) for x in tok[1:4]])
+            elif tok[0] == 'f':
+                idx = [int(t.split('/')[0]) for t in tok[1:]]
+                polygons.append([i - 1 if i > 0 else len(vertices) + i for i in idx])   # (negative: relative to the end)
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    vn = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    return Mesh(v, _fan(polygons), vertex_normals=vn if len(vn) == len(v) and len(v) else None)
+
+
+def _load_ply(path):
+    with open(path, 'rb') as fh:
+        data = fh.read()
+    end = data.find(b'end_header')
+    if not data.startswith(b'ply') or end < 0:
+        raise ValueError('no PLY header')
+    body = data.index(b'\n', end) + 1
+    fmt, elements = None, []
+    for line in data[:end].decode('ascii', 'replace').splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ('comment', 'obj_info'):
+            continue
+        if tok[0] == 'format':
+            fmt = tok[1]
+        elif tok[0] == 'element':
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == 'property':
+            if not elements:
+                raise ValueError('a property before any element')
+            elements[-1][2].append((tok[-1], (tok[2], tok[3])) if tok[1] == 'list' else (tok[-1], tok[1]))
+    if fmt not in ('ascii', 'binary_little_endian'):
+        raise ValueError('format %r (supported: ascii, binary_little_endian)' % fmt)
+    vertices, polygons, normals = None, [], None
+    tokens, tpos = (data[body:].split(), 0) if fmt == 'ascii' else (None, 0)
+    pos = body
+    for name, count, props in elements:
+        has_list = any(isinstance(t, tuple) for _, t in props)
+        if any((t if not isinstance(t, tuple) else t[0]) not in _PLY_TYPES or (isinstance(t, tuple) and t[1] not in _PLY_TYPES)
+               for _, t in props):
+            raise ValueError('element %s: unknown property type' % name)
+        if not has_list:
+            if fmt == 'ascii':
+                rows = np.asarray(tokens[tpos:tpos + count * len(props)], dtype=np.float64).reshape(count, len(props))
+                tpos += count * len(props)
+                cols = dict((p, rows[:, i]) for i, (p, _) in enumerate(props))
+            else:
+                dt = np.dtype([(p, '<' + _PLY_TYPES[t]) for p, t in props])
+                rec = np.frombuffer(data, dtype=dt, count=count, offset=pos)
+                pos += count * dt.itemsize
+                cols = dict((p, rec[p]) for p, _ in props)
+            if name == 'vertex':
+                vertices = np.stack([cols['x'], cols['y'], cols['z']], axis=1).astype(np.float64)
+                if all(k in cols for k in ('nx', 'ny', 'nz')):
+                    normals = np.stack([cols['nx'], cols['ny'], cols['nz']], axis=1).astype(np.float64)
+            continue
+        is_face = name == 'face'
+        if fmt == 'binary_little_endian' and len(props) == 1 and count > 0:
+            # the common case (and what Mesh.export writes): one list property, every face with as many corners as the first
+            ct, it = _PLY_TYPES[props[0][1][0]], _PLY_TYPES[props[0][1][1]]
+            k = int(np.frombuffer(data, dtype='<' + ct, count=1, offset=pos)[0])
+            dt = np.dtype([('n', '<' + ct), ('i', '<' + it, (k,))])
+            if pos + count * dt.itemsize <= len(data):
+                rec = np.frombuffer(data, dtype=dt, count=count, offset=pos)
+                if (rec['n'] == k).all():
+                    pos += count * dt.itemsize
+                    if is_face:
+                        polygons = rec['i'].astype(np.int64).reshape(count, k)
+                    continue
+        rows = []
+        for _ in range(count):
+            row = None
+            for pname, t in props:
+                if isinstance(t, tuple):
+                    if fmt == 'ascii':
+                        k = int(tokens[tpos])
+                        idx = [int(x) for x in tokens[tpos + 1:tpos + 1 + k]]
+                        tpos += 1 + k
+                    else:
+                        ct, it = np.dtype('<' + _PLY_TYPES[t[0]]), np.dtype('<' + _PLY_TYPES[t[1]])
+                        k = int(np.frombuffer(data, dtype=ct, count=1, offset=pos)[0])
+                        idx = np.frombuffer(data, dtype=it, count=k, offset=pos + ct.itemsize).astype(np.int64).tolist()
+                        pos += ct.itemsize + k * it.itemsize
+                    if pname in ('vertex_indices', 'vertex_index'):
+                        row = idx
+                elif fmt == 'ascii':
+                    tpos += 1
+                else:
+                    pos += np.dtype(_PLY_TYPES[t]).itemsize
+            if is_face and row is not None:
+                rows.append(row)
+        if is_face:
+            polygons = rows
+    if vertices is None:
+        raise ValueError('no vertex element')
+    faces = _fan([list(p) for p in polygons]) if len(polygons) else np.zeros((0, 3), dtype=np.int64)
+    return Mesh(vertices, faces, vertex_normals=normals)
+
+
+def load_mesh(path):
+    """Read what ``Mesh.export`` writes, and ground-truth scans of the same kinds: Wavefront .obj (v / vn / f with a, a/b, a/b/c or
+    a//n corners) and .ply (ascii or binary little-endian).  Polygons with more than three corners are fan-triangulated.
+    Anything else raises a ValueError that names the file."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext not in ('.obj', '.ply'):
+        raise ValueError('load_mesh: %s: unsupported extension %r (supported: .obj, .ply)' % (path, ext))
+    try:
+        mesh = _load_obj(path) if ext == '.obj' else _load_ply(path)
+    except (ValueError, KeyError, IndexError) as e:
+        raise ValueError('load_mesh: %s: %s' % (path, e))
+    if len(mesh.faces) and (mesh.faces.min() < 0 or mesh.faces.max() >= len(mesh.vertices)):
+        raise ValueError('load_mesh: %s: a face refers to a vertex that does not exist' % path)
+    return mesh

@@ -35,3 +35,16 @@ def PSNR(img1, img2, mask=None):
         a, b = a[m], b[m]
     mse = np.mean((a - b) ** 2)
     return 100 if mse == 0 else -10.0 * math.log10(mse)
+
+
+def get_chamfer_dist(src_mesh, tgt_mesh, num_samples=10000, rng=None, device=None):
+    """Chamfer distance between two meshes -> (chamfer, raw) (metrics.py:79-101): psnerf_amd.meshdist, on the host for numpy
+    meshes and on the device for device tensors or ``device='cuda'``."""
+    from .meshdist import get_chamfer_dist as f
+    return f(src_mesh, tgt_mesh, num_samples, rng=rng, device=device)
+
+
+def get_surface_dist(src_mesh, tgt_mesh, num_samples=10000, rng=None, device=None):
+    """One-sided mean distance of src_mesh's surface samples to tgt_mesh (metrics.py:103-113): psnerf_amd.meshdist."""
+    from .meshdist import get_surface_dist as f
+    return f(src_mesh, tgt_mesh, num_samples, rng=rng, device=device)
