@@ -25,6 +25,62 @@ import torch
 from . import hip
 
 
+class PackCache(object):
+    """The weight packs of one module: ``slot -> pack``, each valid for the parameter values it was built from."""
+
+    def __init__(self):
+        self.epoch = 0
+        self._slots = {}  # slot -> (key, pack)
+
+    def key(self, params):
+        """Cache key of a weight pack: version counter AND storage address of EVERY parameter (an assign-style
+        load_state_dict replaces storages of individual layers), plus the invalidation epoch.  In-place edits
+        through ``.data`` bump neither: callers that do that (EMA swaps, manual clipping) call ``invalidate_packs()``."""
+        return (self.epoch,) + tuple((int(p._version), p.data_ptr()) for p in params)
+
+    def invalidate(self):
+        self.epoch += 1
+
+    def get(self, slot, params, build, extra=()):
+        """The pack of ``slot`` for the current values of ``params``; ``build(previous pack or None)`` runs (without a graph)
+        only when the key changed.  ``extra``: run-time switches that are part of the pack's identity."""
+        key = (self.key(params), extra)
+        hit = self._slots.get(slot)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                pack = build(hit[1] if hit is not None else None)
+            hit = self._slots[slot] = (key, pack)
+        return hit[1]
+
+
+class PackCached(object):
+    """Mixin for an nn.Module that runs on weight packs (listed BEFORE nn.Module in the bases): ``self.packs`` and the events
+    that invalidate it by themselves -- ``.to()`` / ``.double()`` / ... and ``load_state_dict`` (which visits every submodule
+    itself, so every module that owns packs carries the mixin)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.packs = PackCache()
+
+    def invalidate_packs(self):
+        """Drop the cached weight packs.  Needed only after editing parameters through ``.data`` (EMA swaps, manual
+        clipping): such edits bump neither the version counters nor the storage addresses the caches key on."""
+        self.packs.invalidate()
+
+    def _apply(self, fn, *a, **k):
+        self.packs.invalidate()
+        return super()._apply(fn, *a, **k)
+
+    def _load_from_state_dict(self, *a, **k):
+        self.packs.invalidate()
+        return super()._load_from_state_dict(*a, **k)
+
+
+def interleave(weights, biases):
+    """[W0, b0, W1, b1, ...]: the parameter order of the autograd functions in ops."""
+    return [t for pair in zip(weights, biases) for t in pair]
+
+
 class PackedMLP(object):
     def __init__(self, desc, w, b, init_wa=None, init_wb=None, init_bias=None):
         self.desc, self.w, self.b = desc, w, b

@@ -232,10 +232,7 @@ class ReluMLP(torch.autograd.Function):
 
 
 def relu_mlp(x, in_cols, skip_at, final_sigmoid, weights, biases):
-    params = []
-    for W, b in zip(weights, biases):
-        params += [W, b]
-    return ReluMLP.apply(x, in_cols, skip_at, final_sigmoid, *params)
+    return ReluMLP.apply(x, in_cols, skip_at, final_sigmoid, *fused.interleave(weights, biases))
 
 
 class FusedPairMLP(torch.autograd.Function):

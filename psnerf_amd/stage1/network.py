@@ -34,7 +34,7 @@ class WNLinear(nn.Module):
         return v * (self.weight_g / v.norm(2, dim=1, keepdim=True))
 
 
-class NeuralNetwork(nn.Module):
+class NeuralNetwork(fused.PackCached, nn.Module):
     def __init__(self, cfg_all, **kwargs):
         super().__init__()
         cfg = cfg_all['model']
@@ -80,39 +80,15 @@ class NeuralNetwork(nn.Module):
         for l in range(self.n_app):
             lin = nn.Linear(dims_app[l], dims_app[l + 1])
             setattr(self, 'lina%d' % l, WNLinear(lin.weight.detach(), lin.bias.detach()))
-        self._pack_epoch = 0
-        self._packed = None
-        self._packed_key = None
         # 'fp32' (default, exact) or 'bf16x6': GRADIENT-FREE occupancy queries (shadow rays, ray-march sweep, shape_extract;
         # stage1/model/rendering.py:297-523) on the split-bf16 engine -- fp32-class arithmetic on the bf16 matrix pipe
         # (csrc/mlp_infer_x3.hip, OCC variant).  Opt-in experiment, never the headline; every training path stays exact fp32.
         self.inference_precision = 'fp32'
-        self._packed_x3 = None
-        self._packed_x3_key = None
-        self._packed_b3 = None
-        self._packed_b3_key = None
-        self._chains = None
-        self._chains_key = None
-        self._app_packed = None
-        self._app_key = None
 
-    # ---- weight-pack caches ---------------------------------------------------------------------
-    def _params_key(self):
-        """Version counter and storage address of EVERY parameter + the invalidation epoch (see invalidate_packs)."""
-        return (self._pack_epoch,) + tuple((int(q._version), q.data_ptr()) for q in self.parameters())
-
-    def invalidate_packs(self):
-        """Drop the cached occupancy / chain packs.  Needed only after editing parameters through ``.data`` (EMA swaps,
-        manual clipping): such edits bump neither the version counters nor the storage addresses the caches key on."""
-        self._pack_epoch += 1
-
-    def _apply(self, fn, *a, **k):
-        self._pack_epoch += 1
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._pack_epoch += 1
-        return super()._load_from_state_dict(*a, **k)
+    # ---- weight-pack cache ----------------------------------------------------------------------
+    def _pack(self, slot, build, extra=()):
+        """The cached pack ``slot`` (fused.PackCache): every pack of this module is keyed on ALL of its parameters."""
+        return self.packs.get(slot, self.parameters(), build, extra)
 
     # ---- effective weights ----------------------------------------------------------------------
     def _effective(self, prefix, n, scales):
@@ -129,10 +105,7 @@ class NeuralNetwork(nn.Module):
     def _geo_params(self):
         inv = float(1.0 / np.sqrt(2))  # folds the cat[x, pe]/sqrt(2) of network.py:90-91 into the skip layer
         Ws = self._effective('lin', self.n_geo, [inv if l in self.skips else 1.0 for l in range(self.n_geo)])
-        out = []
-        for l in range(self.n_geo):
-            out += [Ws[l], getattr(self, 'lin%d' % l).bias]
-        return out
+        return fused.interleave(Ws, [getattr(self, 'lin%d' % l).bias for l in range(self.n_geo)])
 
     def _app_params(self):
         Ws = self._effective('lina', self.n_app, [1.0] * self.n_app)
@@ -142,12 +115,18 @@ class NeuralNetwork(nn.Module):
     MAX_ROWS = 1 << 20  # rows per GeoField call: bounds the saved activations to ~50 GB of the 288 GB HBM
 
     def _geo_chains(self, params):
-        key = (self._params_key(), ops.CHAIN_X3)  # (a run-time switch: a toggle rebuilds the packs)
-        if self._chains is None or self._chains_key != key:
-            with torch.no_grad():
-                self._chains = fused.pack_geo_chains(params[0::2], params[1::2], self.skips, self.d_pe, x3=ops.CHAIN_X3)
-            self._chains_key = key
-        return self._chains
+        x3 = ops.CHAIN_X3  # (a run-time switch: a toggle rebuilds the packs)
+        return self._pack('geo_chains', lambda _: fused.pack_geo_chains(params[0::2], params[1::2], self.skips, self.d_pe, x3=x3),
+                          extra=(x3,))
+
+    def _geo_chains_fit(self):
+        """The geometry network has the one shape the fused chains hold (fused.pack_geo_chains)."""
+        return self._hidden_is_256() and len(self.skips) == 1 and self.feat_size == 256 and self.n_geo <= 10 and self.d_pe <= 64
+
+    def _app_chains_fit(self, Ws, d_x):
+        """The appearance network (effective matrices ``Ws``) has the shape the fused chains hold (fused.pack_app_chains)."""
+        return (self.feat_size == 256 and d_x <= 64 and Ws[0].shape[0] == 256
+                and all(w.shape == (256, 256) for w in Ws[1:-1]) and self.n_app <= 10)
 
     def _geo_call(self, p_flat, with_grad, params, chains, feat_rows=None):
         if chains is not None:
@@ -170,12 +149,11 @@ class NeuralNetwork(nn.Module):
         if occupancy and self._hidden_is_256():
             self._occupancy_packed()
         if chains and self.USE_FUSED_CHAINS:
-            if self._hidden_is_256() and len(self.skips) == 1 and self.feat_size == 256 and self.n_geo <= 10 and self.d_pe <= 64:
+            if self._geo_chains_fit():
                 self._geo_chains(self._geo_params())
             Ws, bs = self._app_params()
             d_x = 3 + self.d_view + 3
-            if (self.feat_size == 256 and d_x <= 64 and Ws[0].shape[0] == 256
-                    and all(w.shape == (256, 256) for w in Ws[1:-1]) and self.n_app <= 10):
+            if self._app_chains_fit(Ws, d_x):
                 self._app_chains(Ws, bs, d_x)
 
     def _geo_parts(self, p_flat, with_grad):
@@ -183,8 +161,7 @@ class NeuralNetwork(nn.Module):
         fused register-resident chains (ops.GeoFieldFused); other widths fall back to the GEMM sequence."""
         params = self._geo_params()
         chains = None
-        if self.USE_FUSED_CHAINS and self._hidden_is_256() and len(self.skips) == 1 and self.feat_size == 256 \
-                and self.n_geo <= 10 and self.d_pe <= 64:
+        if self.USE_FUSED_CHAINS and self._geo_chains_fit():
             chains = self._geo_chains(params)
         if p_flat.shape[0] <= self.MAX_ROWS:
             return self._geo_call(p_flat, with_grad, params, chains)
@@ -205,47 +182,27 @@ class NeuralNetwork(nn.Module):
         if allow_x3 and prec == 'bf16x3' and not torch.is_grad_enabled():
             # the exact engine's kernels on split-bf16 weight stages (two bf16 pieces per operand, three partial products:
             # PsnMlpDesc.w_format = PSN_W_BF16X2; ~1e-5 relative) -- same call surface, the sweep included
-            key = self._params_key()
-            if getattr(self, '_packed_b3', None) is None or self._packed_b3_key != key:
-                with torch.no_grad():
-                    Ws = self._effective('lin', self.n_geo, [1.0] * self.n_geo)
-                    bs = [getattr(self, 'lin%d' % l).bias for l in range(self.n_geo)]
-                    self._packed_b3 = fused.pack_geo_occupancy(Ws, bs, self.skips, self.d_pe, x3=True)
-                self._packed_b3_key = key
-            return self._packed_b3
-        key = self._params_key()
-        if self._packed is None or self._packed_key != key:
-            with torch.no_grad():
-                # without the 1/sqrt(2) fold: pack_geo_occupancy applies it itself
-                Ws = self._effective('lin', self.n_geo, [1.0] * self.n_geo)
-                bs = [getattr(self, 'lin%d' % l).bias for l in range(self.n_geo)]
-                self._packed = fused.pack_geo_occupancy(Ws, bs, self.skips, self.d_pe)
-            self._packed_key = key
-        return self._packed
+            return self._occ_pack('occ_b3', fused.pack_geo_occupancy, x3=True)
+        return self._occ_pack('occ', fused.pack_geo_occupancy)
+
+    def _occ_pack(self, slot, pack, **kwargs):
+        """The cached occupancy-type pack ``slot``, built by ``pack`` (fused.pack_geo_occupancy / _x3 / pack_geo_logit)."""
+        def build(_):
+            # without the 1/sqrt(2) fold of _geo_params: the builders apply it themselves
+            Ws = self._effective('lin', self.n_geo, [1.0] * self.n_geo)
+            bs = [getattr(self, 'lin%d' % l).bias for l in range(self.n_geo)]
+            return pack(Ws, bs, self.skips, self.d_pe, **kwargs)
+        return self._pack(slot, build)
 
     def _logit_packed(self):
         """The negated-logit pack of the exact-fp32 lean engine (fused.pack_geo_logit): the value function of the mesh extraction
         (stage1/extracting.py), cached by parameter version like the occupancy pack."""
-        key = self._params_key()
-        if getattr(self, '_packed_logit', None) is None or self._packed_logit_key != key:
-            with torch.no_grad():
-                Ws = self._effective('lin', self.n_geo, [1.0] * self.n_geo)
-                bs = [getattr(self, 'lin%d' % l).bias for l in range(self.n_geo)]
-                self._packed_logit = fused.pack_geo_logit(Ws, bs, self.skips, self.d_pe)
-            self._packed_logit_key = key
-        return self._packed_logit
+        return self._occ_pack('logit', fused.pack_geo_logit)
 
     def _occupancy_packed_x3(self):
         """The occupancy network for the split-bf16 engine (opt-in: ``inference_precision = 'bf16x6'``; gradient-free queries
         only -- shadow rays, ray march, shape_extract; rendering.py:378-523): fp32-class arithmetic on the bf16 matrix pipe."""
-        key = self._params_key()
-        if getattr(self, '_packed_x3', None) is None or self._packed_x3_key != key:
-            with torch.no_grad():
-                Ws = self._effective('lin', self.n_geo, [1.0] * self.n_geo)
-                bs = [getattr(self, 'lin%d' % l).bias for l in range(self.n_geo)]
-                self._packed_x3 = fused.pack_geo_occupancy_x3(Ws, bs, self.skips, self.d_pe)
-            self._packed_x3_key = key
-        return self._packed_x3
+        return self._occ_pack('occ_x3', fused.pack_geo_occupancy_x3)
 
     # ---- reference API ----------------------------------------------------------------------------
     def infer_occ(self, p):
@@ -268,12 +225,8 @@ class NeuralNetwork(nn.Module):
         return self._app(x)
 
     def _app_chains(self, Ws, bs, d_x):
-        key = (self._params_key(), ops.CHAIN_X3)  # (a run-time switch: a toggle rebuilds the packs)
-        if self._app_packed is None or self._app_key != key:
-            with torch.no_grad():
-                self._app_packed = fused.pack_app_chains(Ws, bs, d_x, x3=ops.CHAIN_X3)
-            self._app_key = key
-        return self._app_packed
+        x3 = ops.CHAIN_X3  # (a run-time switch: a toggle rebuilds the packs)
+        return self._pack('app_chains', lambda _: fused.pack_app_chains(Ws, bs, d_x, x3=x3), (x3,))
 
     def _app_parts(self, points, view, normal, feat):
         """Colour from (point, raw view direction, normal, geometry features) = infer_app (network.py:128-138) on the
@@ -281,18 +234,14 @@ class NeuralNetwork(nn.Module):
         (ops.AppNetFused) whose 64-column input table [p | gamma(v / |v|) | n] is written by one launch (psn_app_input)."""
         d_x = 3 + self.d_view + 3
         Ws, bs = self._app_params()
-        if not (self.USE_FUSED_CHAINS and self.feat_size == 256 and d_x <= 64 and Ws[0].shape[0] == 256
-                and all(w.shape == (256, 256) for w in Ws[1:-1]) and self.n_app <= 10 and points.is_cuda):
+        if not (self.USE_FUSED_CHAINS and self._app_chains_fit(Ws, d_x) and points.is_cuda):
             if self.USE_FUSED_CHAINS:
                 ops.fallback('stage1 appearance network -> layer-wise GEMMs (ops.ReluMLP)', points, 'widths / input size outside the fused chains')
             v = view / torch.norm(view, dim=-1, keepdim=True)
             v_pe = ops.positional_encoding(v, self.octaves_pe_views)
             return self._app(torch.cat([points, v_pe, normal, feat], dim=-1))
         x = hip.app_input(points.detach(), view.detach(), normal.detach(), self.octaves_pe_views)
-        params = []
-        for W, b in zip(Ws, bs):
-            params += [W, b]
-        y = ops.AppNetFused.apply(x, normal, feat, d_x, self._app_chains(Ws, bs, d_x), *params)
+        y = ops.AppNetFused.apply(x, normal, feat, d_x, self._app_chains(Ws, bs, d_x), *fused.interleave(Ws, bs))
         return torch.tanh(y) * 0.5 + 0.5
 
     def _app(self, x):
@@ -342,8 +291,8 @@ class NeuralNetwork(nn.Module):
         flat, ex = p.reshape(-1, 3), extra.reshape(-1, 3)
         q1 = flat.shape[0]
         params = self._geo_params()
-        fused_ok = (self.USE_FUSED_CHAINS and self._hidden_is_256() and len(self.skips) == 1 and self.feat_size == 256
-                    and self.n_geo <= 10 and self.d_pe <= 64 and q1 + ex.shape[0] <= self.MAX_ROWS and q1 > 0 and flat.is_cuda)
+        fused_ok = (self.USE_FUSED_CHAINS and self._geo_chains_fit() and q1 + ex.shape[0] <= self.MAX_ROWS and q1 > 0
+                    and flat.is_cuda)
         if not fused_ok:
             rgb, occ = self.forward(p, ray_d, return_addocc=True)
             return rgb, occ, self.gradient(extra)

@@ -31,13 +31,6 @@ from .. import fused, hip, ops
 PE_STRIDE = 64  # 3 + 6*10 = 63 real columns + 1 zero pad
 
 
-def params_key(params, epoch=0):
-    """Cache key of a weight pack: version counter AND storage address of EVERY parameter (an assign-style
-    load_state_dict replaces storages of individual layers), plus the module's invalidation epoch.  In-place edits
-    through ``.data`` bump neither: callers that do that (EMA swaps, manual clipping) call ``invalidate_packs()``."""
-    return (epoch,) + tuple((int(p._version), p.data_ptr()) for p in params)
-
-
 def camera_rays(uv, pose, intrinsics):
     """stage2/utils/rend_util.py:90-147 (4x4 pose case), device-agnostic."""
     fx, fy = intrinsics[:, 0, 0], intrinsics[:, 1, 1]
@@ -52,7 +45,7 @@ def camera_rays(uv, pose, intrinsics):
     return F.normalize(d, dim=2), pose[:, :3, 3]
 
 
-class MLP(nn.Module):
+class MLP(fused.PackCached, nn.Module):
     """Network / Normal_Network (renderer.py:17-49).  Parameters live in ``linears`` exactly like the
     reference; the forward runs on the HIP GEMM path."""
 
@@ -66,18 +59,6 @@ class MLP(nn.Module):
         self.final = final
         self.din, self.width = din, W
 
-    def invalidate_packs(self):
-        """Drop the cached weight packs (call after editing parameters through ``.data``)."""
-        self._pack_epoch = getattr(self, '_pack_epoch', 0) + 1
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate_packs()
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self.invalidate_packs()
-        return super()._load_from_state_dict(*a, **k)
-
     def _skip_index(self):
         s = [i for i in self.skip_at if 0 <= i < len(self.linears) - 1]
         assert len(s) <= 1, 'at most one skip connection is supported'
@@ -88,33 +69,29 @@ class MLP(nn.Module):
 
     FUSED = True  # 64 / 128 / 256-wide networks on encoded points run in the register-resident kernel (ops.FusedReluNet)
 
-    def _fusable(self, x_padded, in_cols):
+    def _fused_shape(self):
+        """The network has a shape the register-resident kernel holds (fused.pack_relu_mlp with ``width``)."""
         Ws = [l.weight for l in self.linears]
-        return (self.FUSED and self.width in (64, 128, 256) and x_padded.shape[1] == 64 and not x_padded.requires_grad
-                and in_cols.numel() == self.din <= 64 and Ws[-1].shape[0] <= 32 and len(Ws) <= 11
+        return (self.FUSED and self.width in (64, 128, 256) and self.din <= 64 and Ws[-1].shape[0] <= 32
                 and all(w.shape[0] == self.width for w in Ws[:-1]))
+
+    def _fusable(self, x_padded, in_cols):
+        return (self._fused_shape() and x_padded.shape[1] == 64 and not x_padded.requires_grad
+                and in_cols.numel() == self.din and len(self.linears) <= 11)
 
     def prepack(self):
         """The forward weight pack, rebuilt only when the parameters changed since the last call (evaluation loops and
         the two evaluations of a training step share it)."""
-        if not (self.FUSED and self.width in (64, 128, 256) and self.din <= 64 and self.linears[-1].weight.shape[0] <= 32
-                and all(l.weight.shape[0] == self.width for l in list(self.linears)[:-1]) and self.linears[0].weight.is_cuda):
+        if not (self._fused_shape() and self.linears[0].weight.is_cuda):
             return None
-        key = params_key(self.parameters(), getattr(self, '_pack_epoch', 0))
-        if getattr(self, '_pack_key', None) != key:
-            Ws, bs = self.weights()
-            self._pack = ops.FusedReluNet.pack(Ws, bs, self.din, self._skip_index(), self.final == 'sigmoid', self.width)
-            self._pack_key = key
-        return self._pack
+        return self.packs.get('fwd', self.parameters(), lambda _: ops.FusedReluNet.pack(
+            *self.weights(), self.din, self._skip_index(), self.final == 'sigmoid', self.width))
 
     def forward(self, x_padded, in_cols):
         Ws, bs = self.weights()
         if self._fusable(x_padded, in_cols):
-            params = []
-            for W, b in zip(Ws, bs):
-                params += [W, b]
             return ops.FusedReluNet.apply(x_padded, self.din, self._skip_index(), self.final == 'sigmoid', self.width,
-                                          self.prepack(), *params)
+                                          self.prepack(), *fused.interleave(Ws, bs))
         if self.FUSED:  # (FUSED = False is a caller's deliberate choice: the layer-wise cross-check of the tests)
             ops.fallback('stage2.MLP -> layer-wise GEMMs', x_padded, 'width %d, %d layers, input %s' % (self.width, len(Ws), tuple(x_padded.shape)))
         return ops.relu_mlp(x_padded, in_cols, self._skip_index(), self.final == 'sigmoid', Ws, bs)
@@ -137,7 +114,7 @@ class _Dense(object):
         self.fill, self.B, self.C, self.rows = float(fill), int(B), int(C), rows
 
 
-class PSNetwork(nn.Module):
+class PSNetwork(fused.PackCached, nn.Module):
     def __init__(self, conf):
         super().__init__()
         self.conf = conf
@@ -221,17 +198,9 @@ class PSNetwork(nn.Module):
             mlps = self.__dict__['_mlp_list'] = [m for m in self.modules() if isinstance(m, MLP)]
         live = [m for m in mlps if not trainable_only or any(q.requires_grad for q in m.parameters())]
         if live:
-            self._pack_epoch = getattr(self, '_pack_epoch', 0) + 1  # (the model-level epoch keys the visibility packs)
+            self.packs.invalidate()  # (the model-level epoch keys the visibility packs)
         for m in live:
             m.invalidate_packs()
-
-    def _apply(self, fn, *a, **k):
-        self._pack_epoch = getattr(self, '_pack_epoch', 0) + 1
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._pack_epoch = getattr(self, '_pack_epoch', 0) + 1
-        return super()._load_from_state_dict(*a, **k)
 
     def _pe(self, x, n_freqs):
         return ops.positional_encoding(x, n_freqs, PE_STRIDE)
@@ -255,20 +224,13 @@ class PSNetwork(nn.Module):
         net = self.visibility_net
         Ws, bs = net.weights()
         cols = self._cols(self.n_freqs, pe_x.device, pair=True)
-        if (fused_ok and net.width == 256 and self.inference_precision == 'bf16x3' and not torch.is_grad_enabled() and pe_x.is_cuda):
-            return self._visibility_rows_b3(pe_x, pe_l)
-        if (fused_ok and net.width == 256 and self.inference_precision in ('bf16', 'bf16x6') and not torch.is_grad_enabled()
-                and len(Ws) <= 12 and pe_x.is_cuda):
-            # opt-in bf16 MFMA engines (evaluation / relighting): plain bf16 (csrc/mlp_infer_bf16.hip) or the split form with
-            # fp32-class accuracy (csrc/mlp_infer_x3.hip)
-            if self.inference_precision == 'bf16x6':
-                return self._visibility_rows_x3(pe_x, pe_l)
-            return self._visibility_rows_bf16(pe_x, pe_l)
+        mode = self.inference_precision
+        if (fused_ok and net.width == 256 and mode in ('bf16', 'bf16x6', 'bf16x3') and not torch.is_grad_enabled() and pe_x.is_cuda
+                and (mode == 'bf16x3' or len(Ws) <= 12)):
+            # opt-in bf16 MFMA engines (evaluation / relighting)
+            return self._visibility_rows_lowp(mode, pe_x, pe_l)
         if fused_ok and net.width == 256:
-            params = []
-            for W, b in zip(Ws, bs):
-                params += [W, b]
-            return ops.FusedPairMLP.apply(pe_x, pe_l, cols, net._skip_index(), *params)
+            return ops.FusedPairMLP.apply(pe_x, pe_l, cols, net._skip_index(), *fused.interleave(Ws, bs))
         if fused_ok:
             ops.fallback('stage2.visibility rows -> expanded [L Ns, 128] input', pe_x, 'visibility_net width %d' % net.width)
         ns, nl = pe_x.shape[0], pe_l.shape[0]
@@ -278,62 +240,58 @@ class PSNetwork(nn.Module):
     def _visibility_pair_args(self, pe_x, light_dir, light_vis_train):
         pe_l = self._pe(torch.cat([light_dir.detach(), light_vis_train.detach()], dim=0), self.n_freqs)
         net = self.visibility_net
-        Ws, bs = net.weights()
-        params = []
-        for W, b in zip(Ws, bs):
-            params += [W, b]
         cols = self._cols(self.n_freqs, pe_x.device, pair=True)
-        return pe_x.detach(), pe_l, light_dir.shape[0], cols, net._skip_index(), params
+        return pe_x.detach(), pe_l, light_dir.shape[0], cols, net._skip_index(), fused.interleave(*net.weights())
 
     def _visibility_prepack(self):
         """Packed visibility-net weights (input block through init tables), rebuilt only when the parameters changed."""
         net = self.visibility_net
         if net.width != 256 or not net.linears[0].weight.is_cuda:
             return None
-        key = params_key(net.parameters(), getattr(self, '_pack_epoch', 0))
-        if getattr(self, '_vis_pack_key', None) != key:
+        # (the previous pack's init-table buffers are rewritten in place: its launches are behind us on this stream)
+        return self._vis_pack('fp32', lambda prev, *net_args: fused.pack_relu_mlp(*net_args, reuse=prev))
+
+    def _vis_pack(self, slot, build):
+        """The cached pack ``slot`` of visibility_net, keyed on ITS parameters and the MODEL-level epoch.
+        ``build(previous pack or None, weights, biases, din_a, din_b, skip_at)``."""
+        net = self.visibility_net
+
+        def make(prev):
             Ws, bs = net.weights()
             half = 3 + 6 * self.n_freqs
-            with torch.no_grad():
-                # (the previous pack's init-table buffers are rewritten in place: its launches are behind us on this stream)
-                self._vis_pack = fused.pack_relu_mlp(list(Ws), list(bs), half, half, net._skip_index(),
-                                                     reuse=getattr(self, '_vis_pack', None))
-            self._vis_pack_key = key
-        return self._vis_pack
+            return build(prev, list(Ws), list(bs), half, half, net._skip_index())
+        return self.packs.get(slot, net.parameters(), make)
+
+    def _vis_out_act(self):
+        return hip.OUT_SIGMOID if self.visibility_net.final == 'sigmoid' else hip.OUT_NONE
 
     @torch.no_grad()
     def _visibility_rows_bf16(self, pe_x, pe_l):
         """Gradient-free visibility_net rows (light-major) on the bf16 MFMA engine."""
         # grouped form: the light's half of the input block enters as a per-light bias (fp32 product, once per light)
-        return self._visibility_prepack_bf16()(pe_x.to(torch.bfloat16), pe_l.contiguous())
+        pack = self._vis_pack('bf16', lambda prev, *net_args: fused.pack_relu_mlp_bf16_grouped(*net_args, self._vis_out_act()))
+        return pack(pe_x.to(torch.bfloat16), pe_l.contiguous())
 
     @torch.no_grad()
     def _visibility_rows_x3(self, pe_x, pe_l):
         """Gradient-free visibility_net rows (light-major) on the split-bf16 engine (fp32-class accuracy; experiment)."""
-        net = self.visibility_net
-        key = params_key(net.parameters(), getattr(self, '_pack_epoch', 0))
-        if getattr(self, '_vis_packx3_key', None) != key:
-            Ws, bs = net.weights()
-            half = 3 + 6 * self.n_freqs
-            self._vis_packx3 = fused.pack_relu_mlp_x3_grouped(list(Ws), list(bs), half, half, net._skip_index(),
-                                                              hip.OUT_SIGMOID if net.final == 'sigmoid' else hip.OUT_NONE)
-            self._vis_packx3_key = key
-        return self._vis_packx3(pe_x.contiguous(), pe_l.contiguous())
+        pack = self._vis_pack('bf16x6', lambda prev, *net_args: fused.pack_relu_mlp_x3_grouped(*net_args, self._vis_out_act()))
+        return pack(pe_x.contiguous(), pe_l.contiguous())
 
     @torch.no_grad()
     def _visibility_rows_b3(self, pe_x, pe_l):
         """Gradient-free visibility_net rows (light-major) through the exact engine's kernel on split-bf16 weight stages (experiment)."""
-        net = self.visibility_net
-        key = params_key(net.parameters(), getattr(self, '_pack_epoch', 0))
-        if getattr(self, '_vis_packb3_key', None) != key:
-            Ws, bs = net.weights()
-            half = 3 + 6 * self.n_freqs
-            self._vis_packb3 = fused.pack_relu_mlp(list(Ws), list(bs), half, half, net._skip_index(),
-                                                   out_act=hip.OUT_SIGMOID if net.final == 'sigmoid' else hip.OUT_NONE,
-                                                   reuse=getattr(self, '_vis_packb3', None), x3=True)
-            self._vis_packb3_key = key
+        pack = self._vis_pack('bf16x3', lambda prev, *net_args: fused.pack_relu_mlp(
+            *net_args, out_act=self._vis_out_act(), reuse=prev, x3=True))
         ns, nl = pe_x.shape[0], pe_l.shape[0]
-        return self._vis_packb3(pe_x.contiguous(), nl * ns, a_div=1, a_mod=ns, tab_b=pe_l.contiguous(), b_div=ns, b_mod=nl)
+        return pack(pe_x.contiguous(), nl * ns, a_div=1, a_mod=ns, tab_b=pe_l.contiguous(), b_div=ns, b_mod=nl)
+
+    def _visibility_rows_lowp(self, mode, pe_x, pe_l):
+        """Gradient-free visibility_net rows on the opt-in engine that ``inference_precision`` / ``train.vis_<mode>`` name:
+        plain bf16 (csrc/mlp_infer_bf16.hip), the split form with fp32-class accuracy (csrc/mlp_infer_x3.hip), or the exact
+        engine's kernel on split-bf16 weight stages."""
+        rows = {'bf16': self._visibility_rows_bf16, 'bf16x6': self._visibility_rows_x3, 'bf16x3': self._visibility_rows_b3}
+        return rows[mode](pe_x, pe_l)
 
     def _memo(self, tag, input, fn):
         """Light-independent intermediate of a gradient-free evaluation, computed once per (pixel set, weights) while a
@@ -343,23 +301,10 @@ class PSNetwork(nn.Module):
         if cache is None or torch.is_grad_enabled():
             return fn()
         key = (tag,) + tuple((input[k].data_ptr(), input[k]._version) for k in ('points', 'surface_mask', 'uv')) \
-            + params_key(self.parameters(), getattr(self, '_pack_epoch', 0))
+            + self.packs.key(self.parameters())
         if key not in cache:
             cache[key] = fn()
         return cache[key]
-
-    def _visibility_prepack_bf16(self):
-        """visibility-net weights in the fragment order of the bf16 engine, rebuilt only when the parameters changed."""
-        net = self.visibility_net
-        key = params_key(net.parameters(), getattr(self, '_pack_epoch', 0))
-        if getattr(self, '_vis_pack16_key', None) != key:
-            Ws, bs = net.weights()
-            half = 3 + 6 * self.n_freqs
-            with torch.no_grad():
-                self._vis_pack16 = fused.pack_relu_mlp_bf16_grouped(list(Ws), list(bs), half, half, net._skip_index(),
-                                                                    hip.OUT_SIGMOID if net.final == 'sigmoid' else hip.OUT_NONE)
-            self._vis_pack16_key = key
-        return self._vis_pack16
 
     def _visibility_pair_launch(self, pe_x, light_dir, light_vis_train, live_count=None):
         """Issue the fused launch now, attach the autograd node later (ops.VisibilityPair.launch).  live_count: the device-side
@@ -422,12 +367,15 @@ class PSNetwork(nn.Module):
         vis_pair = None
         vis_bf16 = None
         side = None
+        pair_ok = False
         if ns > 0 and self.visibility:
             lv0 = input.get('light_vis_train')
             ld0 = input['light_direction']
-            if (lv0 is not None and self.conf.get_bool('train.vis_rgb_detach', default=False)
-                    and self.visibility_net.width == 256 and torch.is_grad_enabled()
-                    and (self.light_vis_detach or not (ld0.requires_grad or lv0.requires_grad))):
+            # shading rows and supervision rows in ONE fused launch: decided here, used again where its autograd node is attached
+            pair_ok = (lv0 is not None and self.conf.get_bool('train.vis_rgb_detach', default=False)
+                       and self.visibility_net.width == 256 and torch.is_grad_enabled()
+                       and (self.light_vis_detach or not (ld0.requires_grad or lv0.requires_grad)))
+            if pair_ok:
                 pe_x = self._pe(surf, self.n_freqs)
                 if self.overlap_small_nets and surf.is_cuda:
                     # fork BEFORE the big launch is queued: the side stream waits for everything issued so far (inputs,
@@ -436,12 +384,12 @@ class PSNetwork(nn.Module):
                     if side is None:
                         side = self._side[device] = torch.cuda.Stream(device=device)  # (a high-priority stream: +-0.05 ms/step at 32768 px; round 5 at 4096 px: 3.76 -> 3.78 ms, 32768 px eager 25.1 -> 27.1 ms)
                     side.wait_stream(torch.cuda.current_stream(device))
-                if self.train_vis_bf16 or self.train_vis_bf16x6 or self.train_vis_bf16x3:
+                mode = 'bf16x3' if self.train_vis_bf16x3 else 'bf16x6' if self.train_vis_bf16x6 else 'bf16' if self.train_vis_bf16 else None
+                if mode is not None:
                     # opt-in (train.vis_bf16 / train.vis_bf16x6): the L shading rows enter the loss detached (renderer.py:197),
                     # so they can run on a bf16 engine; the V supervised rows stay on the exact fp32 path with their dumps
                     pe_l0 = self._pe(ld0.detach(), self.n_freqs)
-                    vis_bf16 = (self._visibility_rows_b3(pe_x, pe_l0) if self.train_vis_bf16x3 else
-                                self._visibility_rows_x3(pe_x, pe_l0) if self.train_vis_bf16x6 else self._visibility_rows_bf16(pe_x, pe_l0))
+                    vis_bf16 = self._visibility_rows_lowp(mode, pe_x, pe_l0)
                     vis_pair = self._visibility_pair_launch(pe_x, ld0[:0], lv0)
                 else:
                     # 'surface_count' (float32 [1] on the device, beside a 'surface_idx' padded to a fixed capacity -- hip.surface_index,
@@ -551,20 +499,17 @@ class PSNetwork(nn.Module):
             vis_t_pre = None
             if self.visibility:
                 detach = self.conf.get_bool('train.vis_rgb_detach', default=False)
-                lv = input.get('light_vis_train')
-                pair_ok = (lv is not None and detach and self.visibility_net.width == 256 and torch.is_grad_enabled()
-                           and (self.light_vis_detach or not (light_dir.requires_grad or lv.requires_grad)))
                 if pair_ok:
-                    # shading rows and supervision rows in ONE fused launch (the latter dump their activations)
+                    # the fused launch issued at the top (the supervision rows dump their activations)
                     # (round 6, measured and dropped: attaching this node BEHIND the shading node -- so that autograd queues the V-row
                     #  chain and its 256 x 256 weight gradients first -- costs 0.23 ms at 4096 px (3.74 -> 3.97 ms replayed) and 0.45 ms
                     #  at 32768 px: the weight-gradient launch holds every CU while the small networks' backward, the longer dependent
                     #  chain, waits; profiles/r06d_ab_strong4096.jsonl)
                     if vis_bf16 is not None:
-                        _none, vis_t_pre = self._visibility_pair(pe_x, light_dir[:0], lv, launched=vis_pair)
+                        _none, vis_t_pre = self._visibility_pair(pe_x, light_dir[:0], lv0, launched=vis_pair)
                         vis = vis_bf16
                     else:
-                        vis, vis_t_pre = self._visibility_pair(pe_x, light_dir, lv, launched=vis_pair)
+                        vis, vis_t_pre = self._visibility_pair(pe_x, light_dir, lv0, launched=vis_pair)
                 else:
                     # gradient-free unless a caller backpropagates into output['visibility']
                     vis = self._visibility_rows(pe_x, light_dir, fused_ok=True)  # [L*Ns, 1], light-major

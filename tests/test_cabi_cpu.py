@@ -438,3 +438,120 @@ def test_envmap_readers_known_answers_and_round_trips(tmp_path):
     import pytest
     with pytest.raises(NotImplementedError):
         relight.load_light(str(tmp_path / 'e.png'))
+
+
+def _counting_builder():
+    calls = []
+
+    def build(prev):
+        calls.append(prev)
+        return 'pack%d' % len(calls)
+    return calls, build
+
+
+def test_pack_cache_key_semantics():
+    """fused.PackCache on CPU parameters with a builder that counts its calls: what rebuilds a weight pack and what does not."""
+    import torch
+    from psnerf_amd import fused
+    lin = torch.nn.Linear(4, 3)
+    params = list(lin.parameters())
+    cache = fused.PackCache()
+    calls, build = _counting_builder()
+    assert cache.get('a', params, build) == 'pack1' and calls == [None]      # first time: no previous pack
+    assert cache.get('a', iter(params), build) == 'pack1' and len(calls) == 1  # unchanged parameters: a hit (any iterable)
+    with torch.no_grad():
+        lin.bias.add_(1.0)                                                   # in-place update of ONE parameter (not the first)
+    assert cache.get('a', params, build) == 'pack2' and calls == [None, 'pack1']  # rebuilt, handed the previous pack
+    opt = torch.optim.Adam(params, lr=1e-2)
+    lin(torch.ones(2, 4)).sum().backward()
+    opt.step()
+    assert cache.get('a', params, build) == 'pack3' and len(calls) == 3
+    assert cache.get('a', params, build) == 'pack3' and len(calls) == 3
+    lin.weight.data.mul_(2.0)                                                # the documented blind spot: a .data edit is silent ...
+    assert cache.get('a', params, build) == 'pack3' and len(calls) == 3
+    cache.invalidate()                                                       # ... until the caller announces it
+    assert cache.get('a', params, build) == 'pack4' and calls[-1] == 'pack3'
+    # run-time switches that are part of a pack's identity
+    assert cache.get('a', params, build, extra=(True,)) == 'pack5'
+    assert cache.get('a', params, build, extra=(True,)) == 'pack5' and len(calls) == 5
+    assert cache.get('a', params, build, extra=(False,)) == 'pack6'
+    # two slots of one cache do not disturb each other
+    calls_b, build_b = _counting_builder()
+    assert cache.get('b', params, build_b) == 'pack1' and calls_b == [None]
+    assert cache.get('a', params, build, extra=(False,)) == 'pack6' and len(calls) == 6
+    assert cache.get('b', params, build_b) == 'pack1' and len(calls_b) == 1
+    with torch.no_grad():
+        lin.weight.add_(1.0)
+    assert cache.get('b', params, build_b) == 'pack2' and calls_b == [None, 'pack1']
+    assert cache.get('a', params, build, extra=(False,)) == 'pack7'
+    # the builder runs without a graph, whatever the caller's mode
+    seen = []
+    with torch.enable_grad():
+        cache.get('c', params, lambda prev: seen.append(torch.is_grad_enabled()))
+    assert seen == [False]
+    # the key is the epoch + (version, address) of EVERY parameter
+    assert cache.key(params) == (cache.epoch,) + tuple((p._version, p.data_ptr()) for p in params)
+
+
+def _pack_modules():
+    import psnerf_amd.stage1 as s1
+    import psnerf_amd.stage2 as s2
+    from psnerf_amd.synthetic import stage1_cfg
+    return {'stage1.NeuralNetwork': lambda: s1.NeuralNetwork(stage1_cfg('bunny')),
+            'stage2.MLP': lambda: s2.MLP(9, 3, 64, 3, skip_at=[1]),
+            'stage2.PSNetwork': lambda: s2.PSNetwork(s2.bear_conf())}
+
+
+@pytest.mark.parametrize('which', ['stage1.NeuralNetwork', 'stage2.MLP', 'stage2.PSNetwork'])
+def test_pack_cache_module_hooks(which):
+    """load_state_dict (copying and assign=True), .double() and invalidate_packs() drop the packs of every module that owns
+    some, through the module's own hooks; the cache is no part of the state dict."""
+    import torch
+    from psnerf_amd import fused
+    net = _pack_modules()[which]()
+    assert isinstance(net.packs, fused.PackCache)
+    assert not any('pack' in k for k in net.state_dict().keys())
+    calls, build = _counting_builder()
+    get = lambda: net.packs.get('t', net.parameters(), build)
+    assert get() == 'pack1' and get() == 'pack1' and calls == [None]
+    sd = {k: v.clone() for k, v in net.state_dict().items()}
+    e = net.packs.epoch
+    net.load_state_dict(sd)
+    assert net.packs.epoch > e and get() == 'pack2' and get() == 'pack2'
+    e = net.packs.epoch
+    net.load_state_dict({k: v.clone() for k, v in sd.items()}, assign=True)
+    assert net.packs.epoch > e and get() == 'pack3' and get() == 'pack3'
+    e = net.packs.epoch
+    net.double()
+    assert net.packs.epoch > e and get() == 'pack4' and get() == 'pack4'
+    next(iter(net.parameters())).data.mul_(0.5)     # silent by contract ...
+    assert get() == 'pack4'
+    net.invalidate_packs()                          # ... announced by the caller
+    assert get() == 'pack5' and calls == [None, 'pack1', 'pack2', 'pack3', 'pack4']
+
+
+def test_pack_cache_psnetwork_levels():
+    """PSNetwork: load_state_dict / .double() reach the hooks of every MLP below it, and invalidate_packs(trainable_only=True)
+    leaves the epoch of an MLP without a trainable parameter alone."""
+    import psnerf_amd.stage2 as s2
+    net = s2.PSNetwork(s2.bear_conf())
+    mlps = [m for m in net.modules() if isinstance(m, s2.MLP)]
+    assert net.visibility_net in mlps and net.albedo_net in mlps and len(mlps) >= 3
+    epochs = lambda: [m.packs.epoch for m in mlps]
+    e = epochs()
+    net.load_state_dict({k: v.clone() for k, v in net.state_dict().items()})
+    assert all(b > a for a, b in zip(e, epochs()))
+    e = epochs()
+    net.double()
+    assert all(b > a for a, b in zip(e, epochs()))
+    net.albedo_net.requires_grad_(False)
+    frozen = [m for m in mlps if not any(p.requires_grad for p in m.parameters())]
+    assert net.albedo_net in frozen and net.visibility_net not in frozen
+    e, e_model = epochs(), net.packs.epoch
+    net.invalidate_packs(trainable_only=True)
+    for m, a, b in zip(mlps, e, epochs()):
+        assert (b == a) if m in frozen else (b > a)
+    assert net.packs.epoch > e_model                # (the model-level epoch keys the visibility packs)
+    e, e_model = epochs(), net.packs.epoch
+    net.invalidate_packs()
+    assert all(b > a for a, b in zip(e, epochs())) and net.packs.epoch > e_model

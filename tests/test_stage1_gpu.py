@@ -932,3 +932,51 @@ def test_x3_occupancy_engine_passes_the_march_and_light_visibility_goldens(cuda)
         assert_close(lv, g['light_vis'], 1e-4, 'light visibility', atol=ATOL_UNIT)
     finally:
         net.inference_precision = 'fp32'
+
+
+def test_invalidate_packs_after_data_edit_stage1(cuda):
+    """The stage-1 counterpart of test_stage2_gpu.test_invalidate_packs_after_data_edit: every weight pack of NeuralNetwork
+    (occupancy, geometry / appearance chains, negated logit) is cached by parameter version + storage address; an edit through
+    ``.data`` changes neither, so callers announce it with invalidate_packs(); load_state_dict invalidates by itself.  Unchanged
+    parameters: a second call runs on the cached packs and is bit-identical.
+    "Changed" = max |difference| > 1e-4: the edits scale a hidden layer's weight_g by 1.5 / 0.5 (an O(1) change of every
+    output; weight_v would not do, w = g v / |v| is invariant to its scale), fp32 rounding is ~1e-6."""
+    from psnerf_amd.stage1 import NeuralNetwork
+    g = np.load(os.path.join(GOLDEN, 'stage1_net_h256.npz'))
+    cfg = stage1_cfg('bunny')
+    net = NeuralNetwork(cfg)
+    net.load_state_dict(stage1_state_dict(cfg, seed=11))
+    net.to(cuda)
+    p, ray_d = T(g['p'], cuda), T(g['ray_d'], cuda)
+    flat = p.reshape(-1, 3).contiguous()
+
+    def run():
+        with torch.no_grad():
+            occ = net.occupancy(flat).clone()
+            logit = net._logit_packed().on_points(flat, net.octaves_pe, 1.0 / net.rescale).clone()
+        rgb = net(p.clone(), ray_d).detach().clone()  # (with a graph: the fused geometry / appearance chains)
+        return {'occupancy': occ, 'render': rgb, 'logit': logit}
+
+    def assert_same(x, y):
+        for k in x:
+            assert torch.equal(x[k], y[k]), k
+
+    def assert_changed(x, y):
+        for k in x:
+            d = float((x[k] - y[k]).abs().max())
+            print('%s: max |difference| %.3e' % (k, d))
+            assert d > 1e-4, k
+
+    a = run()
+    assert_same(a, run())
+    net.lin2.weight_g.data.mul_(1.5)  # no version bump
+    net.invalidate_packs()
+    b = run()
+    assert_changed(a, b)
+    assert_same(b, run())
+    sd = {k: v.clone() for k, v in net.state_dict().items()}
+    sd['lin3.weight_g'] = sd['lin3.weight_g'] * 0.5
+    net.load_state_dict(sd)
+    c = run()
+    assert_changed(b, c)
+    assert_same(c, run())
