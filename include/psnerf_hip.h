@@ -849,6 +849,45 @@ int psn_closest_point(const PsnTriGrid* grid, const double* vertices, const int6
                       const int* list, const int* over_list, int64_t n_over, const double* points, const int64_t* order,
                       int64_t n_points, double* closest, double* dist, int64_t* tri, long long* n_tests, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Image evaluation: what the reference's evaluation.py computes per image pair and per view (csrc/imgmetrics.hip; the float64
+ * numpy definition is psnerf_amd/imgmetrics.py:host_*).  float64 arithmetic, no floating-point atomics: each call writes one row
+ * of partial sums per tile / chunk into ``partial`` (psn_img_workspace doubles; every row written on every call) and a second,
+ * fixed-order step adds them, so two calls on the same input give the same bits everywhere.
+ *   images   pred / gt [B, H, W, 3], both PSN_IMG_F32 (float) or both PSN_IMG_U8 (a byte u is the float32 value (float)u / 255.0f);
+ *            PSN_IMG_MIN_EXTENT <= H, W <= PSN_IMG_MAX_EXTENT (the 11-tap window must fit), 1 <= B <= 65535.
+ *   mask     bytes (0 / non-0) [mask_batch, H, W] with mask_batch = B or 1 (one mask for every image), or null = every pixel.
+ *
+ * psn_img_scale_sums: sums [B, 7] = per image the masked sums of pred * gt per channel (3), of pred * pred per channel (3) and the
+ *   number of masked pixels (1): the terms of evaluation.py:15-24 (scale = mean over the channels of the quotients).
+ * psn_img_metrics: the fused pass.  scale: null, or double [B]: pred becomes clip(pred * scale [b], 0, 1).  Then both images are
+ *   composited onto white outside the mask.  ssim [B]: skimage's structural_similarity(data_range=1, channel_axis=2,
+ *   gaussian_weights=True, sigma=1.5, use_sample_covariance=False) of the composited pair -- 11 taps, scipy's 'reflect' border,
+ *   axis 0 filtered before axis 1, the mean over the map with a 5-pixel border cropped, per channel, then over the channels.
+ *   psnr [B]: -10 log10 of the mean squared difference over the masked pixels and the three channels; 100 if that is 0.
+ *   sums [B, 7]: cropped sum of the SSIM map per channel (3), masked squared error per channel (3), masked pixels (1).
+ *   ssim_map: null, or double [B, H, W, 3], the uncropped map.
+ * psn_normal_mae: pred / gt float [B, n_pixels, 3] normal maps; stage2/utils/metrics.py:17-37: v / (|v| + 1e-5) if normalize
+ *   (a zero vector stays zero and gives 90 degrees), the dot product clipped to [-1, 1], acos in degrees.  sums [B, 2] = the
+ *   masked sum of the errors and the number of masked pixels; err_map: null, or double [B, n_pixels], every pixel's error.
+ * psn_img_workspace: the doubles ``partial`` must hold for (which, B, H, W) (normal MAE: H * W = n_pixels); -1 on a bad argument.
+ * Errors: PSN_E_ARG for null pointers, an unknown image_type, sizes out of range, a mask batch that is neither 1 nor B; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_IMG_F32 0
+#define PSN_IMG_U8 1
+#define PSN_IMG_MIN_EXTENT 11
+#define PSN_IMG_MAX_EXTENT 16384
+#define PSN_IMG_WS_SCALE_SUMS 0
+#define PSN_IMG_WS_METRICS 1
+#define PSN_IMG_WS_NORMAL_MAE 2
+int64_t psn_img_workspace(int which, int B, int H, int W);
+int psn_img_scale_sums(const void* pred, const void* gt, int image_type, const unsigned char* mask, int mask_batch, int B, int H, int W,
+                       double* partial, double* sums, void* stream);
+int psn_img_metrics(const void* pred, const void* gt, int image_type, const unsigned char* mask, int mask_batch, const double* scale, int B,
+                    int H, int W, double* partial, double* sums, double* ssim, double* psnr, double* ssim_map, void* stream);
+int psn_normal_mae(const float* pred, const float* gt, const unsigned char* mask, int mask_batch, int normalize, int B, int64_t n_pixels,
+                   double* partial, double* sums, double* err_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,10 @@ SIGNATURES = {
     'psn_tri_grid_count': (i32, [c_f, c_f, c_f, i64, c_f, c_f, c_f, c_f]),
     'psn_tri_grid_fill': (i32, [c_f, c_f, c_f, i64, c_f, i64, c_f, c_f]),
     'psn_closest_point': (i32, [c_f, c_f, c_f, i64, c_f, c_f, c_f, i64, c_f, c_f, i64, c_f, c_f, c_f, c_f, c_f]),
+    'psn_img_workspace': (i64, [i32, i32, i32, i32]),
+    'psn_img_scale_sums': (i32, [c_f, c_f, i32, c_f, i32, i32, i32, i32, c_f, c_f, c_f]),
+    'psn_img_metrics': (i32, [c_f, c_f, i32, c_f, i32, c_f, i32, i32, i32, c_f, c_f, c_f, c_f, c_f, c_f]),
+    'psn_normal_mae': (i32, [c_f, c_f, c_f, i32, i32, i32, i64, c_f, c_f, c_f, c_f]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(_lib, _name)  # AttributeError here = library out of date: fail loudly
@@ -1706,3 +1710,115 @@ def closest_point(grid, vertices, faces, cell_start, lst, over_list, n_over, poi
                                       closest.data_ptr(), dist.data_ptr(), tri.data_ptr(),
                                       None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'closest_point')
     return closest, dist, tri
+
+
+# --------------------------------------------------------------------------- image evaluation (csrc/imgmetrics.hip)
+IMG_TYPES = {torch.float32: 0, torch.uint8: 1}   # PSN_IMG_F32 / PSN_IMG_U8
+IMG_MIN_EXTENT = 11
+IMG_WS_SCALE_SUMS, IMG_WS_METRICS, IMG_WS_NORMAL_MAE = range(3)
+
+
+def _img_pair(what, pred, gt, mask):
+    """The checks every image entry shares -> (image_type, mask pointer or None, mask batch, B, H, W)."""
+    for name, t in (('pred', pred), ('gt', gt)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError('%s: %s must be a HIP device tensor (the product path has no CPU fallback; host arrays: '
+                               'psnerf_amd.imgmetrics.host_*)' % (what, name))
+        if t.dtype not in IMG_TYPES:
+            raise RuntimeError('%s: %s must be float32 or uint8, got %s' % (what, name, t.dtype))
+        if t.dim() != 4 or t.shape[3] != 3:
+            raise RuntimeError('%s: %s [B, H, W, 3] expected, got %s' % (what, name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise RuntimeError('%s: %s must be contiguous' % (what, name))
+    if pred.dtype != gt.dtype:
+        raise RuntimeError('%s: pred is %s and gt is %s (one dtype for the pair)' % (what, pred.dtype, gt.dtype))
+    if pred.shape != gt.shape:
+        raise RuntimeError('%s: shape mismatch, pred %s and gt %s' % (what, tuple(pred.shape), tuple(gt.shape)))
+    B, H, W = (int(x) for x in pred.shape[:3])
+    if B < 1 or H < IMG_MIN_EXTENT or W < IMG_MIN_EXTENT:
+        raise RuntimeError('%s: %d images of %d x %d pixels (at least one, and at least %d pixels per extent: the 11-tap window must fit)'
+                           % (what, B, H, W, IMG_MIN_EXTENT))
+    mp, mb = _mask_ptr(what, mask, B, (H, W), pred.device)
+    return IMG_TYPES[pred.dtype], mp, mb, B, H, W
+
+
+def _mask_ptr(what, mask, B, tail, device):
+    """mask: None, or a uint8 / bool device tensor [B or 1, *tail] -> (pointer or None, mask batch)."""
+    if mask is None:
+        return None, 1
+    if not torch.is_tensor(mask) or not mask.is_cuda:
+        raise RuntimeError('%s: mask must be a HIP device tensor' % what)
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise RuntimeError('%s: mask must be uint8 or bool, got %s' % (what, mask.dtype))
+    if mask.dim() != 1 + len(tail) or tuple(mask.shape[1:]) != tuple(tail):
+        raise RuntimeError('%s: mask [B or 1, %s] expected, got %s' % (what, ', '.join(str(x) for x in tail), tuple(mask.shape)))
+    if mask.shape[0] not in (1, B):
+        raise RuntimeError('%s: mask batch %d is neither 1 nor B = %d' % (what, mask.shape[0], B))
+    if not mask.is_contiguous() or mask.device != device:
+        raise RuntimeError('%s: mask must be contiguous and on the images\' device' % what)
+    return mask.data_ptr(), int(mask.shape[0])
+
+
+def _img_partial(which, B, H, W, device):
+    n = int(_lib.psn_img_workspace(which, B, H, W))
+    if n < 0:
+        raise RuntimeError('psn_img_workspace(%d, %d, %d, %d) refused' % (which, B, H, W))
+    return torch.empty(n, dtype=torch.float64, device=device)
+
+
+def img_scale_sums(pred, gt, mask):
+    """psn_img_scale_sums: pred / gt [B, H, W, 3] (float32 or uint8), mask [B or 1, H, W] (uint8 / bool) or None ->
+    (sums float64 [B, 7] = masked sum of pred * gt per channel, of pred * pred per channel, masked pixels; partial rows)."""
+    ty, mp, mb, B, H, W = _img_pair('img_scale_sums', pred, gt, mask)
+    partial = _img_partial(IMG_WS_SCALE_SUMS, B, H, W, pred.device)
+    sums = torch.empty(B, 7, dtype=torch.float64, device=pred.device)
+    with _Prof('img_scale_sums', B * H * W * (2 * 3 * pred.element_size() + 1)):
+        _check(_lib.psn_img_scale_sums(pred.data_ptr(), gt.data_ptr(), ty, mp, mb, B, H, W, partial.data_ptr(), sums.data_ptr(), _stream()),
+               'img_scale_sums')
+    return sums, partial
+
+
+def img_metrics(pred, gt, mask, scale=None, full=False):
+    """psn_img_metrics, the fused pass: pred / gt [B, H, W, 3] (float32 or uint8), mask [B or 1, H, W] or None, scale float64 [B] or
+    None -> dict(ssim [B], psnr [B], sums [B, 7], partial, map [B, H, W, 3] or None), all float64 device tensors."""
+    ty, mp, mb, B, H, W = _img_pair('img_metrics', pred, gt, mask)
+    dev = pred.device
+    if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda and scale.dtype == torch.float64 and scale.is_contiguous()
+                                  and tuple(scale.shape) == (B,)):
+        raise RuntimeError('img_metrics: scale must be a contiguous float64 HIP device tensor [%d]' % B)
+    partial = _img_partial(IMG_WS_METRICS, B, H, W, dev)
+    sums = torch.empty(B, 7, dtype=torch.float64, device=dev)
+    ssim = torch.empty(B, dtype=torch.float64, device=dev)
+    psnr = torch.empty(B, dtype=torch.float64, device=dev)
+    smap = torch.empty(B, H, W, 3, dtype=torch.float64, device=dev) if full else None
+    with _Prof('img_metrics', B * H * W * (2 * 3 * pred.element_size() + 1)):   # the compulsory bytes: two images and one mask
+        _check(_lib.psn_img_metrics(pred.data_ptr(), gt.data_ptr(), ty, mp, mb, None if scale is None else scale.data_ptr(), B, H, W,
+                                    partial.data_ptr(), sums.data_ptr(), ssim.data_ptr(), psnr.data_ptr(),
+                                    None if smap is None else smap.data_ptr(), _stream()), 'img_metrics')
+    return {'ssim': ssim, 'psnr': psnr, 'sums': sums, 'partial': partial, 'map': smap}
+
+
+def normal_mae(pred, gt, mask, normalize=True, full=False):
+    """psn_normal_mae: pred / gt float32 [B, N, 3] normal maps, mask [B or 1, N] (uint8 / bool) or None -> (sums float64 [B, 2] =
+    masked sum of the angular errors in degrees, masked pixels; partial rows; per-pixel errors [B, N] or None)."""
+    for name, t in (('pred', pred), ('gt', gt)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError('normal_mae: %s must be a HIP device tensor (the product path has no CPU fallback; host arrays: '
+                               'psnerf_amd.metrics.MAE)' % name)
+        if t.dtype != torch.float32:
+            raise RuntimeError('normal_mae: %s must be float32, got %s' % (name, t.dtype))
+        if t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous():
+            raise RuntimeError('normal_mae: %s: contiguous [B, N, 3] expected, got %s' % (name, tuple(t.shape)))
+    if pred.shape != gt.shape:
+        raise RuntimeError('normal_mae: shape mismatch, pred %s and gt %s' % (tuple(pred.shape), tuple(gt.shape)))
+    B, N = int(pred.shape[0]), int(pred.shape[1])
+    if B < 1 or N < 1:
+        raise RuntimeError('normal_mae: empty input %s' % (tuple(pred.shape),))
+    mp, mb = _mask_ptr('normal_mae', mask, B, (N,), pred.device)
+    partial = _img_partial(IMG_WS_NORMAL_MAE, B, 1, N, pred.device)
+    sums = torch.empty(B, 2, dtype=torch.float64, device=pred.device)
+    err = torch.empty(B, N, dtype=torch.float64, device=pred.device) if full else None
+    with _Prof('normal_mae', B * N * 25):
+        _check(_lib.psn_normal_mae(pred.data_ptr(), gt.data_ptr(), mp, mb, int(bool(normalize)), B, N, partial.data_ptr(), sums.data_ptr(),
+                                   None if err is None else err.data_ptr(), _stream()), 'normal_mae')
+    return sums, partial, err
