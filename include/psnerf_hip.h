@@ -110,8 +110,9 @@ int psn_gemm(int trans_a, int trans_b, int64_t M, int N, int K, const float* A, 
  * with A_i = dZ_i [K, M_i], B_i = the layer input [K, N_i] (row-major, row strides lda / ldb), all sharing K = the
  * number of rows of the pass.  One launch over all items + one reduction launch; split_k slices of K per product.
  * The optional second product covers a layer that is used twice (stage1/model/network.py:108-120: value pass and
- * gradient sweep share the weights).  n_items <= 12.  workspace: sum over items of
+ * gradient sweep share the weights).  n_items <= PSN_GEMM_TN_MAX_ITEMS.  workspace: sum over items of
  * n_products * split_k * M * N + split_k * M floats (+ 8 floats of padding per item). */
+#define PSN_GEMM_TN_MAX_ITEMS 12
 typedef struct {
     const float* A; int64_t lda;
     const float* B; int64_t ldb;

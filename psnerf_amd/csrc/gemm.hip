@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
 // needs ~128 split-K slices to fill 256 CUs and then spends as long reducing 128 partial tiles as multiplying; sixteen
 // of them together fill the chip with 8 slices each.  Block ranges are padded to multiples of 8 so that the XCD-aware
 // work order of gemm_tile stays aligned with the hardware's block -> XCD round robin.
-constexpr int kMaxGroup = 12;
+constexpr int kMaxGroup = PSN_GEMM_TN_MAX_ITEMS;
 struct GroupedArgs {
     int n;
     int64_t block_start[kMaxGroup + 1];

@@ -1,7 +1,9 @@
 """ctypes binding of libpsnerf_hip.so (C ABI in include/psnerf_hip.h).
 
 Importing this module loads the shared library and FAILS LOUDLY if it is
-missing -- there is no CPU or PyTorch fallback on the product path.  Wrappers
+missing -- there is no CPU or PyTorch fallback on the product path.  The
+prototypes, structs and constants are not repeated here: cabi.parse reads them
+from the header at import, and a symbol the library lacks fails right there.  Wrappers
 take torch tensors only as carriers of device pointers: they validate
 device / dtype / contiguity, pass ``data_ptr()`` and the current HIP stream,
 and raise RuntimeError with ``psn_last_error()`` on failure.
@@ -10,6 +12,8 @@ import ctypes
 import os
 
 import torch
+
+from . import cabi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libpsnerf_hip.so')
@@ -20,208 +24,17 @@ if not os.path.exists(LIB_PATH):
         'There is no fallback path.' % LIB_PATH)
 _lib = ctypes.CDLL(LIB_PATH)
 
-c_f = ctypes.c_void_p  # device pointers travel as void*
-i64, i32, f32 = ctypes.c_int64, ctypes.c_int, ctypes.c_float
+HEADER_PATH = os.path.join(_HERE, '..', 'include', 'psnerf_hip.h')
+if not os.path.exists(HEADER_PATH):
+    raise ImportError('psnerf_amd: %s is missing: the binding is derived from it. There is no fallback path.' % HEADER_PATH)
 
-MAX_LAYERS = 12
-(EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_SOFTPLUS, EPI_MUL_AUX, EPI_MUL_POS, EPI_BIAS_SIGMOID, EPI_ACCUM,
- EPI_MUL2, EPI_SOFTPLUS_BWD, EPI_MUL_AUX_RAW) = range(11)
-(ACT_NONE, ACT_RELU, ACT_SOFTPLUS100, ACT_RELU_MASK, ACT_MUL_AUX, ACT_MUL2, ACT_SOFTPLUS_BWD,
- ACT_HEAD, ACT_RELU_BITS, ACT_MUL_AUX_A, ACT_MUL2_A, ACT_SOFTPLUS_BWD_A) = range(12)
-OUT_NONE, OUT_SIGMOID, OUT_OCC = range(3)
-W_F32, W_BF16X2 = range(2)  # PsnMlpDesc.w_format / PsnPackItem.format
-
-
-class PsnMlpLayer(ctypes.Structure):
-    _fields_ = [('n_kt_in', i32), ('n_kt_act', i32), ('n_mt', i32), ('act', i32), ('w_off', i64), ('b_off', i64),
-                ('init_off', i64)]
-
-
-class PsnMlpDesc(ctypes.Structure):
-    _fields_ = [('n_layers', i32), ('n_out', i32), ('out_act', i32), ('in_kt_a', i32), ('in_kt_b', i32),
-                ('init_stride', i32), ('w_format', i32), ('layers', PsnMlpLayer * MAX_LAYERS)]
-
-
-class PsnBf16Desc(ctypes.Structure):
-    _fields_ = [('n_hidden', i32), ('n_out', i32), ('out_act', i32), ('reserved', i32),
-                ('has_in', ctypes.c_uint8 * (MAX_LAYERS + 4))]
-
-
-class PsnScatterItem(ctypes.Structure):
-    _fields_ = [('rows', ctypes.c_void_p), ('dense', ctypes.c_void_p), ('row_stride', i64), ('col_stride', i64),
-                ('B', i32), ('C', i32), ('fill', f32)]
-
-
-class PsnPackItem(ctypes.Structure):
-    _fields_ = [('W', ctypes.c_void_p), ('dst', ctypes.c_void_p), ('ldw', i64), ('rows', i32), ('cols', i32),
-                ('transpose', i32), ('n_mt', i32), ('k_tiles', i32), ('format', i32)]
-
-
-class PsnWnItem(ctypes.Structure):
-    _fields_ = [('v', ctypes.c_void_p), ('g', ctypes.c_void_p), ('w', ctypes.c_void_p), ('dw', ctypes.c_void_p),
-                ('dv', ctypes.c_void_p), ('dg', ctypes.c_void_p), ('rows', i32), ('cols', i32), ('scale', f32)]
-
-
-class PsnGemmTnItem(ctypes.Structure):
-    _fields_ = [('A', ctypes.c_void_p), ('lda', i64), ('B', ctypes.c_void_p), ('ldb', i64),
-                ('A2', ctypes.c_void_p), ('lda2', i64), ('B2', ctypes.c_void_p), ('ldb2', i64),
-                ('C', ctypes.c_void_p), ('ldc', i64), ('M', i32), ('N', i32), ('accumulate', i32),
-                ('colsum_a', ctypes.c_void_p), ('b_div', i64), ('b_mod', i64),
-                ('B_tab2', ctypes.c_void_p), ('ldb_tab2', i64), ('b2_div', i64), ('b2_mod', i64), ('b_split', i32), ('k_rows', i64)]
-
-
-class PsnPairSumsItem(ctypes.Structure):
-    _fields_ = [('x', ctypes.c_void_p), ('sx', ctypes.c_void_p), ('dWl', ctypes.c_void_p), ('bias', ctypes.c_void_p)]
-
-
-class PsnCopy2dItem(ctypes.Structure):
-    _fields_ = [('src', ctypes.c_void_p), ('ld_src', i64), ('dst', ctypes.c_void_p), ('ld_dst', i64), ('rows', i32), ('cols', i32)]
-
-
-COPY2D_MAX = 24
-
-
-class PsnCopyBytesItem(ctypes.Structure):
-    _fields_ = [('src', ctypes.c_void_p), ('dst', ctypes.c_void_p), ('n_bytes', i64), ('aligned', i32)]
-
-
-COPY_BYTES_MAX = 24
-
-
-class PsnAdamSeg(ctypes.Structure):
-    _fields_ = [('offset', i64), ('grad_offset', i64), ('n', i64), ('neg_step_size', f32), ('bias_correction2_sqrt', f32)]
-
-
-ADAM_MAX_SEGS = 16
-
-
-class PsnViewBatch(ctypes.Structure):
-    _fields_ = [('images', ctypes.c_void_p), ('image_type', i32), ('lut', ctypes.c_void_p),
-                ('object_mask', ctypes.c_void_p), ('surface_mask', ctypes.c_void_p),
-                ('points', ctypes.c_void_p), ('normal', ctypes.c_void_p), ('visibility', ctypes.c_void_p), ('vis_plus', ctypes.c_void_p),
-                ('light_direction', ctypes.c_void_p),
-                ('hw', i64), ('width', i32),
-                ('lidx', ctypes.c_void_p), ('n_lights', i32),
-                ('pix', ctypes.c_void_p), ('pix0', i64), ('n', i64),
-                ('vidx', ctypes.c_void_p), ('n_vis', i32),
-                ('rgb', ctypes.c_void_p), ('object_mask_out', ctypes.c_void_p), ('surface_mask_out', ctypes.c_void_p), ('uv', ctypes.c_void_p),
-                ('points_out', ctypes.c_void_p), ('normal_out', ctypes.c_void_p), ('visibility_out', ctypes.c_void_p),
-                ('vis_train_gt', ctypes.c_void_p), ('sampling_idx_out', ctypes.c_void_p), ('light_direction_out', ctypes.c_void_p)]
-
-
-class PsnRowAdamItem(ctypes.Structure):
-    _fields_ = [('param', ctypes.c_void_p), ('grad', ctypes.c_void_p), ('exp_avg', ctypes.c_void_p), ('exp_avg_sq', ctypes.c_void_p),
-                ('rows', i64), ('cols', i32), ('one_minus_beta1', f32), ('one_minus_beta2', f32), ('eps', f32), ('step_size', f32)]
-
-
-class PsnTriGrid(ctypes.Structure):
-    _fields_ = [('lo', ctypes.c_double * 3), ('hi', ctypes.c_double * 3), ('cell', ctypes.c_double), ('n', i32 * 3), ('max_span', i32)]
-
-
-MAX_GROUP = 12
-
-# every exported symbol of include/psnerf_hip.h with its signature
-SIGNATURES = {
-    'psn_last_error': (ctypes.c_char_p, []),
-    'psn_version': (i32, []),
-    'psn_composite_fwd': (i32, [c_f, c_f, i64, i32, i32, c_f, c_f, c_f, c_f]),
-    'psn_composite_bwd': (i32, [c_f, c_f, c_f, c_f, i64, i32, i32, c_f, c_f, c_f]),
-    'psn_pe_encode': (i32, [c_f, i64, i32, f32, c_f, i32, c_f]),
-    'psn_pe_encode_bwd': (i32, [c_f, c_f, i64, i32, f32, i32, c_f, i32, c_f, c_f]),
-    'psn_app_input': (i32, [c_f, c_f, c_f, i64, i32, c_f, c_f]),
-    'psn_pe_encode_jvp': (i32, [c_f, c_f, i64, i32, f32, c_f, i32, c_f]),
-    'psn_gemm': (i32, [i32, i32, i64, i32, i32, c_f, i64, c_f, i64, c_f, i64, c_f, i32, c_f, i64, c_f, i64, c_f, i64,
-                       i32, c_f, c_f, c_f]),
-    'psn_gemm_tn_grouped': (i32, [i32, ctypes.c_void_p, i64, i32, c_f, i64, c_f]),
-    'psn_gemm_tn_x3_set_products': (i32, [i32]),
-    'psn_mlp_block_order': (i32, [i32]),
-    'psn_gemm_tn_grouped_x3': (i32, [i32, ctypes.c_void_p, i64, i32, c_f, i64, c_f]),
-    'psn_colsum': (i32, [c_f, c_f, i32, i64, i64, i32, i64, c_f, i32, c_f, c_f]),
-    'psn_sample_points': (i32, [c_f, c_f, c_f, c_f, c_f, i64, i32, f32, f32, c_f, c_f, i32, c_f, c_f, i32, c_f, c_f, c_f]),
-    'psn_sample_points_flagged': (i32, [c_f, c_f, c_f, c_f, c_f, i64, f32, f32, c_f, c_f, i32, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f]),
-    'psn_mlp_pack_layer': (i32, [c_f, i64, i32, i32, i32, i32, i32, c_f, c_f]),
-    'psn_mlp_pack_layers': (i32, [i32, ctypes.c_void_p, c_f]),
-    'psn_sg_shade_fwd': (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, f32, c_f, i32, i64, i32, i32, c_f, c_f, c_f]),
-    'psn_sg_shade_bwd': (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, f32, c_f, i32, i64, i32, i32, c_f, c_f, c_f, c_f,
-                               c_f, c_f, c_f, c_f, c_f, c_f]),
-    'psn_mf_shade_fwd': (i32, [c_f, c_f, c_f, c_f, c_f, c_f, f32, f32, c_f, i32, i64, c_f, c_f]),
-    'psn_mf_shade_bwd': (i32, [c_f, c_f, c_f, c_f, c_f, c_f, f32, f32, c_f, i32, i64, c_f, c_f, c_f, c_f, c_f, c_f,
-                               c_f, c_f, c_f]),
-    'psn_mlp_infer': (i32, [ctypes.POINTER(PsnMlpDesc), c_f, c_f, c_f, i64, i64, c_f, i64, i64, c_f, c_f,
-                            ctypes.POINTER(ctypes.c_void_p), i64, ctypes.POINTER(ctypes.c_void_p),
-                            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), c_f, i64, c_f, c_f, i32,
-                            ctypes.POINTER(ctypes.c_uint32), i64, c_f, c_f]),
-    'psn_mlp_infer_padded': (i32, [ctypes.POINTER(PsnMlpDesc), c_f, c_f, c_f, i64, i64, c_f, i64, i64, c_f, c_f,
-                                   ctypes.POINTER(ctypes.c_void_p), i64, i64, c_f, c_f, i64, c_f]),
-    'psn_mlp_infer_bits': (i32, [ctypes.POINTER(PsnMlpDesc), c_f, c_f, c_f, i64, i64, c_f, i64, i64, c_f, c_f,
-                                 ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), i64, i64, c_f, c_f, i64, c_f]),
-    'psn_scatter_rows': (i32, [i32, ctypes.c_void_p, c_f, i64, i64, c_f]),
-    'psn_gather_rows': (i32, [i32, ctypes.c_void_p, c_f, i64, i64, c_f]),
-    'psn_gather_rows_valid': (i32, [i32, ctypes.c_void_p, c_f, c_f, i64, i64, c_f]),
-    'psn_surface_index': (i32, [c_f, i64, i64, c_f, c_f, c_f]),
-    'psn_view_batch': (i32, [ctypes.c_void_p, c_f]),
-    'psn_secant_step': (i32, [c_f, f32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, c_f]),
-    'psn_first_crossing': (i32, [c_f, c_f, c_f, c_f, f32, f32, i64, i32, c_f, c_f, c_f]),
-    'psn_stage2_loss_fwd': (i32, [c_f, c_f, i32, c_f, c_f, c_f, c_f, i32, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f, i64, i32, c_f, c_f, c_f,
-                                  c_f, c_f, c_f]),
-    'psn_stage2_loss_bwd': (i32, [c_f, c_f, c_f, i32, f32, c_f, c_f, c_f, f32, c_f, c_f, c_f, c_f, i32, f32, c_f, c_f, c_f, c_f, i32, f32,
-                                  c_f, c_f, c_f, c_f, f32, f32, c_f, c_f, c_f, c_f, i64, i32, c_f, c_f]),
-    'psn_pair_sums': (i32, [c_f, i32, i64, i32, c_f, c_f, ctypes.POINTER(ctypes.c_int), c_f]),
-    'psn_pair_sums_group_workspace': (i64, [i32, i32, i64, i32]),
-    'psn_pair_sums_group': (i32, [i32, ctypes.c_void_p, i32, i64, i32, c_f, i64, i32, i64, c_f, c_f]),
-    'psn_row_adam': (i32, [i32, ctypes.c_void_p, c_f, i32, c_f]),
-    'psn_row_adam_dev': (i32, [i32, ctypes.c_void_p, c_f, i32, c_f, c_f]),
-    'psn_shadow_points': (i32, [c_f, c_f, i64, i32, i32, f32, f32, c_f, c_f, f32, c_f, c_f, c_f, c_f]),
-    'psn_mlp_infer_pe': (i32, [ctypes.POINTER(PsnMlpDesc), c_f, c_f, c_f, i64, i32, f32, c_f, c_f]),
-    'psn_mlp_infer_pe_indirect': (i32, [ctypes.POINTER(PsnMlpDesc), c_f, c_f, c_f, i64, c_f, c_f, i32, f32, c_f, c_f]),
-    'psn_root_find': (i32, [ctypes.POINTER(PsnMlpDesc), c_f, c_f, c_f, c_f, c_f, i64, f32, i32, i32, f32, c_f, c_f]),
-    'psn_march_sweep': (i32, [ctypes.POINTER(PsnMlpDesc), c_f, c_f, c_f, c_f, c_f, c_f, c_f, f32, i64, i32, f32, i32, f32, c_f, c_f, c_f, c_f]),
-    'psn_normalize_rows_fwd': (i32, [c_f, i64, f32, c_f, c_f]),
-    'psn_normalize_rows_bwd': (i32, [c_f, c_f, i64, f32, c_f, c_f]),
-    'psn_light_rows_fwd': (i32, [c_f, c_f, c_f, i32, f32, c_f, c_f, c_f]),
-    'psn_light_rows_bwd': (i32, [c_f, c_f, i32, i64, f32, c_f, c_f, c_f, c_f, c_f]),
-    'psn_camera_rays': (i32, [c_f, c_f, c_f, c_f, i64, f32, c_f, c_f]),
-    'psn_stage1_loss_partial_floats': (i32, []),
-    'psn_stage1_loss_fwd': (i32, [c_f] * 10 + [i64, i64, ctypes.c_void_p, c_f, c_f, c_f, c_f]),
-    'psn_stage1_loss_terms': (i32, [c_f, i64, ctypes.c_void_p, i32, i32, i32, c_f, c_f]),
-    'psn_stage1_loss_bwd': (i32, [c_f] * 11 + [i64, i64, ctypes.c_void_p, c_f, c_f, c_f, c_f, c_f]),
-    'psn_surface_normals_fwd': (i32, [c_f, c_f, i64, f32, c_f, c_f, c_f]),
-    'psn_surface_normals_bwd': (i32, [c_f, c_f, i64, f32, c_f, c_f, c_f, c_f]),
-    'psn_stage1_rays': (i32, [c_f, c_f, i32, c_f, f32, i64, c_f, c_f, c_f, c_f]),
-    'psn_surface_points': (i32, [c_f, c_f, c_f, c_f, i64, c_f, c_f, c_f, c_f, c_f]),
-    'psn_stage1_targets': (i32, [c_f, i64, i32, i32, c_f, c_f, c_f, c_f, c_f, c_f, i32, f32, c_f, c_f, c_f, c_f, c_f, c_f]),
-    'psn_copy2d_group': (i32, [i32, ctypes.c_void_p, c_f]),
-    'psn_copy_bytes_group': (i32, [i32, ctypes.c_void_p, c_f]),
-    'psn_mask_count': (i32, [c_f, c_f, i64, c_f, c_f]),
-    'psn_inverse_index': (i32, [c_f, i64, i64, c_f, c_f, c_f]),
-    'psn_adam_flat': (i32, [c_f, c_f, c_f, c_f, i32, ctypes.c_void_p, f32, f32, f32, f32, c_f]),
-    'psn_adam_flat_dev': (i32, [c_f, c_f, c_f, c_f, i32, ctypes.c_void_p, f32, f32, f32, f32, c_f, c_f]),
-    'psn_weight_norm_fwd': (i32, [i32, ctypes.c_void_p, c_f]),
-    'psn_weight_norm_bwd': (i32, [i32, ctypes.c_void_p, c_f]),
-    'psn_mlp_pack_bf16': (i32, [c_f, i64, i32, i32, i32, i32, i32, i32, c_f, c_f]),
-    'psn_mlp_infer_bf16': (i32, [ctypes.POINTER(PsnBf16Desc), c_f, c_f, c_f, i64, i64, c_f, i64, i64, i64, c_f, c_f]),
-    'psn_mlp_infer_bf16_grouped': (i32, [ctypes.POINTER(PsnBf16Desc), c_f, c_f, c_f, i64, c_f, i64, c_f, c_f]),
-    'psn_bf16_pack_group_bias': (i32, [c_f, i64, c_f, c_f]),
-    'psn_x3_pack': (i32, [c_f, i64, i32, i32, i32, i32, i32, i32, c_f, c_f]),
-    'psn_x3_pack_bias': (i32, [c_f, i64, c_f, c_f]),
-    'psn_mlp_infer_x3_grouped': (i32, [ctypes.POINTER(PsnBf16Desc), c_f, c_f, c_f, c_f, i64, c_f, i64, c_f, c_f]),
-    'psn_mlp_infer_x3_occ': (i32, [ctypes.POINTER(PsnBf16Desc), c_f, c_f, c_f, c_f, i64, c_f, c_f, i32, f32, i32, i32, c_f, c_f]),
-    'psn_march_sweep_x3': (i32, [ctypes.POINTER(PsnBf16Desc), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, f32, i64, i32, f32, i32, f32, i32, i32,
-                                 c_f, c_f, c_f, c_f]),
-    'psn_mise_collect': (i32, [c_f, i32, f32, i64, c_f, c_f, c_f, c_f]),
-    'psn_mise_refine': (i32, [c_f, c_f, c_f, i32, i32, ctypes.c_double, c_f, c_f]),
-    'psn_grid_ffill': (i32, [c_f, i32, c_f]),
-    'psn_mc_blocks': (i64, [i32]),
-    'psn_mc_count': (i32, [c_f, i32, ctypes.c_double, c_f, c_f, c_f, c_f]),
-    'psn_mc_emit': (i32, [c_f, i32, ctypes.c_double, c_f, c_f, c_f, i64, i64, ctypes.c_double, c_f, c_f, c_f, c_f]),
-    'psn_tri_grid_count': (i32, [c_f, c_f, c_f, i64, c_f, c_f, c_f, c_f]),
-    'psn_tri_grid_fill': (i32, [c_f, c_f, c_f, i64, c_f, i64, c_f, c_f]),
-    'psn_closest_point': (i32, [c_f, c_f, c_f, i64, c_f, c_f, c_f, i64, c_f, c_f, i64, c_f, c_f, c_f, c_f, c_f]),
-    'psn_img_workspace': (i64, [i32, i32, i32, i32]),
-    'psn_img_scale_sums': (i32, [c_f, c_f, i32, c_f, i32, i32, i32, i32, c_f, c_f, c_f]),
-    'psn_img_metrics': (i32, [c_f, c_f, i32, c_f, i32, c_f, i32, i32, i32, c_f, c_f, c_f, c_f, c_f, c_f]),
-    'psn_normal_mae': (i32, [c_f, c_f, c_f, i32, i32, i32, i64, c_f, c_f, c_f, c_f]),
-}
+# The binding is DERIVED from the header (cabi.parse), nothing of it is written down here: every PSN_* #define and enumerator under its
+# name without the prefix (EPI_*, ACT_*, OUT_*, W_*, IMG_*, *_MAX*, ...), every Psn* struct as a ctypes structure class and every psn_*
+# prototype as SIGNATURES[name] = (restype, argtypes); pointers of every kind travel as void*.
+_constants, _structs, SIGNATURES = cabi.parse(HEADER_PATH)
+globals().update({_k[len('PSN_'):]: _v for _k, _v in _constants.items()})
+globals().update(_structs)
+MAX_LAYERS = MLP_MAX_LAYERS  # noqa: F821
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(_lib, _name)  # AttributeError here = library out of date: fail loudly
     _fn.restype = _res
@@ -259,36 +72,28 @@ def _check(rc, what):
         raise RuntimeError('%s failed (%d): %s' % (what, rc, _lib.psn_last_error().decode()))
 
 
-def _ptr(t, name, allow_none=False):
+def _tptr(t, name, dtype=torch.float32, allow_none=False, contiguous=True):
+    """Device pointer of a tensor, after the checks every wrapper shares: on the device, of ``dtype`` (one, or a tuple of the
+    admissible ones) and contiguous.  The one validator of this module; helpers that add a shape rule call it."""
     if t is None:
         if allow_none:
             return None
         raise RuntimeError('%s: tensor required' % name)
-    if not t.is_cuda:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError('%s: must be a HIP device tensor (the product path has no CPU fallback)' % name)
-    if t.dtype != torch.float32:
-        raise RuntimeError('%s: must be float32, got %s' % (name, t.dtype))
-    if not t.is_contiguous():
+    if t.dtype != dtype and (type(dtype) is not tuple or t.dtype not in dtype):
+        want = ' or '.join(str(d)[len('torch.'):] for d in (dtype if type(dtype) is tuple else (dtype,)))
+        raise RuntimeError('%s: must be %s, got %s' % (name, want, t.dtype))
+    if contiguous and not t.is_contiguous():
         raise RuntimeError('%s: must be contiguous' % name)
     return t.data_ptr()
 
 
 def _bits_ptr(t, name):
     """Device pointer of a tensor of sign-bit words ([rows, 4] int64, contiguous)."""
-    if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 4):
+    if t.dim() != 2 or t.shape[1] != 4:
         raise RuntimeError('%s: sign-bit words are a contiguous int64 [rows, 4] device tensor' % name)
-    return t.data_ptr()
-
-
-def _iptr(t, name, allow_none=False):
-    """Device pointer of an int64 index tensor."""
-    if t is None:
-        if allow_none:
-            return None
-        raise RuntimeError('%s: tensor required' % name)
-    if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous():
-        raise RuntimeError('%s: must be a contiguous int64 HIP device tensor' % name)
-    return t.data_ptr()
+    return _tptr(t, name, torch.int64)
 
 
 def _stream():
@@ -311,8 +116,8 @@ def composite_fwd(alpha, rgb, white_bg, need_weights=True):
     # algorithmic bytes: alpha 4 S (+ colour 12 S) in, weights 4 S (if kept) + rgb 12 + acc 4 out
     nbytes = N * (4 * S + (12 * S + 12 if rgb is not None else 0) + (4 * S if need_weights else 0) + 4)
     with _Prof('composite_fwd' if rgb is not None else 'composite_alpha', nbytes):
-        _check(_lib.psn_composite_fwd(_ptr(alpha, 'alpha'), _ptr(rgb, 'rgb', True), N, S, int(bool(white_bg)),
-                                      _ptr(weights, 'weights', True), _ptr(rgb_out, 'rgb_out', True), _ptr(acc, 'acc'),
+        _check(_lib.psn_composite_fwd(_tptr(alpha, 'alpha'), _tptr(rgb, 'rgb', allow_none=True), N, S, int(bool(white_bg)),
+                                      _tptr(weights, 'weights', allow_none=True), _tptr(rgb_out, 'rgb_out', allow_none=True), _tptr(acc, 'acc'),
                                       _stream()), 'composite_fwd')
     return weights, rgb_out, acc
 
@@ -322,9 +127,9 @@ def composite_bwd(alpha, rgb, d_rgb_out, d_acc, white_bg):
     d_alpha = torch.empty_like(alpha)
     d_rgb = torch.empty_like(rgb) if rgb is not None else None
     with _Prof('composite_bwd', N * (36 * S + 16)):  # 36 S + 16 bytes per ray
-        _check(_lib.psn_composite_bwd(_ptr(alpha, 'alpha'), _ptr(rgb, 'rgb', True), _ptr(d_rgb_out, 'd_rgb_out', True),
-                                      _ptr(d_acc, 'd_acc', True), N, S, int(bool(white_bg)), _ptr(d_alpha, 'd_alpha'),
-                                      _ptr(d_rgb, 'd_rgb', True), _stream()), 'composite_bwd')
+        _check(_lib.psn_composite_bwd(_tptr(alpha, 'alpha'), _tptr(rgb, 'rgb', allow_none=True), _tptr(d_rgb_out, 'd_rgb_out', allow_none=True),
+                                      _tptr(d_acc, 'd_acc', allow_none=True), N, S, int(bool(white_bg)), _tptr(d_alpha, 'd_alpha'),
+                                      _tptr(d_rgb, 'd_rgb', allow_none=True), _stream()), 'composite_bwd')
     return d_alpha, d_rgb
 
 
@@ -335,7 +140,7 @@ def pe_encode(x, n_freqs, out_stride=None, scale=1.0):
     width = 3 + 6 * n_freqs
     out_stride = width if out_stride is None else out_stride
     out = torch.empty(n, out_stride, device=x.device, dtype=torch.float32)
-    _check(_lib.psn_pe_encode(_ptr(x, 'x'), n, n_freqs, float(scale), _ptr(out, 'out'), out_stride, _stream()),
+    _check(_lib.psn_pe_encode(_tptr(x, 'x'), n, n_freqs, float(scale), _tptr(out, 'out'), out_stride, _stream()),
            'pe_encode')
     return out
 
@@ -347,7 +152,7 @@ def app_input(p, v, normal, n_freqs):
     out = torch.empty(Q, 64, device=p.device, dtype=torch.float32)
     p, v, normal = p.contiguous(), v.contiguous(), normal.contiguous()
     if Q:
-        _check(_lib.psn_app_input(_ptr(p, 'p'), _ptr(v, 'v'), _ptr(normal, 'normal'), Q, int(n_freqs), out.data_ptr(), _stream()),
+        _check(_lib.psn_app_input(_tptr(p, 'p'), _tptr(v, 'v'), _tptr(normal, 'normal'), Q, int(n_freqs), out.data_ptr(), _stream()),
                'app_input')
     return out
 
@@ -356,7 +161,7 @@ def pe_encode_jvp(x, t, n_freqs, out_stride, scale=1.0):
     """J_PE(x) t: tangent t [n,3] -> [n, out_stride]."""
     n = x.shape[0]
     out = torch.empty(n, out_stride, device=x.device, dtype=torch.float32)
-    _check(_lib.psn_pe_encode_jvp(_ptr(x, 'x'), _ptr(t, 't'), n, n_freqs, float(scale), _ptr(out, 'out'), out_stride,
+    _check(_lib.psn_pe_encode_jvp(_tptr(x, 'x'), _tptr(t, 't'), n, n_freqs, float(scale), _tptr(out, 'out'), out_stride,
                                   _stream()), 'pe_encode_jvp')
     return out
 
@@ -367,9 +172,9 @@ def pe_encode_bwd(x, d_out, n_freqs, scale=1.0, add=None):
     n = x.shape[0]
     d_x = torch.empty_like(x)
     assert d_out.shape[1] >= 3 + 6 * n_freqs and (add is None or add.shape[1] >= 3 + 6 * n_freqs)
-    _check(_lib.psn_pe_encode_bwd(_ptr(x, 'x'), _mat_ptr(d_out, 'd_out'), n, n_freqs, float(scale), _ld(d_out),
+    _check(_lib.psn_pe_encode_bwd(_tptr(x, 'x'), _mat_ptr(d_out, 'd_out'), n, n_freqs, float(scale), _ld(d_out),
                                   None if add is None else _mat_ptr(add, 'add'), 0 if add is None else _ld(add),
-                                  _ptr(d_x, 'd_x'), _stream()), 'pe_encode_bwd')
+                                  _tptr(d_x, 'd_x'), _stream()), 'pe_encode_bwd')
     return d_x
 
 
@@ -382,11 +187,11 @@ def sample_points(origin, direction, far, out, hit, near, u0, idx=None, dist=Non
     assert out.shape[1] == c0 + c1 and out.is_contiguous() and (idx is None or idx.dtype == torch.int64)
     if noise is not None:
         assert noise.numel() == n * (c0 + c1)
-    _check(_lib.psn_sample_points(_ptr(origin, 'origin'), _ptr(direction, 'direction'), _ptr(dist, 'dist', True), _ptr(far, 'far'),
+    _check(_lib.psn_sample_points(_tptr(origin, 'origin'), _tptr(direction, 'direction'), _tptr(dist, 'dist', allow_none=True), _tptr(far, 'far'),
                                   None if idx is None else idx.data_ptr(), n, int(bool(hit)), float(near), float(delta),
-                                  _ptr(u0[0], 'u0'), _ptr(u0[1], 'omu0'), c0,
-                                  None if u1 is None else _ptr(u1[0], 'u1'), None if u1 is None else _ptr(u1[1], 'omu1'), c1,
-                                  _ptr(noise, 'noise', True), _ptr(out, 'out'), _stream()), 'sample_points')
+                                  _tptr(u0[0], 'u0'), _tptr(u0[1], 'omu0'), c0,
+                                  None if u1 is None else _tptr(u1[0], 'u1'), None if u1 is None else _tptr(u1[1], 'omu1'), c1,
+                                  _tptr(noise, 'noise', allow_none=True), _tptr(out, 'out'), _stream()), 'sample_points')
     return out
 
 
@@ -400,19 +205,16 @@ def sample_points_flagged(origin, direction, dist, far, flags, out, near, delta,
     assert flags.dtype == torch.bool and flags.is_cuda and flags.is_contiguous() and flags.numel() == n
     if noise is not None:
         assert noise.numel() == n * (c0 + c1)
-    _check(_lib.psn_sample_points_flagged(_ptr(origin, 'origin'), _ptr(direction, 'direction'), _ptr(dist, 'dist'), _ptr(far, 'far'),
-                                          flags.data_ptr(), n, float(near), float(delta), _ptr(u0[0], 'u0'), _ptr(u0[1], 'omu0'), c0,
-                                          None if u1 is None else _ptr(u1[0], 'u1'), None if u1 is None else _ptr(u1[1], 'omu1'), c1,
-                                          _ptr(u_miss[0], 'um'), _ptr(u_miss[1], 'omum'), _ptr(noise, 'noise', True), _ptr(out, 'out'),
+    _check(_lib.psn_sample_points_flagged(_tptr(origin, 'origin'), _tptr(direction, 'direction'), _tptr(dist, 'dist'), _tptr(far, 'far'),
+                                          flags.data_ptr(), n, float(near), float(delta), _tptr(u0[0], 'u0'), _tptr(u0[1], 'omu0'), c0,
+                                          None if u1 is None else _tptr(u1[0], 'u1'), None if u1 is None else _tptr(u1[1], 'omu1'), c1,
+                                          _tptr(u_miss[0], 'um'), _tptr(u_miss[1], 'omum'), _tptr(noise, 'noise', allow_none=True), _tptr(out, 'out'),
                                           _stream()), 'sample_points_flagged')
     return out
 
 
 # --------------------------------------------------------------------------- GEMM
 _ws_cache = {}
-
-
-SCATTER_MAX_ITEMS = 16
 
 
 def copy2d_group(pairs):
@@ -560,7 +362,7 @@ def gather_rows(specs, dense_grads, idx, n_pixels, n_surf, inv=None):
         for i in range(n):
             (B, C, _), g, e = specs[c0 + i], dense_grads[c0 + i], arr[i]
             assert g.is_contiguous() and g.shape == (B, n_pixels, C)
-            e.rows, e.dense, e.B, e.C = out[c0 + i].data_ptr(), _ptr(g, 'dense_grad'), B, C
+            e.rows, e.dense, e.B, e.C = out[c0 + i].data_ptr(), _tptr(g, 'dense_grad'), B, C
         assert idx.dtype == torch.int64 and idx.is_contiguous()
         if inv is not None:
             assert inv.dtype == torch.int32 and inv.is_contiguous() and inv.numel() == n_pixels
@@ -573,9 +375,9 @@ def gather_rows(specs, dense_grads, idx, n_pixels, n_surf, inv=None):
 
 def secant_step(occ, tau, d_pred, d_low, d_high, f_low, f_high, origin, direction, p_mid):
     """One regula-falsi iteration in place (csrc/sample.hip); occ=None: initial step."""
-    _check(_lib.psn_secant_step(_ptr(occ, 'occ', True), float(tau), _ptr(d_pred, 'd_pred'), _ptr(d_low, 'd_low'),
-                                _ptr(d_high, 'd_high'), _ptr(f_low, 'f_low'), _ptr(f_high, 'f_high'),
-                                _ptr(origin, 'origin', True), _ptr(direction, 'direction', True), _ptr(p_mid, 'p_mid', True),
+    _check(_lib.psn_secant_step(_tptr(occ, 'occ', allow_none=True), float(tau), _tptr(d_pred, 'd_pred'), _tptr(d_low, 'd_low'),
+                                _tptr(d_high, 'd_high'), _tptr(f_low, 'f_low'), _tptr(f_high, 'f_high'),
+                                _tptr(origin, 'origin', allow_none=True), _tptr(direction, 'direction', allow_none=True), _tptr(p_mid, 'p_mid', allow_none=True),
                                 d_pred.numel(), _stream()), 'secant_step')
 
 
@@ -584,18 +386,9 @@ def first_crossing(occ, far, u, omu, near, tau):
     N, M = occ.shape
     bracket = torch.empty(4, N, device=occ.device, dtype=torch.float32)
     flags = torch.empty(N, device=occ.device, dtype=torch.int32)
-    _check(_lib.psn_first_crossing(_ptr(occ, 'occ'), _ptr(far, 'far'), _ptr(u, 'u'), _ptr(omu, 'omu'), float(near), float(tau),
+    _check(_lib.psn_first_crossing(_tptr(occ, 'occ'), _tptr(far, 'far'), _tptr(u, 'u'), _tptr(omu, 'omu'), float(near), float(tau),
                                    N, M, bracket.data_ptr(), flags.data_ptr(), _stream()), 'first_crossing')
     return bracket, flags
-
-
-def _fp(t):
-    return None if t is None else _ptr(t, 'loss tensor')
-
-
-def _bp(t):
-    assert t.is_cuda and t.dtype == torch.bool and t.is_contiguous()
-    return t.data_ptr()
 
 
 def stage2_loss_fwd(rgb, rgb_gt, alb, alb_j, wgt, wgt_j, vis, vis_gt, nrm, nrm_gt, nrm_j, mask_a, mask_b, l2, inv_denom, weight,
@@ -604,12 +397,14 @@ def stage2_loss_fwd(rgb, rgb_gt, alb, alb_j, wgt, wgt_j, vis, vis_gt, nrm, nrm_g
     N = mask_a.numel()
     out = torch.empty(7, device=mask_a.device, dtype=torch.float32)
     partial = workspace(2048 * 6, mask_a.device)
-    _check(_lib.psn_stage2_loss_fwd(_fp(rgb), _fp(rgb_gt), 0 if rgb is None else rgb.shape[0], _fp(alb), _fp(alb_j), _fp(wgt), _fp(wgt_j),
-                                    0 if wgt is None else wgt.shape[-1], _fp(vis), _fp(vis_gt), 0 if vis is None else vis.shape[0],
-                                    _fp(nrm), _fp(nrm_gt), _fp(nrm_j), _bp(mask_a), _bp(mask_b), N, int(l2),
+    f = lambda t: _tptr(t, 'loss tensor', allow_none=True)
+    b = lambda t: _tptr(t, 'mask', torch.bool)
+    _check(_lib.psn_stage2_loss_fwd(f(rgb), f(rgb_gt), 0 if rgb is None else rgb.shape[0], f(alb), f(alb_j), f(wgt), f(wgt_j),
+                                    0 if wgt is None else wgt.shape[-1], f(vis), f(vis_gt), 0 if vis is None else vis.shape[0],
+                                    f(nrm), f(nrm_gt), f(nrm_j), b(mask_a), b(mask_b), N, int(l2),
                                     ctypes.cast((ctypes.c_float * 6)(*[float(x) for x in inv_denom]), ctypes.c_void_p),
                                     ctypes.cast((ctypes.c_float * 6)(*[float(x) for x in weight]), ctypes.c_void_p),
-                                    _ptr(count_dev, 'count_dev', True), partial.data_ptr(), out.data_ptr(), _stream()), 'stage2_loss_fwd')
+                                    _tptr(count_dev, 'count_dev', allow_none=True), partial.data_ptr(), out.data_ptr(), _stream()), 'stage2_loss_fwd')
     return out
 
 
@@ -629,12 +424,14 @@ def stage2_loss_bwd(g_total, rgb, rgb_gt, k_rgb, alb, alb_j, k_alb, wgt, wgt_j, 
         if nrm_j is not None:
             d['nrm_j'] = new(nrm_j)
     g = lambda k: None if k not in d else d[k].data_ptr()
-    _check(_lib.psn_stage2_loss_bwd(_ptr(g_total, 'g_total'), _fp(rgb), _fp(rgb_gt), 0 if rgb is None else rgb.shape[0], float(k_rgb), g('rgb'),
-                                    _fp(alb), _fp(alb_j), float(k_alb), g('alb'), g('alb_j'), _fp(wgt), _fp(wgt_j),
-                                    0 if wgt is None else wgt.shape[-1], float(k_wgt), g('wgt'), g('wgt_j'), _fp(vis), _fp(vis_gt),
-                                    0 if vis is None else vis.shape[0], float(k_vis), g('vis'), _fp(nrm), _fp(nrm_gt), _fp(nrm_j),
-                                    float(k_nrm), float(k_nrmj), g('nrm'), g('nrm_j'), _bp(mask_a), _bp(mask_b), N, int(l2),
-                                    _ptr(count_dev, 'count_dev', True), _stream()), 'stage2_loss_bwd')
+    f = lambda t: _tptr(t, 'loss tensor', allow_none=True)
+    b = lambda t: _tptr(t, 'mask', torch.bool)
+    _check(_lib.psn_stage2_loss_bwd(_tptr(g_total, 'g_total'), f(rgb), f(rgb_gt), 0 if rgb is None else rgb.shape[0], float(k_rgb), g('rgb'),
+                                    f(alb), f(alb_j), float(k_alb), g('alb'), g('alb_j'), f(wgt), f(wgt_j),
+                                    0 if wgt is None else wgt.shape[-1], float(k_wgt), g('wgt'), g('wgt_j'), f(vis), f(vis_gt),
+                                    0 if vis is None else vis.shape[0], float(k_vis), g('vis'), f(nrm), f(nrm_gt), f(nrm_j),
+                                    float(k_nrm), float(k_nrmj), g('nrm'), g('nrm_j'), b(mask_a), b(mask_b), N, int(l2),
+                                    _tptr(count_dev, 'count_dev', allow_none=True), _stream()), 'stage2_loss_bwd')
     return d
 
 
@@ -644,7 +441,7 @@ def pair_sums(x, V, Ns):
     sx = torch.empty(Ns, C, device=x.device, dtype=torch.float32)
     part = torch.empty(2048, V, C, device=x.device, dtype=torch.float32)
     n_chunks = ctypes.c_int(0)
-    _check(_lib.psn_pair_sums(_ptr(x, 'x'), V, Ns, C, sx.data_ptr(), part.data_ptr(), ctypes.byref(n_chunks), _stream()), 'pair_sums')
+    _check(_lib.psn_pair_sums(_tptr(x, 'x'), V, Ns, C, sx.data_ptr(), part.data_ptr(), ctypes.byref(n_chunks), _stream()), 'pair_sums')
     return sx, part[:n_chunks.value].sum(0)
 
 
@@ -654,7 +451,7 @@ def pair_sums_group(xs, V, Ns, pe_l, n_pe, want_bias):
     (psn_pair_sums_group)."""
     C = xs[0].shape[1]
     dev = xs[0].device
-    assert 1 <= len(xs) <= 4 and all(x.shape == (V * Ns, C) and x.is_contiguous() for x in xs) and pe_l.stride(1) == 1 and pe_l.shape[0] == V
+    assert 1 <= len(xs) <= PAIR_GROUP_MAX and all(x.shape == (V * Ns, C) and x.is_contiguous() for x in xs) and pe_l.stride(1) == 1 and pe_l.shape[0] == V
     ws = workspace(int(_lib.psn_pair_sums_group_workspace(len(xs), V, Ns, C)), dev)
     arr = (PsnPairSumsItem * len(xs))()
     out = []
@@ -662,9 +459,9 @@ def pair_sums_group(xs, V, Ns, pe_l, n_pe, want_bias):
         sx = torch.empty(Ns, C, device=dev, dtype=torch.float32)
         dWl = torch.empty(C, 64, device=dev, dtype=torch.float32)  # (columns >= n_pe are never read)
         b = torch.empty(C, device=dev, dtype=torch.float32) if wb else None
-        e.x, e.sx, e.dWl, e.bias = _ptr(x, 'x'), sx.data_ptr(), dWl.data_ptr(), None if b is None else b.data_ptr()
+        e.x, e.sx, e.dWl, e.bias = _tptr(x, 'x'), sx.data_ptr(), dWl.data_ptr(), None if b is None else b.data_ptr()
         out.append((sx, dWl, b))
-    _check(_lib.psn_pair_sums_group(len(xs), ctypes.addressof(arr), V, Ns, C, _ptr(pe_l, 'pe_l'), pe_l.stride(0), int(n_pe), 64,
+    _check(_lib.psn_pair_sums_group(len(xs), ctypes.addressof(arr), V, Ns, C, _tptr(pe_l, 'pe_l'), pe_l.stride(0), int(n_pe), 64,
                                     ws.data_ptr(), _stream()), 'pair_sums_group')
     return out
 
@@ -676,7 +473,7 @@ def row_adam(items, idx, step_sizes_dev=None):
     arr = (PsnRowAdamItem * len(items))()
     for e, (p, g, m, v, b1, b2, eps, ss) in zip(arr, items):
         p2 = p.view(p.shape[0], -1)
-        e.param, e.grad, e.exp_avg, e.exp_avg_sq = _ptr(p, 'param'), _ptr(g, 'grad'), _ptr(m, 'exp_avg'), _ptr(v, 'exp_avg_sq')
+        e.param, e.grad, e.exp_avg, e.exp_avg_sq = _tptr(p, 'param'), _tptr(g, 'grad'), _tptr(m, 'exp_avg'), _tptr(v, 'exp_avg_sq')
         e.rows, e.cols, e.one_minus_beta1, e.one_minus_beta2, e.eps, e.step_size = p2.shape[0], p2.shape[1], 1 - b1, 1 - b2, eps, ss
     assert idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()
     if step_sizes_dev is not None:
@@ -691,14 +488,14 @@ def normalize_rows_fwd(x, eps=1e-12):
     """F.normalize(x, dim=-1) for [n, 3] rows in one launch."""
     assert x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()
     y = torch.empty_like(x)
-    _check(_lib.psn_normalize_rows_fwd(_ptr(x, 'x'), x.shape[0], float(eps), y.data_ptr(), _stream()), 'normalize_rows_fwd')
+    _check(_lib.psn_normalize_rows_fwd(_tptr(x, 'x'), x.shape[0], float(eps), y.data_ptr(), _stream()), 'normalize_rows_fwd')
     return y
 
 
 def normalize_rows_bwd(x, g, eps=1e-12):
     assert x.shape == g.shape and x.shape[1] == 3 and x.is_contiguous() and g.is_contiguous()
     dx = torch.empty_like(x)
-    _check(_lib.psn_normalize_rows_bwd(_ptr(x, 'x'), _ptr(g, 'g'), x.shape[0], float(eps), dx.data_ptr(), _stream()), 'normalize_rows_bwd')
+    _check(_lib.psn_normalize_rows_bwd(_tptr(x, 'x'), _tptr(g, 'g'), x.shape[0], float(eps), dx.data_ptr(), _stream()), 'normalize_rows_bwd')
     return dx
 
 
@@ -711,7 +508,7 @@ def light_rows_fwd(dir_table, int_table, idx, eps=1e-12):
     if int_table is not None:
         assert int_table.shape == (dir_table.shape[0], 1) and int_table.is_contiguous()
         it = torch.empty(L, 1, device=dir_table.device, dtype=torch.float32)
-    _check(_lib.psn_light_rows_fwd(_ptr(dir_table, 'dir_table'), _ptr(int_table, 'int_table', True), _iptr(idx, 'idx'), L, float(eps),
+    _check(_lib.psn_light_rows_fwd(_tptr(dir_table, 'dir_table'), _tptr(int_table, 'int_table', allow_none=True), _tptr(idx, 'idx', torch.int64), L, float(eps),
                                    d.data_ptr(), None if it is None else it.data_ptr(), _stream()), 'light_rows_fwd')
     return d, it
 
@@ -723,8 +520,9 @@ def light_rows_bwd(dir_table, idx, g_dir, g_int, eps=1e-12):
     di = torch.empty(n, 1, device=dir_table.device, dtype=torch.float32) if g_int is not None else None
     for t in (g_dir, g_int):
         assert t is None or t.is_contiguous()
-    _check(_lib.psn_light_rows_bwd(_ptr(dir_table, 'dir_table'), _iptr(idx, 'idx'), idx.shape[0], n, float(eps), _ptr(g_dir, 'g_dir', True),
-                                   _ptr(g_int, 'g_int', True), None if dd is None else dd.data_ptr(), None if di is None else di.data_ptr(),
+    _check(_lib.psn_light_rows_bwd(_tptr(dir_table, 'dir_table'), _tptr(idx, 'idx', torch.int64), idx.shape[0], n, float(eps),
+                                   _tptr(g_dir, 'g_dir', allow_none=True),
+                                   _tptr(g_int, 'g_int', allow_none=True), None if dd is None else dd.data_ptr(), None if di is None else di.data_ptr(),
                                    _stream()), 'light_rows_bwd')
     return dd, di
 
@@ -735,7 +533,8 @@ def camera_rays(uv, pose, intrinsics, idx=None, scale=1.0):
     assert pose.shape == (1, 4, 4) and intrinsics.shape[0] == 1 and intrinsics.shape[1:] == (4, 4) and pose.is_contiguous() and intrinsics.is_contiguous()
     n = uv.shape[1] if idx is None else idx.shape[0]
     out = torch.empty(n, 3, device=uv.device, dtype=torch.float32)
-    _check(_lib.psn_camera_rays(_ptr(uv, 'uv'), _ptr(pose, 'pose'), _ptr(intrinsics, 'intrinsics'), _iptr(idx, 'idx', True), n, float(scale),
+    _check(_lib.psn_camera_rays(_tptr(uv, 'uv'), _tptr(pose, 'pose'), _tptr(intrinsics, 'intrinsics'),
+                                _tptr(idx, 'idx', torch.int64, allow_none=True), n, float(scale),
                                 out.data_ptr(), _stream()), 'camera_rays')
     return out
 
@@ -752,16 +551,18 @@ def stage1_loss_fwd(rgb, rgb_gt, diff, hit, normal, normal_gt, norm_mask, acc, m
     sums = torch.empty(8, device=dev, dtype=torch.float32)
     terms = torch.empty(5, device=dev, dtype=torch.float32) if finish else None
     partial = workspace(_lib.psn_stage1_loss_partial_floats(), dev)
-    _check(_lib.psn_stage1_loss_fwd(_ptr(rgb, 'rgb'), _ptr(rgb_gt, 'rgb_gt'), _fp(diff), _bp(hit) if hit is not None else None, _fp(normal),
-                                    _fp(normal_gt), _bp(norm_mask) if norm_mask is not None else None, _fp(acc), _fp(mask_gt),
-                                    _bp(mask_valid) if mask_valid is not None else None, N, int(n_rays), _w4(weights), partial.data_ptr(),
+    f = lambda t: _tptr(t, 'loss tensor', allow_none=True)
+    b = lambda t: _tptr(t, 'mask', torch.bool, allow_none=True)
+    _check(_lib.psn_stage1_loss_fwd(_tptr(rgb, 'rgb'), _tptr(rgb_gt, 'rgb_gt'), f(diff), b(hit), f(normal),
+                                    f(normal_gt), b(norm_mask), f(acc), f(mask_gt),
+                                    b(mask_valid), N, int(n_rays), _w4(weights), partial.data_ptr(),
                                     sums.data_ptr(), None if terms is None else terms.data_ptr(), _stream()), 'stage1_loss_fwd')
     return sums, terms
 
 
 def stage1_loss_terms(sums, n_rays, weights, has_grad, has_norm, has_mask):
     terms = torch.empty(5, device=sums.device, dtype=torch.float32)
-    _check(_lib.psn_stage1_loss_terms(_ptr(sums, 'sums'), int(n_rays), _w4(weights), int(has_grad), int(has_norm), int(has_mask),
+    _check(_lib.psn_stage1_loss_terms(_tptr(sums, 'sums'), int(n_rays), _w4(weights), int(has_grad), int(has_norm), int(has_mask),
                                       terms.data_ptr(), _stream()), 'stage1_loss_terms')
     return terms
 
@@ -776,9 +577,10 @@ def stage1_loss_bwd(g_loss, sums, rgb, rgb_gt, hit, normal, normal_gt, norm_mask
     if 'normal' in need: d['normal'] = torch.empty_like(normal)
     if 'acc' in need: d['acc'] = torch.empty_like(acc)
     g = lambda k: None if k not in d else d[k].data_ptr()
-    b = lambda t: None if t is None else _bp(t)
-    _check(_lib.psn_stage1_loss_bwd(_ptr(g_loss, 'g_loss'), _ptr(sums, 'sums'), _ptr(rgb, 'rgb'), _ptr(rgb_gt, 'rgb_gt'), b(hit), _fp(normal),
-                                    _fp(normal_gt), b(norm_mask), _fp(acc), _fp(mask_gt), b(mask_valid), N, int(n_rays), _w4(weights),
+    b = lambda t: _tptr(t, 'mask', torch.bool, allow_none=True)
+    f = lambda t: _tptr(t, 'loss tensor', allow_none=True)
+    _check(_lib.psn_stage1_loss_bwd(_tptr(g_loss, 'g_loss'), _tptr(sums, 'sums'), _tptr(rgb, 'rgb'), _tptr(rgb_gt, 'rgb_gt'), b(hit), f(normal),
+                                    f(normal_gt), b(norm_mask), f(acc), f(mask_gt), b(mask_valid), N, int(n_rays), _w4(weights),
                                     g('rgb'), g('diff'), g('normal'), g('acc'), _stream()), 'stage1_loss_bwd')
     return d
 
@@ -789,7 +591,7 @@ def surface_normals_fwd(g, hit, eps=1e-5):
     assert g.shape == (2 * N, 3)
     norm_pred = torch.empty(N, 3, device=g.device, dtype=torch.float32)
     diff = torch.empty(N, device=g.device, dtype=torch.float32)
-    _check(_lib.psn_surface_normals_fwd(_ptr(g, 'g'), _bp(hit), N, float(eps), norm_pred.data_ptr(), diff.data_ptr(), _stream()),
+    _check(_lib.psn_surface_normals_fwd(_tptr(g, 'g'), _tptr(hit, 'hit', torch.bool), N, float(eps), norm_pred.data_ptr(), diff.data_ptr(), _stream()),
            'surface_normals_fwd')
     return norm_pred, diff
 
@@ -797,8 +599,8 @@ def surface_normals_fwd(g, hit, eps=1e-5):
 def surface_normals_bwd(g, hit, d_norm_pred, d_diff, eps=1e-5):
     N = hit.shape[0]
     dg = torch.empty_like(g)
-    _check(_lib.psn_surface_normals_bwd(_ptr(g, 'g'), _bp(hit), N, float(eps), _ptr(d_norm_pred, 'd_norm_pred', True),
-                                        _ptr(d_diff, 'd_diff', True), dg.data_ptr(), _stream()), 'surface_normals_bwd')
+    _check(_lib.psn_surface_normals_bwd(_tptr(g, 'g'), _tptr(hit, 'hit', torch.bool), N, float(eps), _tptr(d_norm_pred, 'd_norm_pred', allow_none=True),
+                                        _tptr(d_diff, 'd_diff', allow_none=True), dg.data_ptr(), _stream()), 'surface_normals_bwd')
     return dg
 
 
@@ -810,7 +612,7 @@ def stage1_rays(pix, camera_mat, world_mat, radius):
     n = pix.shape[0]
     cam, rays = (torch.empty(n, 3, device=pix.device, dtype=torch.float32) for _ in range(2))
     far = torch.empty(n, device=pix.device, dtype=torch.float32)
-    _check(_lib.psn_stage1_rays(_ptr(pix, 'pix'), _ptr(camera_mat, 'camera_mat'), camera_mat.shape[0], _ptr(world_mat, 'world_mat'),
+    _check(_lib.psn_stage1_rays(_tptr(pix, 'pix'), _tptr(camera_mat, 'camera_mat'), camera_mat.shape[0], _tptr(world_mat, 'world_mat'),
                                 float(radius ** 2), n, cam.data_ptr(), rays.data_ptr(), far.data_ptr(), _stream()), 'stage1_rays')
     return cam, rays, far
 
@@ -825,7 +627,7 @@ def surface_points(d_pred, flags, cam, rays, want_d=False):
     obj = torch.empty(n, device=dev, dtype=torch.bool)
     pts = torch.empty(n, 3, device=dev, dtype=torch.float32)
     d_i = torch.empty(n, device=dev, dtype=torch.float32) if want_d else None
-    _check(_lib.psn_surface_points(_ptr(d_pred, 'd_pred'), flags.data_ptr(), _ptr(cam, 'cam'), _ptr(rays, 'rays'), n,
+    _check(_lib.psn_surface_points(_tptr(d_pred, 'd_pred'), flags.data_ptr(), _tptr(cam, 'cam'), _tptr(rays, 'rays'), n,
                                    None if d_i is None else d_i.data_ptr(), dists.data_ptr(), obj.data_ptr(), pts.data_ptr(),
                                    _stream()), 'surface_points')
     return (dists, obj, pts, d_i) if want_d else (dists, obj, pts)
@@ -847,9 +649,10 @@ def stage1_targets(pix, img, mask=None, mask_valid=None, normal=None, norm_mask=
     valid = torch.empty(n, device=dev, dtype=torch.bool)
     nmask = torch.empty(n, device=dev, dtype=torch.bool) if norm_mask is not None else None
     ngt = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_normal else None
-    _check(_lib.psn_stage1_targets(_ptr(pix, 'pix'), n, h, w, _ptr(img, 'img'), _ptr(mask, 'mask', True), _ptr(mask_valid, 'mask_valid', True),
-                                   _ptr(normal, 'normal', True) if want_normal else None, _ptr(norm_mask, 'norm_mask', True),
-                                   _ptr(world_mat, 'world_mat', True) if want_normal else None, int(cos_thresh is not None),
+    _check(_lib.psn_stage1_targets(_tptr(pix, 'pix'), n, h, w, _tptr(img, 'img'), _tptr(mask, 'mask', allow_none=True),
+                                   _tptr(mask_valid, 'mask_valid', allow_none=True),
+                                   _tptr(normal, 'normal', allow_none=True) if want_normal else None, _tptr(norm_mask, 'norm_mask', allow_none=True),
+                                   _tptr(world_mat, 'world_mat', allow_none=True) if want_normal else None, int(cos_thresh is not None),
                                    float(cos_thresh if cos_thresh is not None else 0.0), rgb.data_ptr(), mask_gt.data_ptr(), valid.data_ptr(),
                                    None if ngt is None else ngt.data_ptr(), None if nmask is None else nmask.data_ptr(), _stream()),
            'stage1_targets')
@@ -888,8 +691,8 @@ def shadow_points(surf, ldir, n_steps, lnear, lfar, u, omu, box):
     pts = torch.empty(max(cap, 1), 3, device=surf.device, dtype=torch.float32)
     rows = torch.empty(max(cap, 1), device=surf.device, dtype=torch.int64)
     counter = torch.zeros(1, device=surf.device, dtype=torch.int64)
-    _check(_lib.psn_shadow_points(_ptr(surf, 'surf'), _ptr(ldir, 'ldir'), Ns, L, int(n_steps), float(lnear), float(lfar),
-                                  _ptr(u, 'u'), _ptr(omu, 'omu'), float(box), pts.data_ptr(), rows.data_ptr(), counter.data_ptr(),
+    _check(_lib.psn_shadow_points(_tptr(surf, 'surf'), _tptr(ldir, 'ldir'), Ns, L, int(n_steps), float(lnear), float(lfar),
+                                  _tptr(u, 'u'), _tptr(omu, 'omu'), float(box), pts.data_ptr(), rows.data_ptr(), counter.data_ptr(),
                                   _stream()), 'shadow_points')
     return pts, rows, counter
 
@@ -912,14 +715,14 @@ def mlp_infer_pe(desc, packed_w, packed_b, points, pe_octaves, pe_scale, out=Non
         assert out_rows is None or (out_rows.dtype == torch.int64 and out_rows.is_cuda and out_rows.is_contiguous() and out_rows.numel() >= Q)
         # (no flop count for the profile: how many rows were evaluated is known to the device only)
         with _Prof('mlp_infer', Q, None):
-            _check(_lib.psn_mlp_infer_pe_indirect(ctypes.byref(desc), _ptr(packed_w, 'packed_w'), _ptr(packed_b, 'packed_b'),
-                                                  _ptr(points, 'points'), Q, n_rows_dev.data_ptr(),
+            _check(_lib.psn_mlp_infer_pe_indirect(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'),
+                                                  _tptr(points, 'points'), Q, n_rows_dev.data_ptr(),
                                                   None if out_rows is None else out_rows.data_ptr(), int(pe_octaves), float(pe_scale),
                                                   out.data_ptr(), _stream()), 'mlp_infer_pe_indirect')
         return out
     assert out_rows is None
     with _Prof('mlp_infer', Q, None if macs_per_row is None else 2.0 * macs_per_row * Q):
-        _check(_lib.psn_mlp_infer_pe(ctypes.byref(desc), _ptr(packed_w, 'packed_w'), _ptr(packed_b, 'packed_b'), _ptr(points, 'points'),
+        _check(_lib.psn_mlp_infer_pe(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'), _tptr(points, 'points'),
                                      Q, int(pe_octaves), float(pe_scale), out.data_ptr(), _stream()), 'mlp_infer_pe')
     return out
 
@@ -939,8 +742,8 @@ def march_sweep(desc, packed_w, packed_b, origin, direction, far, u, omu, near, 
     # counter and the flops of ONE block, so that the reader prices evaluated work, not the N x M rows of the dense sweep
     count = torch.zeros(1, device=origin.device, dtype=torch.int64) if PROFILE_EVENTS is not None else None
     with _Prof('march_sweep', Q, None if (macs_per_row is None or count is None) else (count, 2.0 * macs_per_row * 64)):
-        _check(_lib.psn_march_sweep(ctypes.byref(desc), _ptr(packed_w, 'packed_w'), _ptr(packed_b, 'packed_b'), _ptr(origin, 'origin'),
-                                    _ptr(direction, 'direction'), _ptr(far, 'far'), _ptr(u, 'u'), _ptr(omu, 'omu'), float(near), N,
+        _check(_lib.psn_march_sweep(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'), _tptr(origin, 'origin'),
+                                    _tptr(direction, 'direction'), _tptr(far, 'far'), _tptr(u, 'u'), _tptr(omu, 'omu'), float(near), N,
                                     int(n_steps), float(tau), int(pe_octaves), float(pe_scale),
                                     None if skip is None else skip.data_ptr(), None if count is None else count.data_ptr(),
                                     occ.data_ptr(), _stream()), 'march_sweep')
@@ -953,8 +756,8 @@ def root_find(desc, packed_w, packed_b, origin, direction, bracket, tau, n_iter,
     assert bracket.shape == (4, N)
     out = torch.empty(N, device=origin.device, dtype=torch.float32)
     with _Prof('root_find', N, None):
-        _check(_lib.psn_root_find(ctypes.byref(desc), _ptr(packed_w, 'packed_w'), _ptr(packed_b, 'packed_b'), _ptr(origin, 'origin'),
-                                  _ptr(direction, 'direction'), _ptr(bracket, 'bracket'), N, float(tau), int(n_iter), int(pe_octaves),
+        _check(_lib.psn_root_find(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'), _tptr(origin, 'origin'),
+                                  _tptr(direction, 'direction'), _tptr(bracket, 'bracket'), N, float(tau), int(n_iter), int(pe_octaves),
                                   float(pe_scale), out.data_ptr(), _stream()), 'root_find')
     return out
 
@@ -994,10 +797,8 @@ def _ld(t):
 
 
 def _mat_ptr(t, name):
-    """2-D row-major view (may be a column slice of a wider buffer: ld = stride(0))."""
-    if not t.is_cuda or t.dtype != torch.float32:
-        raise RuntimeError('%s: must be a float32 HIP tensor' % name)
-    return t.data_ptr()
+    """2-D row-major view (may be a column slice of a wider buffer: ld = stride(0), so no contiguity rule)."""
+    return _tptr(t, name, contiguous=False)
 
 
 def gemm(A, B, trans_a=False, trans_b=False, bias=None, epi=EPI_NONE, aux_in=None, out=None, aux_out=None,
@@ -1020,13 +821,13 @@ def gemm(A, B, trans_a=False, trans_b=False, bias=None, epi=EPI_NONE, aux_in=Non
     if split_k > 1:
         ws = workspace(split_k * M * (N + 1), A.device)
     _check(_lib.psn_gemm(int(trans_a), int(trans_b), M, N, K, _mat_ptr(A, 'A'), _ld(A), _mat_ptr(B, 'B'), _ld(B),
-                         _mat_ptr(out, 'out'), _ld(out), _ptr(bias, 'bias', True), epi,
+                         _mat_ptr(out, 'out'), _ld(out), _tptr(bias, 'bias', allow_none=True), epi,
                          None if aux_in is None else _mat_ptr(aux_in, 'aux_in'), 0 if aux_in is None else _ld(aux_in),
                          None if aux_in2 is None else _mat_ptr(aux_in2, 'aux_in2'),
                          0 if aux_in2 is None else _ld(aux_in2),
                          None if aux_out is None else _mat_ptr(aux_out, 'aux_out'),
                          0 if aux_out is None else _ld(aux_out), split_k,
-                         None if ws is None else ws.data_ptr(), _ptr(colsum_a, 'colsum_a', True), _stream()), 'gemm')
+                         None if ws is None else ws.data_ptr(), _tptr(colsum_a, 'colsum_a', allow_none=True), _stream()), 'gemm')
     return out
 
 
@@ -1101,8 +902,8 @@ def gemm_tn_grouped(items, split_k=None, x3=None):
         # nothing else filled; there a chunk may shrink to 128 rows (8 k-steps): 340 workgroups, the reduction is 20 MB
         min_rows = 512 if K >= 16384 else 128
         split_k = int(max(1, min(want, K // min_rows if K >= min_rows else 1, 256)))
-    for c0 in range(0, len(items), MAX_GROUP):
-        chunk = items[c0:c0 + MAX_GROUP]
+    for c0 in range(0, len(items), GEMM_TN_MAX_ITEMS):
+        chunk = items[c0:c0 + GEMM_TN_MAX_ITEMS]
         arr = (PsnGemmTnItem * len(chunk))()
         need = 0
         keep = []
@@ -1195,9 +996,6 @@ def mlp_pack_layer(W, n_mt, k_tiles, dst, transpose=False):
                                    _stream()), 'mlp_pack_layer')
 
 
-PACK_MAX_ITEMS = 24
-
-
 def mlp_pack_layers(plan):
     """plan: list of (W, transpose, n_mt, k_tiles, dst[, format = W_F32]) like mlp_pack_layer, packed in ONE launch per 24 blocks."""
     for c0 in range(0, len(plan), PACK_MAX_ITEMS):
@@ -1268,7 +1066,7 @@ def mlp_infer(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod
         if lst is None:
             return None
         assert len(lst) == n, '%s: expected %d entries' % (name, n)
-        return (ctypes.c_void_p * n)(*[None if t is None else (_bits_ptr(t, name) if t.dtype == torch.int64 else _ptr(t, name)) for t in lst])
+        return (ctypes.c_void_p * n)(*[None if t is None else (_bits_ptr(t, name) if t.dtype == torch.int64 else _tptr(t, name)) for t in lst])
 
     mask_arr = ptr_array(mask, desc.n_layers, 'mask')
     aux2_arr = ptr_array(aux2, desc.n_layers, 'aux2')
@@ -1276,7 +1074,7 @@ def mlp_infer(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod
     save_arr = None
     if save is not None:
         assert len(save) == n_hidden
-        save_arr = (ctypes.c_void_p * len(save))(*[None if t is None else _ptr(t, 'save') for t in save])
+        save_arr = (ctypes.c_void_p * len(save))(*[None if t is None else _tptr(t, 'save') for t in save])
     # 'mlp_infer' = the lean engine, 'mlp_chain' = the chain engine (same dispatch rule as psn_mlp_infer)
     chain = act_init is not None or rank_init is not None or tiles_arr is not None or mask is not None or aux2 is not None or save2 is not None or any(
         desc.layers[l].act > ACT_SOFTPLUS100 for l in range(desc.n_layers))
@@ -1289,10 +1087,10 @@ def mlp_infer(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod
         bits_arr = (ctypes.c_void_p * n_hidden)(*[None if t is None else _bits_ptr(t, 'save_bits') for t in save_bits])
         cnt, period = live if live is not None else (None, 0)
         with _Prof('mlp_infer', n_rows, None if macs_per_row is None else 2.0 * macs_per_row * n_rows):
-            _check(_lib.psn_mlp_infer_bits(ctypes.byref(desc), _ptr(packed_w, 'packed_w'), _ptr(packed_b, 'packed_b'),
-                                           _ptr(tab_a, 'tab_a', True), a_div, a_mod, _ptr(tab_b, 'tab_b', True), b_div, b_mod,
-                                           _ptr(init_a, 'init_a', True), _ptr(init_b, 'init_b', True), save_arr, bits_arr, save_row0, n_rows,
-                                           _ptr(out, 'out', True), None if cnt is None else cnt.data_ptr(), int(period), _stream()), 'mlp_infer_bits')
+            _check(_lib.psn_mlp_infer_bits(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'),
+                                           _tptr(tab_a, 'tab_a', allow_none=True), a_div, a_mod, _tptr(tab_b, 'tab_b', allow_none=True), b_div, b_mod,
+                                           _tptr(init_a, 'init_a', allow_none=True), _tptr(init_b, 'init_b', allow_none=True), save_arr, bits_arr, save_row0, n_rows,
+                                           _tptr(out, 'out', allow_none=True), None if cnt is None else cnt.data_ptr(), int(period), _stream()), 'mlp_infer_bits')
         return out
     if live is not None:
         cnt, period = live
@@ -1300,24 +1098,21 @@ def mlp_infer(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod
             raise RuntimeError('mlp_infer: a device-side live count is for plain forward launches (no chain operands)')
         assert cnt.is_cuda and cnt.dtype == torch.float32 and cnt.numel() == 1 and int(period) >= 1
         with _Prof('mlp_infer', n_rows, None if macs_per_row is None else 2.0 * macs_per_row * n_rows):
-            _check(_lib.psn_mlp_infer_padded(ctypes.byref(desc), _ptr(packed_w, 'packed_w'), _ptr(packed_b, 'packed_b'),
-                                             _ptr(tab_a, 'tab_a', True), a_div, a_mod, _ptr(tab_b, 'tab_b', True), b_div, b_mod,
-                                             _ptr(init_a, 'init_a', True), _ptr(init_b, 'init_b', True), save_arr, save_row0, n_rows,
-                                             _ptr(out, 'out', True), cnt.data_ptr(), int(period), _stream()), 'mlp_infer_padded')
+            _check(_lib.psn_mlp_infer_padded(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'),
+                                             _tptr(tab_a, 'tab_a', allow_none=True), a_div, a_mod, _tptr(tab_b, 'tab_b', allow_none=True), b_div, b_mod,
+                                             _tptr(init_a, 'init_a', allow_none=True), _tptr(init_b, 'init_b', allow_none=True), save_arr, save_row0, n_rows,
+                                             _tptr(out, 'out', allow_none=True), cnt.data_ptr(), int(period), _stream()), 'mlp_infer_padded')
         return out
     with _Prof('mlp_chain' if chain else 'mlp_infer', n_rows, None if macs_per_row is None else 2.0 * macs_per_row * n_rows):
-        _check(_lib.psn_mlp_infer(ctypes.byref(desc), _ptr(packed_w, 'packed_w'), _ptr(packed_b, 'packed_b'),
-                                  _ptr(tab_a, 'tab_a', True), a_div, a_mod, _ptr(tab_b, 'tab_b', True), b_div, b_mod,
-                                  _ptr(init_a, 'init_a', True), _ptr(init_b, 'init_b', True), save_arr, save_row0, mask_arr,
-                                  aux2_arr, save2_arr, _ptr(act_init, 'act_init', True), int(ai_rows), _ptr(rk_coef, 'rk_coef', True),
-                                  _ptr(rk_basis, 'rk_basis', True), rk_k, tiles_arr, n_rows, _ptr(out, 'out', True), _stream()), 'mlp_infer')
+        _check(_lib.psn_mlp_infer(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'),
+                                  _tptr(tab_a, 'tab_a', allow_none=True), a_div, a_mod, _tptr(tab_b, 'tab_b', allow_none=True), b_div, b_mod,
+                                  _tptr(init_a, 'init_a', allow_none=True), _tptr(init_b, 'init_b', allow_none=True), save_arr, save_row0, mask_arr,
+                                  aux2_arr, save2_arr, _tptr(act_init, 'act_init', allow_none=True), int(ai_rows), _tptr(rk_coef, 'rk_coef', allow_none=True),
+                                  _tptr(rk_basis, 'rk_basis', allow_none=True), rk_k, tiles_arr, n_rows, _tptr(out, 'out', allow_none=True), _stream()), 'mlp_infer')
     return out
 
 
 # --------------------------------------------------------------------------- weight normalisation
-WN_MAX_ITEMS = 16
-
-
 def weight_norm_fwd(vs, gs, scales):
     """[v_l * (g_l / |v_l|_row) * scale_l] for all layers in one launch (<= 16 per launch)."""
     out = [torch.empty_like(v) for v in vs]
@@ -1328,7 +1123,7 @@ def weight_norm_fwd(vs, gs, scales):
             v, g = vs[c0 + i], gs[c0 + i]
             assert v.dim() == 2 and g.numel() == v.shape[0]
             e = arr[i]
-            e.v, e.g, e.w = _ptr(v, 'weight_v'), _ptr(g, 'weight_g'), out[c0 + i].data_ptr()
+            e.v, e.g, e.w = _tptr(v, 'weight_v'), _tptr(g, 'weight_g'), out[c0 + i].data_ptr()
             e.rows, e.cols, e.scale = v.shape[0], v.shape[1], float(scales[c0 + i])
         _check(_lib.psn_weight_norm_fwd(n, ctypes.addressof(arr), _stream()), 'weight_norm_fwd')
     return out
@@ -1344,7 +1139,7 @@ def weight_norm_bwd(vs, gs, scales, dws):
         for i in range(n):
             v, g = vs[c0 + i], gs[c0 + i]
             e = arr[i]
-            e.v, e.g, e.dw = _ptr(v, 'weight_v'), _ptr(g, 'weight_g'), _ptr(dws[c0 + i], 'dw')
+            e.v, e.g, e.dw = _tptr(v, 'weight_v'), _tptr(g, 'weight_g'), _tptr(dws[c0 + i], 'dw')
             e.dv, e.dg = dvs[c0 + i].data_ptr(), dgs[c0 + i].data_ptr()
             e.rows, e.cols, e.scale = v.shape[0], v.shape[1], float(scales[c0 + i])
         _check(_lib.psn_weight_norm_bwd(n, ctypes.addressof(arr), _stream()), 'weight_norm_bwd')
@@ -1362,11 +1157,10 @@ def mlp_pack_bf16(W, permuted, n_ot, ks0, n_ks, dst):
 
 
 def _bf16_table(t, name):
-    if t is None:
-        return None
-    if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 64):
+    """Device pointer of an input table of the bf16 engine ([n, 64] bfloat16, contiguous), or None."""
+    if t is not None and (t.dim() != 2 or t.shape[1] != 64):
         raise RuntimeError('%s: must be a contiguous [n, 64] bfloat16 HIP tensor' % name)
-    return t.data_ptr()
+    return _tptr(t, name, torch.bfloat16, allow_none=True)
 
 
 def mlp_infer_bf16(desc, packed_w, final_bias, tab_a, a_div, a_mod, tab_b, b_div, b_mod, n_rows, out=None):
@@ -1375,9 +1169,9 @@ def mlp_infer_bf16(desc, packed_w, final_bias, tab_a, a_div, a_mod, tab_b, b_div
     assert packed_w.dtype == torch.bfloat16 and packed_w.is_cuda and packed_w.is_contiguous()
     assert final_bias.numel() == 32
     with _Prof('mlp_infer_bf16', n_rows):
-        _check(_lib.psn_mlp_infer_bf16(ctypes.byref(desc), packed_w.data_ptr(), _ptr(final_bias, 'final_bias'),
+        _check(_lib.psn_mlp_infer_bf16(ctypes.byref(desc), packed_w.data_ptr(), _tptr(final_bias, 'final_bias'),
                                        _bf16_table(tab_a, 'tab_a'), a_div, a_mod, _bf16_table(tab_b, 'tab_b'), b_div, b_mod,
-                                       n_rows, _ptr(out, 'out'), _stream()), 'mlp_infer_bf16')
+                                       n_rows, _tptr(out, 'out'), _stream()), 'mlp_infer_bf16')
     return out
 
 
@@ -1404,9 +1198,9 @@ def mlp_infer_bf16_grouped(desc, packed_w, final_bias, tab_a, group_bias, n_grou
         raise RuntimeError('group_bias: must be a contiguous [n_groups * %d, 4096] bfloat16 HIP tensor' % n_in)
     assert out.numel() == n_groups * rows * desc.n_out
     with _Prof('mlp_infer_bf16', n_groups * rows):
-        _check(_lib.psn_mlp_infer_bf16_grouped(ctypes.byref(desc), packed_w.data_ptr(), _ptr(final_bias, 'final_bias'),
+        _check(_lib.psn_mlp_infer_bf16_grouped(ctypes.byref(desc), packed_w.data_ptr(), _tptr(final_bias, 'final_bias'),
                                                _bf16_table(tab_a, 'tab_a'), rows, group_bias.data_ptr(), n_groups,
-                                               _ptr(out, 'out'), _stream()), 'mlp_infer_bf16_grouped')
+                                               _tptr(out, 'out'), _stream()), 'mlp_infer_bf16_grouped')
     return out
 
 
@@ -1446,8 +1240,8 @@ def mlp_infer_x3_grouped(desc, packed_w, bias_steps, final_bias, U, V, out=None,
     assert U.shape[1] == V.shape[1] == n_in * 256 and bias_steps.numel() == desc.n_hidden * 4096
     assert final_bias.numel() == 32 and out.numel() == n_groups * rows * desc.n_out
     with _Prof('mlp_infer_x3', n_groups * rows, None if macs_per_row is None else 2.0 * macs_per_row * n_groups * rows):
-        _check(_lib.psn_mlp_infer_x3_grouped(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _ptr(final_bias, 'final_bias'),
-                                             _ptr(U, 'U'), rows, _ptr(V, 'V'), n_groups, _ptr(out, 'out'), _stream()), 'mlp_infer_x3_grouped')
+        _check(_lib.psn_mlp_infer_x3_grouped(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _tptr(final_bias, 'final_bias'),
+                                             _tptr(U, 'U'), rows, _tptr(V, 'V'), n_groups, _tptr(out, 'out'), _stream()), 'mlp_infer_x3_grouped')
     return out
 
 
@@ -1469,10 +1263,10 @@ def mlp_infer_x3_occ(desc, packed_w, bias_steps, final_bias, points, pe_octaves,
     if out_rows is not None:
         assert out_rows.is_cuda and out_rows.dtype == torch.int64 and out_rows.is_contiguous() and out_rows.numel() >= Q
     with _Prof('mlp_infer_x3_occ', Q, None if macs_per_row is None else 2.0 * macs_per_row * Q):
-        _check(_lib.psn_mlp_infer_x3_occ(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _ptr(final_bias, 'final_bias'),
-                                         _ptr(points, 'points'), Q, None if n_rows_dev is None else n_rows_dev.data_ptr(),
+        _check(_lib.psn_mlp_infer_x3_occ(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _tptr(final_bias, 'final_bias'),
+                                         _tptr(points, 'points'), Q, None if n_rows_dev is None else n_rows_dev.data_ptr(),
                                          None if out_rows is None else out_rows.data_ptr(), int(pe_octaves), float(pe_scale),
-                                         int(skip_layer), int(pe_first), _ptr(out, 'out'), _stream()), 'mlp_infer_x3_occ')
+                                         int(skip_layer), int(pe_first), _tptr(out, 'out'), _stream()), 'mlp_infer_x3_occ')
     return out
 
 
@@ -1481,12 +1275,12 @@ def sg_shade_fwd(light_dir, view, normal, albedo, weights, lobe, light_int, ligh
     L, Ns, nb = light_dir.shape[0], view.shape[0], lobe.shape[0]
     rgb = torch.empty(L * Ns, 3, device=view.device, dtype=torch.float32)
     spec = torch.empty(L * Ns, 3 if specular_rgb else 1, device=view.device, dtype=torch.float32)
-    _check(_lib.psn_sg_shade_fwd(_ptr(light_dir, 'light_dir'), _ptr(view, 'view'), _ptr(normal, 'normal'),
-                                 _ptr(albedo, 'albedo'), _ptr(weights, 'weights'), _ptr(lobe, 'lobe'),
-                                 _ptr(light_int, 'light_int', True),
+    _check(_lib.psn_sg_shade_fwd(_tptr(light_dir, 'light_dir'), _tptr(view, 'view'), _tptr(normal, 'normal'),
+                                 _tptr(albedo, 'albedo'), _tptr(weights, 'weights'), _tptr(lobe, 'lobe'),
+                                 _tptr(light_int, 'light_int', allow_none=True),
                                  1 if light_int is None or light_int.dim() == 1 else light_int.shape[1],
-                                 float(light_int_scalar), _ptr(vis, 'vis', True),
-                                 L, Ns, nb, int(bool(specular_rgb)), _ptr(rgb, 'rgb'), _ptr(spec, 'spec'), _stream()),
+                                 float(light_int_scalar), _tptr(vis, 'vis', allow_none=True),
+                                 L, Ns, nb, int(bool(specular_rgb)), _tptr(rgb, 'rgb'), _tptr(spec, 'spec'), _stream()),
            'sg_shade_fwd')
     return rgb, spec
 
@@ -1502,12 +1296,12 @@ def sg_shade_bwd(light_dir, view, normal, albedo, weights, lobe, light_int, ligh
     d_ldir = torch.empty(L, 3, device=dev)
     d_lint = torch.empty(L, device=dev) if light_int is not None else None
     ws = workspace(((Ns + 63) // 64) * L * 4, dev)
-    _check(_lib.psn_sg_shade_bwd(_ptr(light_dir, 'light_dir'), _ptr(view, 'view'), _ptr(normal, 'normal'),
-                                 _ptr(albedo, 'albedo'), _ptr(weights, 'weights'), _ptr(lobe, 'lobe'),
-                                 _ptr(light_int, 'light_int', True), float(light_int_scalar), _ptr(vis, 'vis', True),
-                                 L, Ns, nb, int(bool(specular_rgb)), _ptr(g_rgb, 'g_rgb'), _ptr(g_spec, 'g_spec', True),
-                                 _ptr(d_albedo, 'd_albedo'), _ptr(d_weights, 'd_weights'), _ptr(d_normal, 'd_normal'),
-                                 _ptr(d_vis, 'd_vis', True), _ptr(d_ldir, 'd_ldir'), _ptr(d_lint, 'd_lint', True),
+    _check(_lib.psn_sg_shade_bwd(_tptr(light_dir, 'light_dir'), _tptr(view, 'view'), _tptr(normal, 'normal'),
+                                 _tptr(albedo, 'albedo'), _tptr(weights, 'weights'), _tptr(lobe, 'lobe'),
+                                 _tptr(light_int, 'light_int', allow_none=True), float(light_int_scalar), _tptr(vis, 'vis', allow_none=True),
+                                 L, Ns, nb, int(bool(specular_rgb)), _tptr(g_rgb, 'g_rgb'), _tptr(g_spec, 'g_spec', allow_none=True),
+                                 _tptr(d_albedo, 'd_albedo'), _tptr(d_weights, 'd_weights'), _tptr(d_normal, 'd_normal'),
+                                 _tptr(d_vis, 'd_vis', allow_none=True), _tptr(d_ldir, 'd_ldir'), _tptr(d_lint, 'd_lint', allow_none=True),
                                  ws.data_ptr(), _stream()), 'sg_shade_bwd')
     return d_albedo, d_weights, d_normal, d_vis, d_ldir, d_lint
 
@@ -1516,9 +1310,9 @@ def sg_shade_bwd(light_dir, view, normal, albedo, weights, lobe, light_int, ligh
 def mf_shade_fwd(light_dir, view, normal, albedo, rough, light_int, light_int_scalar, f0, vis):
     L, Ns = light_dir.shape[0], view.shape[0]
     rgb = torch.empty(L * Ns, 3, device=view.device, dtype=torch.float32)
-    _check(_lib.psn_mf_shade_fwd(_ptr(light_dir, 'light_dir'), _ptr(view, 'view'), _ptr(normal, 'normal'),
-                                 _ptr(albedo, 'albedo'), _ptr(rough, 'rough'), _ptr(light_int, 'light_int', True),
-                                 float(light_int_scalar), float(f0), _ptr(vis, 'vis', True), L, Ns, _ptr(rgb, 'rgb'),
+    _check(_lib.psn_mf_shade_fwd(_tptr(light_dir, 'light_dir'), _tptr(view, 'view'), _tptr(normal, 'normal'),
+                                 _tptr(albedo, 'albedo'), _tptr(rough, 'rough'), _tptr(light_int, 'light_int', allow_none=True),
+                                 float(light_int_scalar), float(f0), _tptr(vis, 'vis', allow_none=True), L, Ns, _tptr(rgb, 'rgb'),
                                  _stream()), 'mf_shade_fwd')
     return rgb
 
@@ -1533,11 +1327,11 @@ def mf_shade_bwd(light_dir, view, normal, albedo, rough, light_int, light_int_sc
     d_ldir = torch.empty(L, 3, device=dev)
     d_lint = torch.empty(L, device=dev) if light_int is not None else None
     ws = workspace(((Ns + 63) // 64) * L * 4, dev)
-    _check(_lib.psn_mf_shade_bwd(_ptr(light_dir, 'light_dir'), _ptr(view, 'view'), _ptr(normal, 'normal'),
-                                 _ptr(albedo, 'albedo'), _ptr(rough, 'rough'), _ptr(light_int, 'light_int', True),
-                                 float(light_int_scalar), float(f0), _ptr(vis, 'vis', True), L, Ns, _ptr(g_rgb, 'g_rgb'),
-                                 _ptr(d_albedo, 'd_albedo'), _ptr(d_rough, 'd_rough'), _ptr(d_normal, 'd_normal'),
-                                 _ptr(d_vis, 'd_vis', True), _ptr(d_ldir, 'd_ldir'), _ptr(d_lint, 'd_lint', True),
+    _check(_lib.psn_mf_shade_bwd(_tptr(light_dir, 'light_dir'), _tptr(view, 'view'), _tptr(normal, 'normal'),
+                                 _tptr(albedo, 'albedo'), _tptr(rough, 'rough'), _tptr(light_int, 'light_int', allow_none=True),
+                                 float(light_int_scalar), float(f0), _tptr(vis, 'vis', allow_none=True), L, Ns, _tptr(g_rgb, 'g_rgb'),
+                                 _tptr(d_albedo, 'd_albedo'), _tptr(d_rough, 'd_rough'), _tptr(d_normal, 'd_normal'),
+                                 _tptr(d_vis, 'd_vis', allow_none=True), _tptr(d_ldir, 'd_ldir'), _tptr(d_lint, 'd_lint', allow_none=True),
                                  ws.data_ptr(), _stream()), 'mf_shade_bwd')
     return d_albedo, d_rough, d_normal, d_vis, d_ldir, d_lint
 
@@ -1558,8 +1352,8 @@ def march_sweep_x3(desc, packed_w, bias_steps, final_bias, origin, direction, fa
         return occ, skip
     count = torch.zeros(1, device=origin.device, dtype=torch.int64) if PROFILE_EVENTS is not None else None
     with _Prof('march_sweep_x3', N * n_steps, None if (macs_per_row is None or count is None) else (count, 2.0 * macs_per_row * 128)):
-        _check(_lib.psn_march_sweep_x3(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _ptr(final_bias, 'final_bias'),
-                                       _ptr(origin, 'origin'), _ptr(direction, 'direction'), _ptr(far, 'far'), _ptr(u, 'u'), _ptr(omu, 'omu'),
+        _check(_lib.psn_march_sweep_x3(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _tptr(final_bias, 'final_bias'),
+                                       _tptr(origin, 'origin'), _tptr(direction, 'direction'), _tptr(far, 'far'), _tptr(u, 'u'), _tptr(omu, 'omu'),
                                        float(near), N, int(n_steps), float(tau), int(pe_octaves), float(pe_scale), int(skip_layer), int(pe_first),
                                        None if skip is None else skip.data_ptr(), occ.data_ptr(), None if count is None else count.data_ptr(),
                                        _stream()), 'march_sweep_x3')
@@ -1567,16 +1361,6 @@ def march_sweep_x3(desc, packed_w, bias_steps, final_bias, origin, direction, fa
 
 
 # --------------------------------------------------------------------------- stage-1 mesh extraction (csrc/mesh.hip)
-MESH_MAX_RESOLUTION = 1024
-
-
-def _tptr(t, name, dtype):
-    """Device pointer of a contiguous tensor of the given dtype."""
-    if t is None or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError('%s: must be a contiguous %s HIP device tensor' % (name, dtype))
-    return t.data_ptr()
-
-
 def mise_flags(resolution, device):
     """Zeroed flag bytes of a (resolution + 1)^3 grid, padded to whole 4-byte words (psn_mise_collect / psn_mise_refine)."""
     n3 = (resolution + 1) ** 3
@@ -1599,7 +1383,7 @@ def mise_refine(grid, flags, vox, resolution0, depth, threshold, pending):
     res = resolution0 << depth
     assert grid.numel() == (res + 1) ** 3 and flags.numel() == ((res + 1) ** 3 + 3) // 4 * 4 and pending.numel() == 1
     assert vox.numel() == sum((resolution0 << l) ** 3 for l in range(depth))
-    _check(_lib.psn_mise_refine(_ptr(grid, 'grid'), _tptr(flags, 'flags', torch.uint8), _tptr(vox, 'vox', torch.uint8), int(resolution0),
+    _check(_lib.psn_mise_refine(_tptr(grid, 'grid'), _tptr(flags, 'flags', torch.uint8), _tptr(vox, 'vox', torch.uint8), int(resolution0),
                                 int(depth), float(threshold), _tptr(pending, 'pending', torch.int64), _stream()), 'mise_refine')
 
 
@@ -1608,7 +1392,7 @@ def grid_ffill(grid):
     n = grid.shape[0]
     assert grid.shape == (n, n, n)
     with _Prof('grid_ffill', 8 * grid.numel()):
-        _check(_lib.psn_grid_ffill(_ptr(grid, 'grid'), n, _stream()), 'grid_ffill')
+        _check(_lib.psn_grid_ffill(_tptr(grid, 'grid'), n, _stream()), 'grid_ffill')
     return grid
 
 
@@ -1626,7 +1410,7 @@ def marching_cubes(grid, threshold, box_size=0.0):
     code = torch.empty(n_cells, dtype=torch.uint8, device=dev)
     blk = torch.empty(2, nb, dtype=torch.int32, device=dev)
     with _Prof('mc_count', 4 * grid.numel()):
-        _check(_lib.psn_mc_count(_ptr(grid, 'grid'), n, float(threshold), code.data_ptr(), blk[0].data_ptr(), blk[1].data_ptr(), _stream()),
+        _check(_lib.psn_mc_count(_tptr(grid, 'grid'), n, float(threshold), code.data_ptr(), blk[0].data_ptr(), blk[1].data_ptr(), _stream()),
                'mc_count')
     incl = torch.cumsum(blk, dim=1, dtype=torch.int64)
     base = (incl - blk).contiguous()
@@ -1637,15 +1421,12 @@ def marching_cubes(grid, threshold, box_size=0.0):
         return vertices, faces
     v_off = torch.empty(n_cells, dtype=torch.int32, device=dev)
     with _Prof('mc_emit', 24 * n_v + 24 * n_f):
-        _check(_lib.psn_mc_emit(_ptr(grid, 'grid'), n, float(threshold), code.data_ptr(), base[0].data_ptr(), base[1].data_ptr(), n_v, n_f,
+        _check(_lib.psn_mc_emit(_tptr(grid, 'grid'), n, float(threshold), code.data_ptr(), base[0].data_ptr(), base[1].data_ptr(), n_v, n_f,
                                 float(box_size), v_off.data_ptr(), vertices.data_ptr(), faces.data_ptr(), _stream()), 'mc_emit')
     return vertices, faces
 
 
 # --------------------------------------------------------------------------- point-to-mesh distance (csrc/meshdist.hip)
-TRI_GRID_MAX_CELLS_PER_AXIS = 256
-
-
 def tri_grid(lo, hi, cell, n, max_span):
     """The host-side descriptor of the triangle grid (PsnTriGrid): bounding box, cell edge, cells per axis, oversize limit."""
     g = PsnTriGrid()
@@ -1713,23 +1494,15 @@ def closest_point(grid, vertices, faces, cell_start, lst, over_list, n_over, poi
 
 
 # --------------------------------------------------------------------------- image evaluation (csrc/imgmetrics.hip)
-IMG_TYPES = {torch.float32: 0, torch.uint8: 1}   # PSN_IMG_F32 / PSN_IMG_U8
-IMG_MIN_EXTENT = 11
-IMG_WS_SCALE_SUMS, IMG_WS_METRICS, IMG_WS_NORMAL_MAE = range(3)
+IMG_TYPES = {torch.float32: IMG_F32, torch.uint8: IMG_U8}  # noqa: F821
 
 
 def _img_pair(what, pred, gt, mask):
     """The checks every image entry shares -> (image_type, mask pointer or None, mask batch, B, H, W)."""
     for name, t in (('pred', pred), ('gt', gt)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError('%s: %s must be a HIP device tensor (the product path has no CPU fallback; host arrays: '
-                               'psnerf_amd.imgmetrics.host_*)' % (what, name))
-        if t.dtype not in IMG_TYPES:
-            raise RuntimeError('%s: %s must be float32 or uint8, got %s' % (what, name, t.dtype))
+        _tptr(t, '%s: %s' % (what, name), tuple(IMG_TYPES))
         if t.dim() != 4 or t.shape[3] != 3:
             raise RuntimeError('%s: %s [B, H, W, 3] expected, got %s' % (what, name, tuple(t.shape)))
-        if not t.is_contiguous():
-            raise RuntimeError('%s: %s must be contiguous' % (what, name))
     if pred.dtype != gt.dtype:
         raise RuntimeError('%s: pred is %s and gt is %s (one dtype for the pair)' % (what, pred.dtype, gt.dtype))
     if pred.shape != gt.shape:
@@ -1746,17 +1519,14 @@ def _mask_ptr(what, mask, B, tail, device):
     """mask: None, or a uint8 / bool device tensor [B or 1, *tail] -> (pointer or None, mask batch)."""
     if mask is None:
         return None, 1
-    if not torch.is_tensor(mask) or not mask.is_cuda:
-        raise RuntimeError('%s: mask must be a HIP device tensor' % what)
-    if mask.dtype not in (torch.uint8, torch.bool):
-        raise RuntimeError('%s: mask must be uint8 or bool, got %s' % (what, mask.dtype))
+    ptr = _tptr(mask, '%s: mask' % what, (torch.uint8, torch.bool))
     if mask.dim() != 1 + len(tail) or tuple(mask.shape[1:]) != tuple(tail):
         raise RuntimeError('%s: mask [B or 1, %s] expected, got %s' % (what, ', '.join(str(x) for x in tail), tuple(mask.shape)))
     if mask.shape[0] not in (1, B):
         raise RuntimeError('%s: mask batch %d is neither 1 nor B = %d' % (what, mask.shape[0], B))
-    if not mask.is_contiguous() or mask.device != device:
-        raise RuntimeError('%s: mask must be contiguous and on the images\' device' % what)
-    return mask.data_ptr(), int(mask.shape[0])
+    if mask.device != device:
+        raise RuntimeError('%s: mask must be on the images\' device' % what)
+    return ptr, int(mask.shape[0])
 
 
 def _img_partial(which, B, H, W, device):
@@ -1783,16 +1553,16 @@ def img_metrics(pred, gt, mask, scale=None, full=False):
     None -> dict(ssim [B], psnr [B], sums [B, 7], partial, map [B, H, W, 3] or None), all float64 device tensors."""
     ty, mp, mb, B, H, W = _img_pair('img_metrics', pred, gt, mask)
     dev = pred.device
-    if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda and scale.dtype == torch.float64 and scale.is_contiguous()
-                                  and tuple(scale.shape) == (B,)):
-        raise RuntimeError('img_metrics: scale must be a contiguous float64 HIP device tensor [%d]' % B)
+    sp = _tptr(scale, 'img_metrics: scale', torch.float64, allow_none=True)
+    if scale is not None and tuple(scale.shape) != (B,):
+        raise RuntimeError('img_metrics: scale [%d] expected, got %s' % (B, tuple(scale.shape)))
     partial = _img_partial(IMG_WS_METRICS, B, H, W, dev)
     sums = torch.empty(B, 7, dtype=torch.float64, device=dev)
     ssim = torch.empty(B, dtype=torch.float64, device=dev)
     psnr = torch.empty(B, dtype=torch.float64, device=dev)
     smap = torch.empty(B, H, W, 3, dtype=torch.float64, device=dev) if full else None
     with _Prof('img_metrics', B * H * W * (2 * 3 * pred.element_size() + 1)):   # the compulsory bytes: two images and one mask
-        _check(_lib.psn_img_metrics(pred.data_ptr(), gt.data_ptr(), ty, mp, mb, None if scale is None else scale.data_ptr(), B, H, W,
+        _check(_lib.psn_img_metrics(pred.data_ptr(), gt.data_ptr(), ty, mp, mb, sp, B, H, W,
                                     partial.data_ptr(), sums.data_ptr(), ssim.data_ptr(), psnr.data_ptr(),
                                     None if smap is None else smap.data_ptr(), _stream()), 'img_metrics')
     return {'ssim': ssim, 'psnr': psnr, 'sums': sums, 'partial': partial, 'map': smap}
@@ -1802,13 +1572,9 @@ def normal_mae(pred, gt, mask, normalize=True, full=False):
     """psn_normal_mae: pred / gt float32 [B, N, 3] normal maps, mask [B or 1, N] (uint8 / bool) or None -> (sums float64 [B, 2] =
     masked sum of the angular errors in degrees, masked pixels; partial rows; per-pixel errors [B, N] or None)."""
     for name, t in (('pred', pred), ('gt', gt)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError('normal_mae: %s must be a HIP device tensor (the product path has no CPU fallback; host arrays: '
-                               'psnerf_amd.metrics.MAE)' % name)
-        if t.dtype != torch.float32:
-            raise RuntimeError('normal_mae: %s must be float32, got %s' % (name, t.dtype))
-        if t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous():
-            raise RuntimeError('normal_mae: %s: contiguous [B, N, 3] expected, got %s' % (name, tuple(t.shape)))
+        _tptr(t, 'normal_mae: %s' % name)
+        if t.dim() != 3 or t.shape[2] != 3:
+            raise RuntimeError('normal_mae: %s: [B, N, 3] expected, got %s' % (name, tuple(t.shape)))
     if pred.shape != gt.shape:
         raise RuntimeError('normal_mae: shape mismatch, pred %s and gt %s' % (tuple(pred.shape), tuple(gt.shape)))
     B, N = int(pred.shape[0]), int(pred.shape[1])

@@ -95,7 +95,7 @@ class RowSparseAdam(torch.optim.Optimizer):
             if self.graph_scalars is not None:
                 self._graph_plan = []
             return None
-        if len(items) > 4:
+        if len(items) > hip.ROW_ADAM_MAX:
             return False
         for p, state, *_ in items:
             state['step'] = int(state['step']) + 1

@@ -10,10 +10,34 @@ import torch
 from tests.helpers import ROOT
 
 
+HEADER = os.path.join(ROOT, 'include', 'psnerf_hip.h')
+
+
+def _header_text():
+    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+
+
 def _declared_symbols():
-    text = open(os.path.join(ROOT, 'include', 'psnerf_hip.h')).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(psn_[a-z0-9_]+)\s*\(', text)))
+    return sorted(set(re.findall(r'\b(psn_[a-z0-9_]+)\s*\(', _header_text())))
+
+
+def _declared_parameter_counts():
+    """name -> number of parameters, by a scan of its own (no psnerf_amd.cabi): the text between the parentheses that follow the
+    name, cut at its top-level commas; ``(void)`` is none."""
+    text, counts = _header_text(), {}
+    for m in re.finditer(r'\b(psn_[a-z0-9_]+)\s*\(', text):
+        depth, commas, i = 1, 0, m.end()
+        while depth:
+            depth += {'(': 1, ')': -1}.get(text[i], 0)
+            commas += depth == 1 and text[i] == ','
+            i += 1
+        inner = text[m.end():i - 1].strip()
+        counts[m.group(1)] = 0 if inner in ('', 'void') else commas + 1
+    return counts
+
+
+def _declared_structs():
+    return re.findall(r'\}\s*(Psn\w+)\s*;', _header_text())
 
 
 def test_library_exports_every_declared_symbol():
@@ -26,6 +50,10 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), 'include/psnerf_hip.h declares %s but the library does not export it' % name
     from psnerf_amd import hip
     assert sorted(hip.SIGNATURES.keys()) == declared, 'ctypes binding and header disagree'
+    counts = _declared_parameter_counts()
+    assert sorted(counts) == declared and max(counts.values()) >= 30 and counts['psn_version'] == 0 and counts['psn_composite_fwd'] == 9
+    for name, (_, argtypes) in hip.SIGNATURES.items():
+        assert len(argtypes) == counts[name], '%s: %d argtypes, the header declares %d parameters' % (name, len(argtypes), counts[name])
     assert hip.version() >= 100
 
 
@@ -38,11 +66,11 @@ def test_struct_layout_matches_header():
     assert ctypes.sizeof(hip.PsnWnItem) == 64                  # 6 pointers + 2 x int32 + float, padded to 8
 
 
-@pytest.mark.parametrize('struct', ['PsnViewBatch', 'PsnMlpDesc', 'PsnPackItem'])
+@pytest.mark.parametrize('struct', _declared_structs())
 def test_struct_layout_against_the_c_compiler(tmp_path, struct):
     """PsnViewBatch (the descriptor of the on-device batch assembly, psn_view_batch) mixes pointers, int64 and int fields, and
-    PsnMlpDesc / PsnPackItem grew a field in round 5 (the weight-stage format): the ctypes mirrors are compared with what gcc
-    makes of include/psnerf_hip.h, field by field."""
+    PsnMlpDesc / PsnPackItem grew a field in round 5 (the weight-stage format): the ctypes classes that psnerf_amd.cabi derives
+    from include/psnerf_hip.h are compared with what gcc makes of it, field by field, for EVERY struct the header declares."""
     import os, subprocess
     from psnerf_amd import hip
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,6 +84,75 @@ def test_struct_layout_against_the_c_compiler(tmp_path, struct):
     got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
     assert got[0] == ctypes.sizeof(cls)
     assert got[1:] == [getattr(cls, f).offset for f in fields]
+
+
+def test_every_struct_of_the_header_is_checked():
+    from psnerf_amd import cabi, hip
+    names = _declared_structs()
+    assert len(names) >= 14 and sorted(names) == sorted(cabi.parse(HEADER)[1])
+    assert all(issubclass(getattr(hip, n), ctypes.Structure) for n in names)
+
+
+def test_constants_against_the_c_compiler(tmp_path):
+    """Every PSN_* #define and enumerator as gcc evaluates it == what psnerf_amd.cabi reads from the header == the name without its
+    prefix in psnerf_amd.hip.  The name list is this test's own scan: every PSN_ word of the comment-stripped header."""
+    import subprocess
+    from psnerf_amd import cabi, hip
+    names = sorted(set(re.findall(r'\bPSN_[A-Z0-9_]+\b', _header_text())))
+    assert len(names) >= 50 and {'PSN_E_ARG', 'PSN_EPI_MUL_AUX_RAW', 'PSN_ACT_SOFTPLUS_BWD_A', 'PSN_W_BF16X2', 'PSN_TRI_GRID_MAX_FACES',
+                                 'PSN_GEMM_TN_MAX_ITEMS', 'PSN_IMG_WS_NORMAL_MAE'} <= set(names)
+    src = tmp_path / 'constants.c'
+    src.write_text('#include <stdio.h>\n#include "psnerf_hip.h"\nint main(void) {\n'
+                   + ''.join('  printf("%s %%lld\\n", (long long)(%s));\n' % (n, n) for n in names) + '  return 0;\n}\n')
+    exe = tmp_path / 'constants'
+    subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)])
+    by_gcc = {k: int(v) for k, v in (line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    assert by_gcc == cabi.parse(HEADER)[0]
+    for name, value in by_gcc.items():
+        assert getattr(hip, name[len('PSN_'):]) == value, name
+    assert hip.MAX_LAYERS == by_gcc['PSN_MLP_MAX_LAYERS'] and by_gcc['PSN_E_ARG'] == -1 and by_gcc['PSN_TRI_GRID_MAX_FACES'] == 2 ** 31 - 2
+    assert hip.IMG_TYPES == {torch.float32: by_gcc['PSN_IMG_F32'], torch.uint8: by_gcc['PSN_IMG_U8']}
+
+
+GOOD_HEADER = '''#define PSN_N 3
+enum { PSN_A, PSN_B = 5, PSN_C };
+typedef struct { const float* p; int64_t a, b[PSN_N + 1]; } PsnItem;
+const char* psn_name(void);
+int psn_call(const PsnItem* items, float* const* out, long long n,
+             double x, void* stream);
+'''
+
+
+@pytest.mark.parametrize('bad, word', [
+    ('int psn_f(size_t n);', 'unknown type'),                                  # a type the table does not know
+    ('typedef struct { wchar_t c; } PsnT;', 'unknown type'),
+    ('int psn_f(const PsnMissing* p);', 'unknown type'),                       # ... also behind a pointer
+    ('int psn_f(int a, int (*callback)(int));', 'outside the grammar'),        # prototypes split in ways the grammar does not cover
+    ('int psn_f(int a,\n#ifdef PSN_MORE\n          int b,\n#endif\n          int c);', 'outside the grammar'),
+    ('PSN_API(int) psn_f(int a);', 'outside the grammar'),
+    ('int psn_f(int);', 'outside the grammar'),
+    ('int psn_f(int a) { return a; }', 'outside the grammar'),
+    ('typedef struct { int flags : 3; int rest; } PsnT;', 'outside the grammar'),   # a bit-field
+    ('typedef struct { int n[PSN_UNKNOWN]; } PsnT;', 'integer constant expression'),
+    ('#define PSN_X 1.5', 'integer constant expression'),
+    ('#pragma pack(1)', 'outside the grammar'),
+])
+def test_header_parser_refuses_what_it_does_not_cover(tmp_path, bad, word):
+    """psnerf_amd.cabi never guesses and never skips: the accepted style parses to exact types, anything else raises an error that
+    names the header line."""
+    from psnerf_amd import cabi
+    path = tmp_path / 'h.h'
+    path.write_text(GOOD_HEADER)
+    constants, structs, functions = cabi.parse(str(path))
+    assert constants == {'PSN_N': 3, 'PSN_A': 0, 'PSN_B': 5, 'PSN_C': 6}
+    item = structs['PsnItem']
+    assert [f[0] for f in item._fields_] == ['p', 'a', 'b'] and ctypes.sizeof(item) == 8 + 8 + 4 * 8 and item.b.offset == 16
+    assert functions == {'psn_name': (ctypes.c_char_p, []),
+                         'psn_call': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_double, ctypes.c_void_p])}
+    path.write_text(GOOD_HEADER + bad + '\n')
+    with pytest.raises(cabi.HeaderError, match=word) as e:
+        cabi.parse(str(path))
+    assert ('h.h:%d:' % (GOOD_HEADER.count('\n') + 1)) in str(e.value)
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason='CPU-only check')
