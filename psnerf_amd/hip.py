@@ -1275,6 +1275,8 @@ def sg_shade_fwd(light_dir, view, normal, albedo, weights, lobe, light_int, ligh
     L, Ns, nb = light_dir.shape[0], view.shape[0], lobe.shape[0]
     rgb = torch.empty(L * Ns, 3, device=view.device, dtype=torch.float32)
     spec = torch.empty(L * Ns, 3 if specular_rgb else 1, device=view.device, dtype=torch.float32)
+    if Ns == 0:  # no points: nothing to launch (an empty tensor has no device pointer to hand over)
+        return rgb, spec
     _check(_lib.psn_sg_shade_fwd(_tptr(light_dir, 'light_dir'), _tptr(view, 'view'), _tptr(normal, 'normal'),
                                  _tptr(albedo, 'albedo'), _tptr(weights, 'weights'), _tptr(lobe, 'lobe'),
                                  _tptr(light_int, 'light_int', allow_none=True),
@@ -1295,6 +1297,8 @@ def sg_shade_bwd(light_dir, view, normal, albedo, weights, lobe, light_int, ligh
     d_vis = torch.empty(L * Ns, device=dev) if want_vis else None
     d_ldir = torch.empty(L, 3, device=dev)
     d_lint = torch.empty(L, device=dev) if light_int is not None else None
+    if Ns == 0:  # the per-light gradients are sums over no points
+        return d_albedo, d_weights, d_normal, d_vis, torch.zeros_like(d_ldir), None if d_lint is None else torch.zeros_like(d_lint)
     ws = workspace(((Ns + 63) // 64) * L * 4, dev)
     _check(_lib.psn_sg_shade_bwd(_tptr(light_dir, 'light_dir'), _tptr(view, 'view'), _tptr(normal, 'normal'),
                                  _tptr(albedo, 'albedo'), _tptr(weights, 'weights'), _tptr(lobe, 'lobe'),
@@ -1310,6 +1314,8 @@ def sg_shade_bwd(light_dir, view, normal, albedo, weights, lobe, light_int, ligh
 def mf_shade_fwd(light_dir, view, normal, albedo, rough, light_int, light_int_scalar, f0, vis):
     L, Ns = light_dir.shape[0], view.shape[0]
     rgb = torch.empty(L * Ns, 3, device=view.device, dtype=torch.float32)
+    if Ns == 0:
+        return rgb
     _check(_lib.psn_mf_shade_fwd(_tptr(light_dir, 'light_dir'), _tptr(view, 'view'), _tptr(normal, 'normal'),
                                  _tptr(albedo, 'albedo'), _tptr(rough, 'rough'), _tptr(light_int, 'light_int', allow_none=True),
                                  float(light_int_scalar), float(f0), _tptr(vis, 'vis', allow_none=True), L, Ns, _tptr(rgb, 'rgb'),
@@ -1326,6 +1332,8 @@ def mf_shade_bwd(light_dir, view, normal, albedo, rough, light_int, light_int_sc
     d_vis = torch.empty(L * Ns, device=dev) if want_vis else None
     d_ldir = torch.empty(L, 3, device=dev)
     d_lint = torch.empty(L, device=dev) if light_int is not None else None
+    if Ns == 0:
+        return d_albedo, d_rough, d_normal, d_vis, torch.zeros_like(d_ldir), None if d_lint is None else torch.zeros_like(d_lint)
     ws = workspace(((Ns + 63) // 64) * L * 4, dev)
     _check(_lib.psn_mf_shade_bwd(_tptr(light_dir, 'light_dir'), _tptr(view, 'view'), _tptr(normal, 'normal'),
                                  _tptr(albedo, 'albedo'), _tptr(rough, 'rough'), _tptr(light_int, 'light_int', allow_none=True),
