@@ -851,6 +851,43 @@ int psn_closest_point(const PsnTriGrid* grid, const double* vertices, const int6
                       int64_t n_points, double* closest, double* dist, int64_t* tri, long long* n_tests, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Mesh clean-up: connected components of a triangle mesh, per-component statistics and compaction (csrc/meshclean.hip; the numpy
+ * definition is psnerf_amd/meshclean.py:host_*).  The reference has no such step (its only answer to floaters is --clip,
+ * stage1/model/extracting.py:130-132); users of the pipeline take trimesh's split() on the host.
+ *   vertices float64 [V, 3];  faces int64 [F, 3];  0 <= V <= PSN_CC_MAX_VERTICES, 0 <= F <= PSN_CC_MAX_FACES.  Duplicated faces and
+ *   faces with a repeated index are legal.  A face with an index outside 0 .. V - 1 is SKIPPED and PSN_CC_E_INDEX is set in status.
+ *   status  int32 [1] on the device, bits PSN_CC_E_*; the caller reads it with the table and raises.
+ *
+ * psn_cc_label: labels int32 [V], labels[v] = the smallest vertex index reachable from v (two vertices are adjacent when one face
+ *   names both; an unreferenced vertex keeps its own index).  parent int32 [V]: scratch.  status is zeroed here.  One pass of a
+ *   lock-free union-find and a flatten launch; no host read, no rounds; bitwise reproducible.  PSN_CC_E_BOUND: a loop ran into its
+ *   static bound (labels are then not valid).
+ * psn_cc_stats: per component, indexed by its label (all three arrays [V], zeroed here): vertex_count, face_count (a face belongs
+ *   to the component of its first index) and area = the sum of 0.5 |(b - a) x (c - a)| in float64.  Counts are exact; the order of
+ *   the area sum is not defined (within n 2^-53 relative of the exact sum of n faces).  status: bits are added.
+ * psn_cc_flag: face_keep [F] bytes = keep_label[labels[first index]] != 0 (keep_label [V] bytes); vertex_keep [V] bytes (zeroed
+ *   here) = 1 for every vertex a kept face names.
+ * psn_cc_compact: face_pos [F] / vertex_pos [V] int64 = exclusive scans of those flags, n_out_* their totals.  out_vertices
+ *   [n_out_vertices, 3] = the kept vertices in their original order, bits untouched; out_normals likewise from normals [V, 3] of
+ *   normal_bytes = 4 (float) or 8 (double) per component, or null with normal_bytes = 0; out_faces [n_out_faces, 3] = the kept faces in
+ *   their original order with vertex_pos applied.
+ * Errors: PSN_E_ARG for null pointers and sizes out of range; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_CC_MAX_VERTICES 2147483646LL
+#define PSN_CC_MAX_FACES 274877906944LL
+#define PSN_CC_E_INDEX 1
+#define PSN_CC_E_BOUND 2
+int psn_cc_label(const int64_t* faces, int64_t n_faces, int64_t n_vertices, int* parent, int* labels, int* status, void* stream);
+int psn_cc_stats(const double* vertices, const int64_t* faces, int64_t n_faces, int64_t n_vertices, const int* labels,
+                 long long* vertex_count, long long* face_count, double* area, int* status, void* stream);
+int psn_cc_flag(const int64_t* faces, int64_t n_faces, int64_t n_vertices, const int* labels, const unsigned char* keep_label,
+                unsigned char* face_keep, unsigned char* vertex_keep, void* stream);
+int psn_cc_compact(const double* vertices, const void* normals, int normal_bytes, const int64_t* faces, int64_t n_faces,
+                   int64_t n_vertices, const unsigned char* face_keep, const unsigned char* vertex_keep, const int64_t* face_pos,
+                   const int64_t* vertex_pos, int64_t n_out_faces, int64_t n_out_vertices, double* out_vertices, void* out_normals,
+                   int64_t* out_faces, void* stream);
+
+/* ------------------------------------------------------------------------
  * Image evaluation: what the reference's evaluation.py computes per image pair and per view (csrc/imgmetrics.hip; the float64
  * numpy definition is psnerf_amd/imgmetrics.py:host_*).  float64 arithmetic, no floating-point atomics: each call writes one row
  * of partial sums per tile / chunk into ``partial`` (psn_img_workspace doubles; every row written on every call) and a second,

@@ -1501,6 +1501,71 @@ def closest_point(grid, vertices, faces, cell_start, lst, over_list, n_over, poi
     return closest, dist, tri
 
 
+# --------------------------------------------------------------------------- mesh clean-up (csrc/meshclean.hip)
+def cc_label(faces, n_vertices, status):
+    """psn_cc_label: faces int64 [F, 3] -> labels int32 [n_vertices], the smallest vertex index reachable from each vertex.  status
+    (int32 [1] on the device) is set: CC_E_* bits; the caller reads it together with the table (meshclean._device_table)."""
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError('cc_label: faces [F, 3] expected, got %s' % (tuple(faces.shape),))
+    n_v, n_f = int(n_vertices), faces.shape[0]
+    assert status.numel() == 1
+    parent = torch.empty(n_v, dtype=torch.int32, device=faces.device)
+    labels = torch.empty(n_v, dtype=torch.int32, device=faces.device)
+    with _Prof('cc_label', 24 * n_f + 12 * n_v):   # faces read once; parent written, read and the labels written
+        _check(_lib.psn_cc_label(_tptr(faces, 'faces', torch.int64), n_f, n_v, parent.data_ptr(), labels.data_ptr(),
+                                 _tptr(status, 'status', torch.int32), _stream()), 'cc_label')
+    return labels
+
+
+def cc_stats(vertices, faces, labels, status):
+    """psn_cc_stats -> (counts int64 [2, V]: vertices and faces per component, area float64 [V]), indexed by the component's label."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    n_v, n_f = vertices.shape[0], faces.shape[0]
+    assert labels.numel() == n_v and status.numel() == 1
+    counts = torch.empty(2, n_v, dtype=torch.int64, device=vertices.device)
+    area = torch.empty(n_v, dtype=torch.float64, device=vertices.device)
+    with _Prof('cc_stats', 28 * n_v + 96 * n_f):   # labels read, three tables zeroed; per face its indices and three vertices
+        _check(_lib.psn_cc_stats(vp, fp, n_f, n_v, _tptr(labels, 'labels', torch.int32), counts[0].data_ptr(), counts[1].data_ptr(),
+                                 area.data_ptr(), _tptr(status, 'status', torch.int32), _stream()), 'cc_stats')
+    return counts, area
+
+
+def cc_flag(faces, labels, keep_label):
+    """psn_cc_flag: keep_label uint8 [V] (per label) -> (face_keep uint8 [F], vertex_keep uint8 [V])."""
+    n_v, n_f = labels.numel(), faces.shape[0]
+    assert keep_label.numel() == n_v
+    face_keep = torch.empty(n_f, dtype=torch.uint8, device=faces.device)
+    vertex_keep = torch.empty(n_v, dtype=torch.uint8, device=faces.device)
+    with _Prof('cc_flag', 29 * n_f + n_v):
+        _check(_lib.psn_cc_flag(_tptr(faces, 'faces', torch.int64), n_f, n_v, _tptr(labels, 'labels', torch.int32),
+                                _tptr(keep_label, 'keep_label', torch.uint8), face_keep.data_ptr(), vertex_keep.data_ptr(), _stream()), 'cc_flag')
+    return face_keep, vertex_keep
+
+
+def cc_compact(vertices, faces, normals, face_keep, vertex_keep, face_pos, vertex_pos, n_out_faces, n_out_vertices):
+    """psn_cc_compact -> (vertices float64 [n_out_vertices, 3], faces int64 [n_out_faces, 3], normals or None): what the flags keep, in
+    the original order, faces re-indexed.  face_pos / vertex_pos: the int64 exclusive scans of the flags; normals float32 or float64."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    n_v, n_f = vertices.shape[0], faces.shape[0]
+    assert face_keep.numel() == face_pos.numel() == n_f and vertex_keep.numel() == vertex_pos.numel() == n_v
+    dev = vertices.device
+    out_v = torch.empty(int(n_out_vertices), 3, dtype=torch.float64, device=dev)
+    out_f = torch.empty(int(n_out_faces), 3, dtype=torch.int64, device=dev)
+    out_n, nb = None, 0
+    if normals is not None:
+        if tuple(normals.shape) != (n_v, 3):
+            raise RuntimeError('cc_compact: normals [%d, 3] expected, got %s' % (n_v, tuple(normals.shape)))
+        nb = normals.element_size()
+        out_n = torch.empty(int(n_out_vertices), 3, dtype=normals.dtype, device=dev)
+    with _Prof('cc_compact', 9 * n_v + 9 * n_f + (48 + 2 * 3 * nb) * int(n_out_vertices) + 72 * int(n_out_faces)):
+        _check(_lib.psn_cc_compact(vp, None if normals is None else _tptr(normals, 'normals', (torch.float32, torch.float64)), nb, fp, n_f, n_v,
+                                   _tptr(face_keep, 'face_keep', torch.uint8), _tptr(vertex_keep, 'vertex_keep', torch.uint8),
+                                   _tptr(face_pos, 'face_pos', torch.int64), _tptr(vertex_pos, 'vertex_pos', torch.int64), int(n_out_faces),
+                                   int(n_out_vertices), out_v.data_ptr(), None if out_n is None else out_n.data_ptr(), out_f.data_ptr(),
+                                   _stream()), 'cc_compact')
+    return out_v, out_f, out_n
+
+
 # --------------------------------------------------------------------------- image evaluation (csrc/imgmetrics.hip)
 IMG_TYPES = {torch.float32: IMG_F32, torch.uint8: IMG_U8}  # noqa: F821
 

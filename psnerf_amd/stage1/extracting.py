@@ -19,8 +19,17 @@ Semantics (restated from the reference, see the functions for the line numbers):
   (a least fixed point: the order of the tests within a round does not change the final set of evaluated points).
   to_dense: holes take their predecessor's value along x, then y, then z.  Marching cubes runs on the grid padded with -1e6,
   with the case table of csrc/mc_table.h (tools/gen_mc_table.py); vertices are float64.
-Not implemented, and refused loudly: ``refinement_step > 0`` (RMSprop vertex refinement, extracting.py:237-323) and
-``mask_loader`` (needs skimage morphology, extracting.py:326-377).
+Clean-up (not in the reference; opt-in): ``Extractor3D(..., keep_components=K, min_component_faces=N)`` keeps the K largest
+  connected components of the extracted mesh among those with at least N faces (psnerf_amd/meshclean.py; on the device
+  csrc/meshclean.hip, applied to the device tensors before the copy-back and before the normals are estimated).  With both at
+  their defaults (None, 0) the extraction is bit for bit what it was.
+Not implemented, and refused loudly:
+  ``refinement_step > 0`` (RMSprop vertex refinement, extracting.py:237-323): it needs d / dp through the value pass and the
+    gradient sweep of the geometry network, and ops.GeoFieldFused.backward returns no gradient for p -- a change to the chain
+    engine, not to this module;
+  ``mask_loader`` (extracting.py:326-377): the reference's filter_points assumes UNISURF's world -> NDC matrices, while the
+    reference's own loader supplies camera-to-world poses and a pixel-unit K (stage1/dataloading/dataset.py:125-127), so a faithful
+    port would carve with the wrong projection on this project's data.
 """
 import os
 import re
@@ -278,7 +287,8 @@ class Extractor3D(object):
     """extracting.py:15-52, same constructor and methods."""
 
     def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0, device=None, resolution0=16,
-                 upsampling_steps=3, with_normals=False, padding=0.4, refine_max_faces=10000):
+                 upsampling_steps=3, with_normals=False, padding=0.4, refine_max_faces=10000, keep_components=None,
+                 min_component_faces=0):
         if device is None and isinstance(model, torch.nn.Module):
             device = next(model.parameters()).device   # (the reference leaves the model where it is; so do we, and follow it)
         self.model = model.to(device) if (model is not None and hasattr(model, 'to')) else model
@@ -291,6 +301,9 @@ class Extractor3D(object):
         self.with_normals = with_normals
         self.padding = padding
         self.refine_max_faces = refine_max_faces
+        # clean-up (meshclean.py): keep the K largest connected components among those with at least N faces; (None, 0) = off
+        self.keep_components = keep_components
+        self.min_component_faces = min_component_faces
         self.last_grid = None   # the dense value grid of the last generate_* call (device tensor or numpy array)
         self.phase_events = None  # a list: (phase, start event, end event) of the device phases are appended (measurement runs)
         self.last_known = None  # which of its points were evaluated (bool, same shape; None without upsampling: all of them)
@@ -309,10 +322,12 @@ class Extractor3D(object):
         stats_dict = {} if stats_dict is None else stats_dict
         if self.refinement_step > 0:
             raise NotImplementedError('Extractor3D: refinement_step > 0 (RMSprop refinement of the vertices, reference '
-                                      'extracting.py:237-323) is not implemented; every shipped config uses 0')
+                                      'extracting.py:237-323) is not implemented: it needs the gradient of the geometry field with '
+                                      'respect to the points through the fused chains; every shipped config uses 0')
         if mask_loader is not None:
             raise NotImplementedError('Extractor3D: mask_loader (carving by dilated image masks, reference extracting.py:120-127, '
-                                      '326-377) is not implemented: it needs skimage.morphology')
+                                      '326-377) is not implemented: its projection assumes world -> NDC matrices, the data '
+                                      'loader supplies camera-to-world poses and a pixel-unit K')
         kwargs.setdefault('clip', False)
         threshold = iso_value(self.threshold)
         box_size = 2 + self.padding
@@ -364,24 +379,45 @@ class Extractor3D(object):
         threshold = iso_value(self.threshold)
         n = occ_hat.shape[0]
         assert tuple(occ_hat.shape) == (n, n, n), 'cubic value grids only'
+        clean = self.keep_components is not None or self.min_component_faces > 0
         t0 = time.time()
         if torch.is_tensor(occ_hat) and occ_hat.is_cuda:
             from .. import hip
             with _Phase(self.phase_events, 'marching cubes'):
                 v, f = hip.marching_cubes(occ_hat.contiguous(), threshold, box_size)
+            if clean:   # on the device tensors: less is copied back, fewer normals are computed
+                from .. import meshclean
+                torch.cuda.synchronize(occ_hat.device)
+                t1 = time.time()
+                with _Phase(self.phase_events, 'components'):
+                    v, f, _, report = meshclean._device_clean(v, f, None, self.keep_components, self.min_component_faces, 'faces')
+                torch.cuda.synchronize(occ_hat.device)
+                t0 += self._clean_stats(stats_dict, report, time.time() - t1)   # ('time (marching cubes)' stays what it was)
             with _Phase(self.phase_events, 'copy-back'):
                 vertices, faces = v.cpu().numpy(), f.cpu().numpy()
+            stats_dict['time (marching cubes)'] = time.time() - t0
         else:
             grid = occ_hat.numpy() if torch.is_tensor(occ_hat) else np.asarray(occ_hat)
             vertices, faces = host_marching_cubes(grid, threshold)
             vertices = to_world(vertices, n, box_size)
-        stats_dict['time (marching cubes)'] = time.time() - t0
+            stats_dict['time (marching cubes)'] = time.time() - t0
+            if clean:
+                from .. import meshclean
+                t1 = time.time()
+                vertices, faces, _, report = meshclean.host_clean(vertices, faces, None, self.keep_components, self.min_component_faces)
+                self._clean_stats(stats_dict, report, time.time() - t1)
         normals = None
         if self.with_normals and vertices.shape[0] != 0:
             t0 = time.time()
             normals = self.estimate_normals(vertices, c)
             stats_dict['time (normals)'] = time.time() - t0
         return Mesh(vertices, faces, vertex_normals=normals)
+
+    @staticmethod
+    def _clean_stats(stats_dict, report, seconds):
+        stats_dict['n_components'], stats_dict['n_faces_removed'] = report['n_components'], report['n_faces_removed']
+        stats_dict['time (components)'] = seconds
+        return seconds
 
     def estimate_normals(self, vertices, c=None):
         """extracting.py:209-235: -grad occupancy-logit / |.| at the vertices, through the model's ``gradient``."""
