@@ -461,20 +461,10 @@ def test_chain_bf16x3_geometry_field_vs_exact_and_float64(cuda):
             objective(logit, feat, grad).backward()
         return [logit.detach(), feat.detach(), grad.detach()] + [p.grad.clone() for p in params]
 
-    x = pts.double().requires_grad_()
-    xs = x * scale
-    pe = torch.cat([xs] + [f(xs * 2.0 ** k) for k in range(octaves) for f in (torch.sin, torch.cos)], -1)
-    h = pe
-    n = len(P64) // 2
-    for l in range(n):
-        if l in skips:
-            h = torch.cat([h, pe], -1)  # (effective weights: the 1 / sqrt(2) of network.py:90-91 is folded in)
-        h = h @ P64[2 * l].t() + P64[2 * l + 1]
-        if l < n - 1:
-            h = torch.nn.functional.softplus(h, beta=100)
-    g64 = torch.autograd.grad(h[:, :1].sum(), x, create_graph=True)[0]
-    objective(h[:, :1], h[:, 1:], g64).backward()
-    ref = [h[:, :1].detach(), h[:, 1:].detach(), g64.detach()] + [p.grad for p in P64]
+    from tests.engine_cases import geo_field   # the float64 statement of the field (shared with tests/test_engines_gpu.py)
+    l64, f64, g64 = geo_field(pts.double().requires_grad_(), P64, octaves, skips, scale)
+    objective(l64, f64, g64).backward()
+    ref = [l64.detach(), f64.detach(), g64.detach()] + [p.grad for p in P64]
     err = {}
     for mode in ('fp32', 'bf16x3'):
         got = run(mode)
