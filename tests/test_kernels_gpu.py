@@ -549,31 +549,10 @@ def test_sample_points_bit_exact(cuda, with_outer, with_noise):
     else:
         hip.sample_points(cam, rays, far, out, True, near, U(steps), idx=hit_idx, dist=dist, delta=delta, noise=nz_h)
 
-    def jitter(d, nz):
-        mid = 0.5 * (d[:, 1:] + d[:, :-1])
-        hi = torch.cat([mid, d[:, -1:]], dim=-1)
-        lo = torch.cat([d[:, :1], mid], dim=-1)
-        return lo + (hi - lo) * nz
-
-    u = torch.linspace(0.0, 1.0, steps=S, device=cuda).view(1, -1)
-    d2 = near * (1.0 - u) + far[miss_idx].view(-1, 1) * u
-    if with_noise:
-        d2 = jitter(d2, nz_m)
-    ref = torch.zeros(N, S, 3, device=cuda)
-    ref[miss_idx] = cam[miss_idx].unsqueeze(-2) + rays[miss_idx].unsqueeze(-2) * d2.unsqueeze(-1)
-    dh, fh = dist[hit_idx], far[hit_idx]
-    dnp, dfp = dh - delta, dh + delta
-    dnp = torch.where(dnp < near, torch.full_like(dnp, near), dnp)
-    dfp = torch.where(dfp > fh, fh, dfp)
-    u = torch.linspace(0.0, 1.0, steps=steps, device=cuda).view(1, -1)
-    d1 = dnp.view(-1, 1) * (1.0 - u) + dfp.view(-1, 1) * u
-    if with_outer:
-        uo = torch.linspace(0.0, 1.0, steps=steps_out, device=cuda).view(1, -1)
-        d_out = near * (1.0 - uo) + dnp.view(-1, 1) * uo
-        d1, _ = torch.sort(torch.cat([d_out, d1], dim=-1), dim=-1)
-    if with_noise:
-        d1 = jitter(d1, nz_h)
-    ref[hit_idx] = cam[hit_idx].unsqueeze(-2) + rays[hit_idx].unsqueeze(-2) * d1.unsqueeze(-1)
+    from tests.ray_cases import sample_points_reference   # the torch formulation, shared with tests/test_ray_gpu.py
+    lin = lambda n: torch.linspace(0.0, 1.0, steps=n, device=cuda)
+    ref = sample_points_reference(cam, rays, far, dist, hit_idx, miss_idx, near, delta, steps, steps_out if with_outer else 0,
+                                  lin(S), lin(steps), lin(steps_out) if with_outer else None, nz_m, nz_h)
     assert torch.equal(out, ref), 'max |diff| = %g' % float((out - ref).abs().max())
 
 

@@ -558,17 +558,13 @@ def test_root_finder_and_crossing_vs_stepwise_formulation(cuda):
         hip.sample_points(cam.reshape(-1, 3).contiguous(), rays.reshape(-1, 3).contiguous(), far.reshape(-1), p_prop, False,
                           float(ren.depth_range[0]), u)
         val = (ren._occ(p_prop.reshape(-1, 3)) - 0.5).view(1, n, M)
-        sgn = torch.cat([torch.sign(val[:, :, :-1] * val[:, :, 1:]), torch.ones(1, n, 1, device=cuda)], dim=-1)
-        cost = sgn * torch.arange(M, 0, -1, device=cuda).float()
-        values, idx = torch.min(cost, -1)
-        mask_ref = (values < 0) & (torch.gather(val, 2, idx.unsqueeze(-1)).squeeze(-1) < 0) & (val[:, :, 0] < 0)
+        from tests.ray_cases import first_crossing_reference   # the tensor formulation, shared with tests/test_ray_gpu.py
+        mask_ref, first_free_ref, bracket_ref = first_crossing_reference(val[0], u[0], u[1], float(ren.depth_range[0]), far)
         flags = st['flags']
         assert torch.equal((flags & 1).bool(), mask_ref.reshape(-1)) and torch.equal((flags & 2).bool(), (val[0, :, 0] < 0))
+        assert torch.equal(first_free_ref, val[0, :, 0] < 0)
         m = mask_ref.reshape(-1)
-        idx2 = torch.clamp(idx + 1, max=M - 1)
-        dep = lambda i: (float(ren.depth_range[0]) * u[1][i] + far * u[0][i]).reshape(-1)
-        gat = lambda i: torch.gather(val, 2, i.unsqueeze(-1)).reshape(-1)
-        for row, ref in enumerate((dep(idx), dep(idx2), gat(idx), gat(idx2))):
+        for row, ref in enumerate(bracket_ref):
             assert torch.equal(st['bracket'][row][m], ref[m]), 'bracket row %d' % row
         # -- fused vs step-by-step secant
         d_fused = ren._march_finish(st, 8)
