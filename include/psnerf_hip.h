@@ -70,6 +70,22 @@ int psn_pe_encode_jvp(const float* x, const float* t, int64_t n, int n_freqs, fl
 int psn_pe_encode_bwd(const float* x, const float* d_out, int64_t n, int n_freqs, float scale, int out_stride,
                       const float* d_out2, int out2_stride, float* d_x, void* stream);
 
+/* Gradient of the stage-1 geometry field with respect to its query points (ops.GeoField / ops.GeoFieldFused backward,
+ * slot 0), ONE launch, no [n, d_pe] intermediate in memory.  With d_pe = 3 + 6 n_freqs (<= 64) and s = scale:
+ *   t [n, d_pe]  = dz0 [n, h0] w0 [h0, d_pe]  (+ dzs [n, hs] ws [hs, d_pe])      fp32 MFMA, fp32 accumulation
+ *   d_p[r, c]    = sum_k J_k(p_rc) t[r, k]  (+ d_grad[r, c] sum_k H_k(p_rc) (g_pe[r, k] + g_pe2[r, k]))
+ * over the encoding columns k of coordinate c: J = s | 2^f s cos | -2^f s sin and H = 0 | -(2^f s)^2 sin | -(2^f s)^2 cos
+ * for the identity | sin | cos column of octave f, all at 2^f s p_rc.
+ * dz0 / dzs are the cotangents of the pre-activations of layer 0 / of the skip layer, w0 / ws the EFFECTIVE weights of the
+ * encoding columns of those layers (ws = the column range W_sk[:, d_a:]); every matrix is row-major with a row stride in
+ * floats (column ranges of wider tensors are fine), h0 and hs are 1..512.  dzs = ws = NULL: no skip block.  g_pe = d_grad
+ * = NULL: no second-order term; g_pe2 may be NULL on its own.  Each d_p element is written by one lane in a fixed order:
+ * the same bits in every run.  n = 0 returns PSN_OK without a launch. */
+int psn_geo_point_grad(const float* p, int64_t n, int n_freqs, float scale, const float* dz0, int64_t ld_dz0, int h0,
+                       const float* w0, int64_t ld_w0, const float* dzs, int64_t ld_dzs, int hs, const float* ws,
+                       int64_t ld_ws, const float* g_pe, int64_t ld_g, const float* g_pe2, int64_t ld_g2,
+                       const float* d_grad, float* d_p, void* stream);
+
 /* ------------------------------------------------------------------------
  * fp32-MFMA GEMM with fused epilogues: the torch.nn.Linear / addmm / mm calls
  * of stage1/model/network.py:85-106 and stage2/model/renderer.py:17-49 and

@@ -178,6 +178,32 @@ def pe_encode_bwd(x, d_out, n_freqs, scale=1.0, add=None):
     return d_x
 
 
+def geo_point_grad(p, n_freqs, scale, dz0, w0, dzs=None, ws=None, g_pe=None, g_pe2=None, d_grad=None):
+    """d loss / d p [n,3] of the stage-1 geometry field (psn_geo_point_grad): J(p)^T (dz0 @ w0 + dzs @ ws) and, when g_pe and
+    d_grad are given, + H(p)[g_pe + g_pe2, d_grad].  dz0 [n,h0] / dzs [n,hs]: cotangents of the pre-activations of layer 0 / of
+    the skip layer; w0 [h0, >= d_pe] / ws [hs, >= d_pe]: the encoding columns of their EFFECTIVE weights; g_pe / g_pe2
+    [n, >= d_pe]: d logit / d pe in one or two pieces.  Every matrix may be a column range of a wider tensor."""
+    n, d_pe = p.shape[0], 3 + 6 * int(n_freqs)
+    assert p.shape == (n, 3) and dz0.shape[0] == n and w0.shape[0] == dz0.shape[1] and w0.shape[1] >= d_pe
+    assert (dzs is None) == (ws is None) and (g_pe is None) == (d_grad is None) and (g_pe2 is None or g_pe is not None)
+    if dzs is not None:
+        assert dzs.shape[0] == n and ws.shape[0] == dzs.shape[1] and ws.shape[1] >= d_pe
+    for t in (g_pe, g_pe2):
+        assert t is None or (t.shape[0] == n and t.shape[1] >= d_pe)
+    assert d_grad is None or d_grad.shape == (n, 3)
+    d_p = torch.empty(n, 3, device=p.device, dtype=torch.float32)
+    if n == 0:
+        return d_p
+    opt = lambda t, name: (None, 0) if t is None else (_mat_ptr(t, name), _ld(t))
+    (dzs_p, dzs_ld), (ws_p, ws_ld), (g_p, g_ld), (g2_p, g2_ld) = opt(dzs, 'dzs'), opt(ws, 'ws'), opt(g_pe, 'g_pe'), opt(g_pe2, 'g_pe2')
+    with _Prof('geo_point_grad', n):
+        _check(_lib.psn_geo_point_grad(_tptr(p, 'p'), n, int(n_freqs), float(scale), _mat_ptr(dz0, 'dz0'), _ld(dz0), dz0.shape[1],
+                                       _mat_ptr(w0, 'w0'), _ld(w0), dzs_p, dzs_ld, 0 if dzs is None else dzs.shape[1], ws_p, ws_ld,
+                                       g_p, g_ld, g2_p, g2_ld, _tptr(d_grad, 'd_grad', allow_none=True), _tptr(d_p, 'd_p'), _stream()),
+               'geo_point_grad')
+    return d_p
+
+
 def sample_points(origin, direction, far, out, hit, near, u0, idx=None, dist=None, delta=0.0, u1=None, noise=None):
     """Fill rows ``idx`` (all rows if None) of out [N,S,3] with origin + direction * depth profile (psn_sample_points).
     u0 / u1: (linspace(0,1,c), 1 - linspace) pairs of device tensors."""

@@ -440,7 +440,8 @@ class GeoField(torch.autograd.Function):
     as EFFECTIVE dense weights (weight-norm is applied by the caller with torch ops on the tiny weight
     tensors, so autograd maps dW back to weight_g / weight_v).
     Points are never differentiated on the reference's training path (sample depths are detached,
-    rendering.py:88-101), so no gradient is returned for p."""
+    rendering.py:88-101); when p requires a gradient (mesh refinement, extracting.py:283-310) backward returns
+    d loss / d p from hip.geo_point_grad, and with no parameter requiring one the weight-gradient GEMMs are skipped."""
 
     @staticmethod
     def forward(ctx, p, n_octaves, scale, skips, with_grad, *params):
@@ -495,6 +496,8 @@ class GeoField(torch.autograd.Function):
             keep = [p, W0p] + Ws + A + S
             if with_grad:
                 keep += U + R[1:n - 1]
+                if ctx.needs_input_grad[0]:
+                    keep.append(d_pe_t)  # d logit / d pe: the encoding's second derivative contracts with it
             ctx.save_for_backward(*keep)
         if grad is None:
             grad = torch.zeros(Q, 3, device=dev)
@@ -515,8 +518,12 @@ class GeoField(torch.autograd.Function):
         db = [None] * n
         sweep = ctx.with_grad and d_grad is not None
         dS = [None] * (n - 1)
+        need_p, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[5:])
+        dz_pe = {}  # cotangents of the pre-activations of the layers that read the encoding (need_p)
 
         def add_dW(l, a_t, b_mat, with_bias=False):  # dW[l] (+)= a_t^T @ b_mat ; db[l] = column sums of a_t
+            if not need_w:
+                return
             sk = _split_k_for(Q, a_t.shape[1], b_mat.shape[1])
             cs = torch.empty(a_t.shape[1], device=dev) if with_bias else None
             if dW[l] is None:
@@ -550,8 +557,9 @@ class GeoField(torch.autograd.Function):
                 add_dW(l, U[l], dR)
                 dR = nxt
             # R[n-1] is row 0 of the last layer broadcast over points
-            dW[n - 1] = torch.zeros_like(Ws[n - 1])
-            dW[n - 1][0] = hip.colsum(dR)
+            if need_w:
+                dW[n - 1] = torch.zeros_like(Ws[n - 1])
+                dW[n - 1][0] = hip.colsum(dR)
 
         g = d_out.contiguous()
         add_dW(n - 1, g, A[n - 1], with_bias=True)
@@ -563,12 +571,27 @@ class GeoField(torch.autograd.Function):
             else:
                 hip.gemm(g, Ws[l][:, :in_a], epi=hip.EPI_MUL_AUX, aux_in=S[l - 1], out=g_prev)
             g = g_prev
+            if need_p and (l - 1 == 0 or (l - 1) in skips):
+                dz_pe[l - 1] = g
             add_dW(l - 1, g, A[l - 1], with_bias=True)
-        dW[0] = dW[0][:, :d_pe]
+        if need_w:
+            dW[0] = dW[0][:, :d_pe]
+        d_p = None
+        if need_p:
+            # value path J^T (W_0^T dz_0 + sum_sk W_sk[:, in_a:]^T dz_sk) and, after a sweep, H[d logit / d pe, d_grad]: one launch
+            # (one more per skip layer beyond the first)
+            sks = [l for l in sorted(dz_pe) if l > 0]
+            first = sks[0] if sks else None
+            d_p = hip.geo_point_grad(p, ctx.n_octaves, ctx.scale, dz_pe[0], W0p,
+                                     dzs=None if first is None else dz_pe[first],
+                                     ws=None if first is None else Ws[first][:, Ws[first].shape[1] - d_pe:],
+                                     g_pe=sv[-1] if sweep else None, d_grad=d_grad.contiguous() if sweep else None)
+            for l in sks[1:]:
+                d_p = d_p + hip.geo_point_grad(p, ctx.n_octaves, ctx.scale, dz_pe[l], Ws[l][:, Ws[l].shape[1] - d_pe:])
         grads = []
         for l in range(n):
             grads += [dW[l], db[l]]
-        return (None, None, None, None, None) + tuple(grads)
+        return (d_p, None, None, None, None) + tuple(grads)
 
 
 # --------------------------------------------------------------------------- GGX microfacet shading
@@ -815,7 +838,9 @@ class GeoFieldFused(torch.autograd.Function):
     Returns (logit [Q,1], feat [Q,256], grad [Q,3]).  ``chains`` = fused.pack_geo_chains(...) (cached per step).
     ``feat_rows`` (None = Q): only the features of the first feat_rows rows are returned / receive a gradient -- the points
     behind them are evaluated for their gradient alone (the surface-normal points of rendering.py:200-212 riding behind
-    the render samples: one set of launches instead of two, and no [Q,256] zero-padded d feat in backward)."""
+    the render samples: one set of launches instead of two, and no [Q,256] zero-padded d feat in backward).
+    When p requires a gradient, backward returns d loss / d p (hip.geo_point_grad on the dumps of the two backward chains;
+    fp32 chains only); when no parameter requires one, the weight-gradient launches are skipped."""
 
     @staticmethod
     def forward(ctx, p, n_octaves, scale, skips, with_grad, chains, feat_rows, *params):
@@ -858,6 +883,8 @@ class GeoFieldFused(torch.autograd.Function):
             keep = [p, pe] + Ws + A
             if with_grad:
                 keep += U
+                if ctx.needs_input_grad[0]:
+                    keep += [r0, r_sk]  # d logit / d pe in its two pieces: the encoding's second derivative contracts with it
             ctx.save_for_backward(*keep)
         if grad is None:
             grad = torch.zeros(Q, 3, device=dev)
@@ -900,6 +927,15 @@ class GeoFieldFused(torch.autograd.Function):
                     mask=[A[n - 2 - j] for j in range(n - 1)],
                     aux2=[E[n - 2 - j] for j in range(n - 1)] if sweep else None,
                     save=[dZ[n - 2 - j] for j in range(n - 1)])
+        d_p = None
+        if ctx.needs_input_grad[0]:
+            # d loss / d p = J^T (W_0^T dZ_0 + W_sk[:, d_a:]^T dZ_sk) + H[d logit / d pe, d_grad]: the chains above already dumped
+            # every operand (the dependence of the sweep on the layers' inputs is folded into dZ through E)
+            d_p = hip.geo_point_grad(p, n_octaves, scale, dZ[0][:, :Ws[0].shape[0]], Ws[0], dzs=dZ[sk][:, :Ws[sk].shape[0]], ws=Ws[sk][:, d_a:],
+                                     g_pe=sv[-2] if sweep else None, g_pe2=sv[-1][:, d_a:d_a + d_pe] if sweep else None,
+                                     d_grad=d_grad.contiguous() if sweep else None)
+        if not any(ctx.needs_input_grad[7:]):  # no parameter wants a gradient (mesh refinement): none of the launches below
+            return (d_p,) + (None,) * (6 + 2 * n)
         # Every weight gradient of the call in ONE grouped launch: dW_l = dZ_l^T A_{l-1} (+ U_l^T dR_l from the sweep),
         # the bias gradients are the column sums of dZ_l, a by-product of staging the A tiles.
         a_last = A[n - 2]
@@ -922,7 +958,7 @@ class GeoFieldFused(torch.autograd.Function):
         grads = []
         for l in range(n):
             grads += [dW[l], db[l]]
-        return (None, None, None, None, None, None, None) + tuple(grads)
+        return (d_p, None, None, None, None, None, None) + tuple(grads)
 
 
 # --------------------------------------------------------------------------- stage-1 appearance network, fused chains

@@ -23,10 +23,15 @@ Clean-up (not in the reference; opt-in): ``Extractor3D(..., keep_components=K, m
   connected components of the extracted mesh among those with at least N faces (psnerf_amd/meshclean.py; on the device
   csrc/meshclean.hip, applied to the device tensors before the copy-back and before the normals are estimated).  With both at
   their defaults (None, 0) the extraction is bit for bit what it was.
+Vertex refinement (extracting.py:237-323): ``Extractor3D.refine_mesh(mesh, steps=N)`` / tools/refine_mesh.py run the reference's
+  RMSprop refinement of the vertices against the field (``refine_loss`` / ``refine_vertices`` below).  The reference's method calls
+  ``self.model.decoder``, which its own NeuralNetwork does not have, so it cannot run there; it is restated with
+  ``self.model(p, None, only_occupancy=True)``, the reading ``estimate_normals`` already takes.  Two implementations of one definition:
+  any differentiable callable through autograd.grad(create_graph=True) (any dtype; the host path, with oracle.stage1.NeuralNetwork),
+  and for a ``NeuralNetwork`` on the device ONE ops.GeoFieldFused call per step whose backward returns d / dp (csrc/geo_dp.hip).
 Not implemented, and refused loudly:
-  ``refinement_step > 0`` (RMSprop vertex refinement, extracting.py:237-323): it needs d / dp through the value pass and the
-    gradient sweep of the geometry network, and ops.GeoFieldFused.backward returns no gradient for p -- a change to the chain
-    engine, not to this module;
+  ``refinement_step > 0`` as a CONSTRUCTOR argument of generate_mesh / generate_from_latent (every shipped config uses 0): call
+    ``refine_mesh`` on the extracted mesh, or tools/refine_mesh.py on the written file;
   ``mask_loader`` (extracting.py:326-377): the reference's filter_points assumes UNISURF's world -> NDC matrices, while the
     reference's own loader supplies camera-to-world poses and a pixel-unit K (stage1/dataloading/dataset.py:125-127), so a faithful
     port would carve with the wrong projection on this project's data.
@@ -322,8 +327,8 @@ class Extractor3D(object):
         stats_dict = {} if stats_dict is None else stats_dict
         if self.refinement_step > 0:
             raise NotImplementedError('Extractor3D: refinement_step > 0 (RMSprop refinement of the vertices, reference '
-                                      'extracting.py:237-323) is not implemented: it needs the gradient of the geometry field with '
-                                      'respect to the points through the fused chains; every shipped config uses 0')
+                                      'extracting.py:237-323) is not wired into generate_mesh; every shipped config uses 0.  Call '
+                                      'Extractor3D.refine_mesh(mesh, steps=N) on the extracted mesh, or tools/refine_mesh.py on the file')
         if mask_loader is not None:
             raise NotImplementedError('Extractor3D: mask_loader (carving by dilated image masks, reference extracting.py:120-127, '
                                       '326-377) is not implemented: its projection assumes world -> NDC matrices, the data '
@@ -429,6 +434,24 @@ class Extractor3D(object):
             normals.append(ni.cpu().numpy())
         return np.concatenate(normals, axis=0)
 
+    def refine_mesh(self, mesh, occ_hat=None, c=None, steps=None, rng=None):
+        """extracting.py:237-323: ``steps`` (default: self.refinement_step) RMSprop steps on the vertices -> a new Mesh with the same
+        faces and vertex normals (the reference, too, estimates the normals before it refines).  ``occ_hat`` and ``c`` are accepted
+        and unused, as in the reference (which only asserts the grid is cubic).  ``rng``: np.random-like (permutation, dirichlet),
+        default the global np.random -- the reference shuffles with torch's DataLoader, so the face order is the same distribution
+        but not bit-pinned to it.  An empty mesh, or steps <= 0, returns ``mesh`` itself.  Leaves
+        self.last_refine = {'n_steps', 'time (refine)', 'loss_first', 'loss_last'}."""
+        steps = self.refinement_step if steps is None else int(steps)
+        if mesh.is_empty or len(mesh.faces) == 0 or steps <= 0:
+            return mesh
+        if hasattr(self.model, 'eval'):
+            self.model.eval()
+        t0 = time.time()
+        v, losses = refine_vertices(self.model, mesh.vertices, mesh.faces, steps, self.refine_max_faces, self.threshold,
+                                    np.random if rng is None else rng, self.device)
+        self.last_refine = {'n_steps': len(losses), 'time (refine)': time.time() - t0, 'loss_first': losses[0], 'loss_last': losses[-1]}
+        return Mesh(v.cpu().numpy().astype(np.float64), mesh.faces, vertex_normals=mesh.vertex_normals)
+
     # -- the two MISE drivers -------------------------------------------------------------------------------------------
     def _mise_host(self, threshold, box_size, stats_dict, **kwargs):
         mise = HostMISE(self.resolution0, self.upsampling_steps, threshold)
@@ -494,6 +517,73 @@ class Extractor3D(object):
         with _Phase(self.phase_events, 'fill'):
             hip.grid_ffill(grid)
         return grid
+
+
+# ------------------------------------------------------------------------------------------------ vertex refinement
+def _device_field(model, p):
+    """(occupancy sigmoid(-10 logit) [F], -d occupancy / d p [F, 3]) of a device NeuralNetwork at p [F, 3], differentiable in p: one
+    geometry-field call with its gradient sweep on DETACHED effective parameters (no parameter wants a gradient, so backward runs
+    the two adjoint chains and csrc/geo_dp.hip and no weight-gradient launch); -d sigmoid(-10 l) / d p = 10 s (1 - s) d l / d p is
+    formed with torch ops on the [F] / [F, 3] tensors."""
+    with torch.no_grad():
+        params = [t.detach() for t in model._geo_params()]
+    chains = model._geo_chains(params) if model.USE_FUSED_CHAINS and model._geo_chains_fit() else None
+    parts = [model._geo_call(q, True, params, chains) for q in torch.split(p, model.MAX_ROWS)]
+    logit, grad = (torch.cat([q[i] for q in parts], 0) if len(parts) > 1 else parts[0][i] for i in (0, 2))
+    occ = torch.sigmoid(logit[:, 0] * -10.0)
+    return occ, (10.0 * occ * (1.0 - occ))[:, None] * grad
+
+
+def refine_loss(model, v, faces, eps, threshold):
+    """extracting.py:283-310 for vertices v [V, 3], a batch of faces [F, 3] (int64) and barycentric weights eps [F, 3]:
+        face_point = sum(eps * v[faces]);  face_normal = cross(v1 - v0, v2 - v1) / (|.| + 1e-10)
+        face_value = sigmoid(-10 logit(face_point));  normal_target = -d face_value.sum() / d face_point / (|.| + 1e-10)
+        loss = mean((face_value - threshold)^2) + 0.01 mean(sum((face_normal - normal_target)^2))
+    -> (loss, loss_target, loss_normal), differentiable in v.  ``model``: a psnerf_amd NeuralNetwork on the device (-> _device_field),
+    or any callable with the reference's signature that autograd can differentiate twice (the reference's own form)."""
+    from .network import NeuralNetwork
+    face_vertex = v[faces]
+    face_point = (face_vertex * eps[:, :, None]).sum(dim=1)
+    face_v1 = face_vertex[:, 1, :] - face_vertex[:, 0, :]
+    face_v2 = face_vertex[:, 2, :] - face_vertex[:, 1, :]
+    face_normal = torch.cross(face_v1, face_v2, dim=1)
+    face_normal = face_normal / (face_normal.norm(dim=1, keepdim=True) + 1e-10)
+    if isinstance(model, NeuralNetwork):
+        if not v.is_cuda:
+            raise RuntimeError('refine_loss: psnerf_amd.stage1.NeuralNetwork runs on the device only; on the host use oracle.stage1.NeuralNetwork')
+        face_value, normal_target = _device_field(model, face_point)
+    else:
+        face_value = torch.cat([model(p_split, None, only_occupancy=True).squeeze(-1)
+                                for p_split in torch.split(face_point.unsqueeze(0), 20000, dim=1)], dim=1).squeeze(0)
+        normal_target = -torch.autograd.grad([face_value.sum()], [face_point], create_graph=True)[0]
+    normal_target = normal_target / (normal_target.norm(dim=1, keepdim=True) + 1e-10)
+    loss_target = (face_value - threshold).pow(2).mean()
+    loss_normal = (face_normal - normal_target).pow(2).sum(dim=1).mean()
+    return loss_target + 0.01 * loss_normal, loss_target, loss_normal
+
+
+def refine_vertices(model, vertices, faces, steps, max_faces, threshold, rng, device, dtype=torch.float32):
+    """The loop of extracting.py:254-320: v = Parameter(vertices) in ``dtype`` on ``device``, RMSprop(lr = 1e-5), face batches of
+    ``max_faces`` from a fresh rng.permutation per epoch, rng.dirichlet((0.5, 0.5, 0.5)) weights per step, exactly ``steps`` steps.
+    -> (refined vertices [V, 3] detached, [loss of every step])"""
+    v = torch.nn.Parameter(torch.as_tensor(np.asarray(vertices), dtype=dtype).to(device))
+    faces = torch.as_tensor(np.asarray(faces), dtype=torch.long).to(device)
+    optimizer = torch.optim.RMSprop([v], lr=1e-5)
+    losses, it_r = [], 0
+    while it_r < steps:
+        perm = torch.as_tensor(np.asarray(rng.permutation(faces.shape[0])), dtype=torch.long)
+        for f_idx in torch.split(perm, max_faces):
+            f_it = faces[f_idx.to(device)]
+            optimizer.zero_grad()
+            eps = torch.as_tensor(rng.dirichlet((0.5, 0.5, 0.5), size=f_it.shape[0]), dtype=dtype).to(device)
+            loss = refine_loss(model, v, f_it, eps, threshold)[0]
+            loss.backward()
+            optimizer.step()
+            losses.append(loss.detach())
+            it_r += 1
+            if it_r >= steps:
+                break
+    return v.detach(), [float(l) for l in losses]
 
 
 def _make_3d_grid(nx):

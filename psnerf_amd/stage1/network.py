@@ -10,6 +10,10 @@ checkpoints load unchanged.  Mapping to kernels:
   * no-grad occupancy queries (ray-march sweep, shadow rays) -> the lean register-resident engine
     (fused.pack_geo_occupancy), re-packed once per optimiser step; the secant refinement -> psn_root_find, the same
     engine iterating inside one launch.
+Gradient with respect to the points: ``forward(only_occupancy=True)``, ``forward(return_logits=True)``, ``infer_occ`` and
+``gradient(p, tflag=True)`` are differentiable in ``p`` as in the reference (both geometry engines return d / dp, csrc/geo_dp.hip).
+The render path (``forward`` with ``ray_d``, ``render_and_gradient``) is NOT: the appearance engine has no gradient for its point
+and view columns, so ``p`` enters the geometry call detached there rather than receiving a partial gradient.
 Weight normalisation (w = g * v / |v|) of all layers of a network is one launch forward / one backward
 (ops.WeightNormAll), so autograd carries dW back to weight_g / weight_v.
 """
@@ -271,7 +275,9 @@ class NeuralNetwork(fused.PackCached, nn.Module):
             logit, _, _ = self._geo_parts(flat, False)
             return torch.sigmoid(logit * -10.0).reshape(*shp, 1)
         if ray_d is not None:
-            logit, feat, grad = self._geo_parts(flat, True)
+            # the appearance engine (ops.AppNetFused) has no gradient for its point and view columns: a gradient for p through
+            # the geometry call alone would be a silently partial one, so the render path stays non-differentiable in p
+            logit, feat, grad = self._geo_parts(flat.detach(), True)
             rgb = self._app_parts(flat, ray_d.reshape(-1, 3), grad, feat).reshape(*shp, 3)
             if return_addocc:
                 return rgb, torch.sigmoid(logit * -10.0).reshape(*shp, 1)
@@ -286,16 +292,17 @@ class NeuralNetwork(fused.PackCached, nn.Module):
         the ``extra`` points (the surface-normal points of rendering.py:200-212, 2 N next to N S render samples) ride
         behind the render samples as rows that are evaluated for d logit / d p only.  Same arithmetic per row as the two
         separate calls; saves four latency-bound chain launches, a weight-gradient launch and the second gradient
-        accumulation of every geometry parameter.  -> (rgb [..., 3], occupancy [..., 1], gradient [Qx, 1, 3])."""
+        accumulation of every geometry parameter.  -> (rgb [..., 3], occupancy [..., 1], gradient [Qx, 1, 3]).
+        Like ``forward`` with ``ray_d``, not differentiable in ``p`` or ``extra`` (both enter detached)."""
         shp = p.shape[:-1]
-        flat, ex = p.reshape(-1, 3), extra.reshape(-1, 3)
+        flat, ex = p.reshape(-1, 3).detach(), extra.reshape(-1, 3).detach()
         q1 = flat.shape[0]
         params = self._geo_params()
         fused_ok = (self.USE_FUSED_CHAINS and self._geo_chains_fit() and q1 + ex.shape[0] <= self.MAX_ROWS and q1 > 0
                     and flat.is_cuda)
         if not fused_ok:
             rgb, occ = self.forward(p, ray_d, return_addocc=True)
-            return rgb, occ, self.gradient(extra)
+            return rgb, occ, self.gradient(ex)
         logit, feat, grad = self._geo_call(torch.cat([flat, ex], dim=0), True, params, self._geo_chains(params), feat_rows=q1)
         grad_r, grad_x = ops.SplitRows.apply(grad, q1)
         logit_r, _ = ops.SplitRows.apply(logit, q1)
