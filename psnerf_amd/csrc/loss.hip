@@ -408,7 +408,7 @@ __global__ __launch_bounds__(256) void row_adam_kernel(RowAdamArgs a) {
 
 static int row_adam_impl(int n_items, const PsnRowAdamItem* items, const int64_t* idx, int n_idx, const float* step_sizes_dev, void* stream) {
     using namespace psn;
-    PSN_CHECK_ARG(items && idx && n_items >= 1 && n_items <= PSN_ROW_ADAM_MAX && n_idx >= 0, "row_adam: bad arguments");
+    PSN_CHECK_ARG(items && (idx || n_idx == 0) && n_items >= 1 && n_items <= PSN_ROW_ADAM_MAX && n_idx >= 0, "row_adam: bad arguments");  // (an empty torch tensor has a null data pointer)
     RowAdamArgs a = {};
     a.dev = step_sizes_dev;
     int64_t max_rows = 0;

@@ -1098,18 +1098,26 @@ def test_mask_count_and_inverse_index_equal_torch(cuda, n):
     assert torch.equal(hip.inverse_index(idx[:0], n), torch.full((n,), -1, dtype=torch.int32, device=cuda))
 
 
-@pytest.mark.parametrize('V,Ns,n_items', [(8, 3655, 2), (3, 17, 1), (16, 1000, 2), (1, 64, 2)])
-def test_pair_sums_group_vs_torch(cuda, V, Ns, n_items):
+# rows_per_block starts at 16 and doubles while ceil(Ns / rows) > PSN_PAIR_SUMS_MAX_CHUNKS = 2048: 32,769 rows are the first to double it
+@pytest.mark.parametrize('V,Ns,n_items,C', [
+    pytest.param(8, 3655, 2, 256, id='8-3655-2'), pytest.param(3, 17, 1, 256, id='3-17-1'), pytest.param(16, 1000, 2, 256, id='16-1000-2'),
+    pytest.param(1, 64, 2, 256, id='1-64-2'),
+    # one column group of 64 / two: threads 4 cg >= C idle | V = PSN_PAIR_SUMS_MAX_V at one row, a partial block of 15, exactly one of 16, 17
+    pytest.param(3, 333, 2, 64, id='3-333-2-C64'), pytest.param(8, 130, 1, 128, id='8-130-1-C128'),
+    pytest.param(16, 1, 2, 256, id='16-1-2'), pytest.param(16, 15, 1, 64, id='16-15-1-C64'), pytest.param(16, 16, 2, 128, id='16-16-2-C128'),
+    pytest.param(16, 17, 1, 256, id='16-17-1'), pytest.param(2, 32769, 1, 256, id='2-32769-1-rows32')])
+def test_pair_sums_group_vs_torch(cuda, V, Ns, n_items, C):
     """psn_pair_sums_group (the separable input-block gradients of ops.VisibilityPair.backward, every input layer in two launches)
     against the torch formulation: sum over the lights, (sum over the points)^T PE(l), and the bias sum."""
     from psnerf_amd import hip
     g = torch.Generator().manual_seed(V * 1000 + Ns)
-    xs = [torch.randn(V * Ns, 256, generator=g).to(cuda) for _ in range(n_items)]
+    xs = [torch.randn(V * Ns, C, generator=g).to(cuda) for _ in range(n_items)]
     pe = torch.randn(V, 64, generator=g).to(cuda)
     pe[:, 63] = 0
     res = hip.pair_sums_group(xs, V, Ns, pe, 64, [i == 0 for i in range(n_items)])
     for i, (x, (sx, dWl, b)) in enumerate(zip(xs, res)):
-        x3 = x.double().view(V, Ns, 256)
+        x3 = x.double().view(V, Ns, C)
+        assert sx.shape == (Ns, C) and dWl.shape == (C, 64)
         assert_close(sx.cpu(), x3.sum(0).float().cpu(), 1e-6, 'sx', atol=1e-5)
         dzl = x3.sum(1)
         assert_close(dWl.cpu(), (dzl.t() @ pe.double()).float().cpu(), 1e-5, 'dWl')
