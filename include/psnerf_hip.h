@@ -867,6 +867,29 @@ int psn_closest_point(const PsnTriGrid* grid, const double* vertices, const int6
                       int64_t n_points, double* closest, double* dist, int64_t* tri, long long* n_tests, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Ray casting against the mesh, over the same index (csrc/meshray.hip; the float64 numpy definition is
+ * psnerf_amd/meshdist.py:host_ray_cast).  The reference has no such query: its depth, normal and shadow maps all come from marching
+ * the occupancy network.  grid, vertices, faces, cell_start, list, over_list, n_over: as psn_closest_point takes them.
+ *
+ * psn_ray_cast: origins / directions float64 [Q, 3] (directions need not be unit vectors: t is the parameter of o + t d); order =
+ *   null or a permutation of 0 .. Q - 1 in which the rays are worked on (outputs are written at the ray's own row either way).
+ *   The intersection test is the watertight one of Woop, Benthin and Wald (JCGT 2013), without back-face culling; a hit counts
+ *   when t_min <= t <= t_max (either may be infinite; t_min <= t_max).  mode = PSN_RAY_FIRST_HIT: t float64 [Q], tri int64 [Q],
+ *   bary float64 [Q, 3] or null, hit bytes [Q] = the minimum of (t, triangle index) in lexicographic order over ALL triangles the
+ *   test accepts -- bitwise reproducible; a miss gives inf, -1, NaN, 0.  mode = PSN_RAY_ANY_HIT: hit only, the walk ends at the
+ *   first accepted triangle; t, tri and bary receive the values of a miss.  A triangle of zero area or seen edge-on is never hit; a
+ *   ray with a non-finite component or a zero direction misses.  n_tests: null, or an int64 counter to which the number of
+ *   ray-triangle tests is added.  Q = 0 is a no-op.
+ * Errors: PSN_E_ARG for null pointers, F or Q out of range, a bad PsnTriGrid, an unknown mode, t_min > t_max; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_RAY_FIRST_HIT 0
+#define PSN_RAY_ANY_HIT 1
+int psn_ray_cast(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
+                 const int* list, const int* over_list, int64_t n_over, const double* origins, const double* directions,
+                 const int64_t* order, int64_t n_rays, double t_min, double t_max, int mode, double* t, int64_t* tri, double* bary,
+                 unsigned char* hit, long long* n_tests, void* stream);
+
+/* ------------------------------------------------------------------------
  * Mesh clean-up: connected components of a triangle mesh, per-component statistics and compaction (csrc/meshclean.hip; the numpy
  * definition is psnerf_amd/meshclean.py:host_*).  The reference has no such step (its only answer to floaters is --clip,
  * stage1/model/extracting.py:130-132); users of the pipeline take trimesh's split() on the host.

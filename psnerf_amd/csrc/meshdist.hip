@@ -8,27 +8,10 @@
 // as the numpy definition psnerf_amd/meshdist.py:host_closest_point does).  A thread per triangle / per query point; counters
 // are integer atomics aggregated per wave.  The order of the ids within a cell list (and of the oversize list) is not defined;
 // the query's result does not depend on it: it is the minimum of (squared distance, triangle id) in lexicographic order.
-#include "common.h"
+#include "trigrid.h"
 
 namespace psn {
 
-__device__ __forceinline__ int md_lane() { return threadIdx.x & 63; }
-
-// the cell of coordinate x on one axis, clamped into the grid (NaN -> 0).  Monotone in x: a rounded subtraction and a rounded
-// product with a positive constant are monotone, floor and the clamp are.
-__device__ __forceinline__ int md_cell(double x, double lo, double inv_cell, int n) {
-    const double t = floor((x - lo) * inv_cell);
-    if (!(t >= 0.0)) return 0;
-    return t > (double)(n - 1) ? n - 1 : (int)t;
-}
-
-struct MdTri {
-    double ax, ay, az, bx, by, bz, cx, cy, cz;
-};
-__device__ __forceinline__ MdTri md_load(const double* __restrict__ v, const int64_t* __restrict__ f, int64_t t) {
-    const int64_t i = f[3 * t], j = f[3 * t + 1], k = f[3 * t + 2];
-    return MdTri{v[3 * i], v[3 * i + 1], v[3 * i + 2], v[3 * j], v[3 * j + 1], v[3 * j + 2], v[3 * k], v[3 * k + 1], v[3 * k + 2]};
-}
 __device__ __forceinline__ double md_min3(double a, double b, double c) { return fmin(a, fmin(b, c)); }
 __device__ __forceinline__ double md_max3(double a, double b, double c) { return fmax(a, fmax(b, c)); }
 
@@ -264,20 +247,6 @@ __global__ __launch_bounds__(256) void closest_point_kernel(PsnTriGrid g, const 
         if (md_lane() == 0 && s > 0) atomicAdd(n_tests, s);
     }
 }
-
-static int md_check_grid(const PsnTriGrid* g, const char* what) {
-    PSN_CHECK_ARG(g != nullptr, "%s: null grid descriptor", what);
-    PSN_CHECK_ARG(g->cell > 0.0 && g->cell < __builtin_inf(), "%s: cell size %g", what, g->cell);
-    for (int a = 0; a < 3; ++a) {
-        PSN_CHECK_ARG(g->n[a] >= 1 && g->n[a] <= PSN_TRI_GRID_MAX_CELLS_PER_AXIS, "%s: %d cells on axis %d (1 .. %d)", what, g->n[a], a,
-                      PSN_TRI_GRID_MAX_CELLS_PER_AXIS);
-        PSN_CHECK_ARG(g->lo[a] <= g->hi[a] && g->lo[a] - g->lo[a] == 0.0 && g->hi[a] - g->hi[a] == 0.0, "%s: bounding box [%g, %g] on axis %d", what,
-                      g->lo[a], g->hi[a], a);
-    }
-    PSN_CHECK_ARG(g->max_span >= 1, "%s: max_span=%d", what, g->max_span);
-    return PSN_OK;
-}
-static inline unsigned md_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace psn
 

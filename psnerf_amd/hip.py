@@ -1527,6 +1527,40 @@ def closest_point(grid, vertices, faces, cell_start, lst, over_list, n_over, poi
     return closest, dist, tri
 
 
+# --------------------------------------------------------------------------- ray casting (csrc/meshray.hip)
+def ray_cast(grid, vertices, faces, cell_start, lst, over_list, n_over, origins, directions, t_min=0.0, t_max=float('inf'), order=None,
+             any_hit=False, n_tests=None, want_bary=True):
+    """psn_ray_cast: origins / directions float64 [Q, 3] -> (t float64 [Q], triangle id int64 [Q], barycentrics float64 [Q, 3] or None,
+    hit uint8 [Q]): the first hit with t_min <= t <= t_max over the whole mesh (a miss: inf, -1, NaN, 0), or with ``any_hit`` only
+    ``hit``.  order = the permutation in which the rays are worked on (or None); n_tests (int64 [1]) accumulates the number of
+    ray-triangle tests."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    for name, x in (('origins', origins), ('directions', directions)):
+        _tptr(x, 'ray_cast: %s' % name, torch.float64)
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise RuntimeError('ray_cast: %s [Q, 3] expected, got %s' % (name, tuple(x.shape)))
+    if origins.shape != directions.shape:
+        raise RuntimeError('ray_cast: %d origins and %d directions' % (origins.shape[0], directions.shape[0]))
+    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
+    q = origins.shape[0]
+    assert order is None or order.numel() == q
+    dev = vertices.device
+    t = torch.empty(q, dtype=torch.float64, device=dev)
+    tri = torch.empty(q, dtype=torch.int64, device=dev)
+    bary = torch.empty(q, 3, dtype=torch.float64, device=dev) if want_bary else None
+    hit = torch.empty(q, dtype=torch.uint8, device=dev)
+    if q == 0:
+        return t, tri, bary, hit
+    with _Prof('ray_cast_any' if any_hit else 'ray_cast', q):
+        _check(_lib.psn_ray_cast(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cell_start, 'cell_start', torch.int32),
+                                 _tptr(lst, 'list', torch.int32), _tptr(over_list, 'over_list', torch.int32), int(n_over),
+                                 origins.data_ptr(), directions.data_ptr(), None if order is None else _tptr(order, 'order', torch.int64), q,
+                                 float(t_min), float(t_max), RAY_ANY_HIT if any_hit else RAY_FIRST_HIT, t.data_ptr(), tri.data_ptr(),  # noqa: F821
+                                 None if bary is None else bary.data_ptr(), hit.data_ptr(),
+                                 None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'ray_cast')
+    return t, tri, bary, hit
+
+
 # --------------------------------------------------------------------------- mesh clean-up (csrc/meshclean.hip)
 def cc_label(faces, n_vertices, status):
     """psn_cc_label: faces int64 [F, 3] -> labels int32 [n_vertices], the smallest vertex index reachable from each vertex.  status

@@ -21,6 +21,14 @@ distance, so no NaN arises and nothing is zeroed.
 Sampling is trimesh.sample.sample_surface as documented: faces with probability proportional to their area, a uniform point in
 the face from two uniforms with the reflection u + v > 1 -> (1 - u, 1 - v).  The distribution is the contract; the order of the
 draws (all face picks, then all (u, v) pairs) is this module's own.
+
+Ray casting (the reference has none: every depth, normal and shadow map of its comes from marching the occupancy network) follows
+the same pattern: ``host_ray_cast`` is the definition, csrc/meshray.hip through ``MeshIndex.ray_cast`` the device path over the same
+grid.  Definition.  A ray o + t d hits a triangle by the watertight test of Woop, Benthin and Wald (JCGT 2013), without back-face
+culling and with t_min <= t <= t_max; the result per ray is the minimum of (t, triangle index) in lexicographic order over ALL
+triangles; a miss is t = inf, triangle -1, NaN barycentrics.  With ``any_hit`` only the boolean is defined.
+Stated differences from what a plain Moeller-Trumbore caster returns: a triangle with det == 0 (zero area, or seen edge-on) is never
+hit; a ray with a NaN (or infinite) component or a zero direction misses.
 """
 import os
 
@@ -134,6 +142,99 @@ def host_closest_point(vertices, faces, points):
         tri_id[q0:q0 + step] = np.argmin(d2, axis=1)            # (the first minimum: the lowest index)
     closest, dist = host_point_triangle(v, f, pts, tri_id)
     return closest, dist, tri_id
+
+
+def _ray_frames(origins, directions):
+    """Per ray the frame of the watertight test: (valid [Q], k int64 [Q, 3] = (kx, ky, kz), o [Q, 3] = the origin in that order,
+    S [Q, 3] = (Sx, Sy, Sz)).  kz = the axis of the largest |d| (the first on a tie), kx, ky the next two cyclically, swapped when
+    d[kz] < 0.  Rays with a non-finite component or a zero direction are not valid (their frame is a placeholder)."""
+    o = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError('rays: origins %s and directions %s differ in shape' % (o.shape, d.shape))
+    valid = np.isfinite(o).all(axis=1) & np.isfinite(d).all(axis=1) & (d != 0.0).any(axis=1)
+    d = np.where(valid[:, None], d, np.array([0.0, 0.0, 1.0]))
+    o = np.where(valid[:, None], o, 0.0)
+    kz = np.argmax(np.abs(d), axis=1)            # (the first maximum)
+    kx, ky = (kz + 1) % 3, (kz + 2) % 3
+    rows = np.arange(len(d))
+    swap = d[rows, kz] < 0.0
+    kx, ky = np.where(swap, ky, kx), np.where(swap, kx, ky)
+    k = np.stack([kx, ky, kz], axis=1)
+    dk = d[rows, kz]
+    S = np.stack([d[rows, kx] / dk, d[rows, ky] / dk, 1.0 / dk], axis=1)
+    return valid, k, np.take_along_axis(o, k, axis=1), S
+
+
+def _ray_triangles(o, S, a, b, c):
+    """The watertight ray-triangle test of Woop, Benthin and Wald (JCGT 2013), operation for operation as csrc/meshray.hip:mr_test.
+    o, S: lists of three broadcastable arrays, the origin and the shear constants in the ray's (kx, ky, kz) order; a, b, c: the
+    corners in the same order -> (accepted, t, U, V, W, det); t_min / t_max are the caller's."""
+    with np.errstate(all='ignore'):
+        Akz, Bkz, Ckz = a[2] - o[2], b[2] - o[2], c[2] - o[2]
+        Ax, Ay = (a[0] - o[0]) - S[0] * Akz, (a[1] - o[1]) - S[1] * Akz
+        Bx, By = (b[0] - o[0]) - S[0] * Bkz, (b[1] - o[1]) - S[1] * Bkz
+        Cx, Cy = (c[0] - o[0]) - S[0] * Ckz, (c[1] - o[1]) - S[1] * Ckz
+        U = Cx * By - Cy * Bx
+        V = Ax * Cy - Ay * Cx
+        W = Bx * Ay - By * Ax
+        same = ((U >= 0.0) & (V >= 0.0) & (W >= 0.0)) | ((U <= 0.0) & (V <= 0.0) & (W <= 0.0))
+        det = U + V + W
+        ok = same & (det != 0.0)
+        Az, Bz, Cz = S[2] * Akz, S[2] * Bkz, S[2] * Ckz
+        t = (U * Az + V * Bz + W * Cz) / det
+        return ok, t, U, V, W, det
+
+
+def host_ray_triangle(vertices, faces, origins, directions, triangle_id):
+    """The watertight test of rays [Q] against the triangles triangle_id [Q] (one triangle per ray), without a window on t ->
+    (t float64 [Q], barycentrics float64 [Q, 3] = (U, V, W) / det, accepted bool [Q]).  Where the test does not accept (or the id is
+    negative) t is inf and the barycentrics are NaN."""
+    v, f = _as_mesh_arrays(vertices, faces)
+    valid, k, o, S = _ray_frames(origins, directions)
+    tid = np.asarray(triangle_id, dtype=np.int64).reshape(-1)
+    valid = valid & (tid >= 0)
+    corners = v[f[np.where(tid >= 0, tid, 0)]]                   # [Q, 3 corners, 3 axes]
+    a, b, c = (np.take_along_axis(corners[:, i, :], k, axis=1) for i in range(3))
+    ok, t, U, V, W, det = _ray_triangles([o[:, i] for i in range(3)], [S[:, i] for i in range(3)], [a[:, i] for i in range(3)],
+                                         [b[:, i] for i in range(3)], [c[:, i] for i in range(3)])
+    ok = ok & valid
+    with np.errstate(all='ignore'):
+        bary = np.where(ok[:, None], np.stack([U / det, V / det, W / det], axis=1), np.nan)
+    return np.where(ok, t, np.inf), bary, ok
+
+
+def host_ray_cast(vertices, faces, origins, directions, t_min=0.0, t_max=np.inf, any_hit=False):
+    """Rays origins + t directions [Q, 3] against the mesh by brute force over all triangles, in chunks of rays so that memory stays
+    bounded -> (t float64 [Q], triangle_id int64 [Q], barycentrics float64 [Q, 3], hit bool [Q]): the first accepted hit with
+    t_min <= t <= t_max, ties on t to the lowest triangle index; a miss is (inf, -1, NaN, False).  ``any_hit``: only ``hit`` is
+    computed, the other three hold the values of a miss.  See the module docstring for the definition."""
+    v, f = _as_mesh_arrays(vertices, faces)
+    if f.shape[0] == 0:
+        raise ValueError('host_ray_cast: the mesh has no faces')
+    if not t_min <= t_max:
+        raise ValueError('host_ray_cast: t_min=%r > t_max=%r' % (t_min, t_max))
+    valid, k, o, S = _ray_frames(origins, directions)
+    n_q = len(valid)
+    tri = np.full(n_q, -1, dtype=np.int64)
+    hit = np.zeros(n_q, dtype=bool)
+    step = max(1, _PAIRS_PER_CHUNK // f.shape[0])
+    code = k[:, 0] * 3 + k[:, 2]                                 # one value per (kx, ky, kz): rays of one frame share the corner order
+    for frame in np.unique(code[valid]):
+        rows = np.nonzero(valid & (code == frame))[0]
+        kk = k[rows[0]]
+        corners = [[v[f[:, j], kk[i]][None, :] for i in range(3)] for j in range(3)]
+        for q0 in range(0, len(rows), step):
+            r = rows[q0:q0 + step]
+            ok, t, _, _, _, _ = _ray_triangles([o[r, i][:, None] for i in range(3)], [S[r, i][:, None] for i in range(3)], *corners)
+            with np.errstate(invalid='ignore'):
+                ok &= (t >= t_min) & (t <= t_max)
+            hit[r] = ok.any(axis=1)
+            tri[r] = np.where(hit[r], np.argmin(np.where(ok, t, np.inf), axis=1), -1)     # (the first minimum: the lowest index)
+    if any_hit:
+        tri[:] = -1
+    t, bary, _ = host_ray_triangle(v, f, origins, directions, tri)
+    return t, tri, bary, hit
 
 
 def host_face_areas(vertices, faces):
@@ -260,6 +361,33 @@ class MeshIndex(object):
         return hip.closest_point(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over, points,
                                  order=order, n_tests=n_tests)
 
+    def entry_order(self, origins, directions, t_min=0.0):
+        """The permutation that sorts the rays by the cell in which they enter the bounding box (the cell of the origin at t_min when
+        that lies inside; rays that miss the box go by their clamped origin): what home_order is for points.  It only orders the
+        work; the kernel clips and walks the ray itself."""
+        lo = torch.tensor(self.lo, dtype=torch.float64, device=origins.device)
+        hi = torch.tensor(self.hi, dtype=torch.float64, device=origins.device)
+        inv = 1.0 / directions
+        t0, t1 = (lo - origins) * inv, (hi - origins) * inv
+        t_in = torch.nan_to_num(torch.minimum(t0, t1), nan=-float('inf')).max(dim=1).values
+        t_in = torch.nan_to_num(torch.clamp(t_in, min=t_min), nan=0.0, posinf=0.0, neginf=0.0)
+        return self.home_order(origins + t_in[:, None] * directions)
+
+    def ray_cast(self, origins, directions, t_min=0.0, t_max=float('inf'), any_hit=False, n_tests=None, sort=True):
+        """origins / directions float64 [Q, 3] on the index's device -> (t [Q], triangle_id int64 [Q], barycentrics [Q, 3], hit bool [Q]),
+        device tensors: host_ray_cast on the device.  n_tests: an int64 [1] device tensor to which the number of ray-triangle tests is
+        added.  sort=False: the rays are worked on in the order given (a caller that hands over coherent bundles, meshrender's
+        8 x 8 pixel tiles)."""
+        from . import hip
+        if not (torch.is_tensor(origins) and origins.is_cuda and torch.is_tensor(directions) and directions.is_cuda):
+            raise RuntimeError('MeshIndex.ray_cast: origins and directions must be device tensors (host arrays: host_ray_cast)')
+        origins = origins.to(torch.float64).reshape(-1, 3).contiguous()
+        directions = directions.to(torch.float64).reshape(-1, 3).contiguous()
+        order = self.entry_order(origins, directions, t_min) if sort and origins.shape[0] > 64 else None   # (one wave: nothing to order)
+        t, tri, bary, hit = hip.ray_cast(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over,
+                                         origins, directions, t_min, t_max, order=order, any_hit=any_hit, n_tests=n_tests)
+        return t, tri, bary, hit.bool()
+
     def face_areas_cumulative(self):
         v, f = self.vertices, self.faces
         a = v[f[:, 0]]
@@ -287,7 +415,7 @@ class MeshIndex(object):
 
 
 class _HostMesh(object):
-    """The host twin of MeshIndex (same three methods), so that the Chamfer functions below are written once."""
+    """The host twin of MeshIndex (same methods), so that the Chamfer functions below and meshrender are written once."""
 
     def __init__(self, vertices, faces, name='mesh'):
         self.vertices, self.faces = _as_mesh_arrays(vertices, faces)
@@ -299,6 +427,10 @@ class _HostMesh(object):
 
     def closest_point(self, points):
         return host_closest_point(self.vertices, self.faces, points)
+
+    def ray_cast(self, origins, directions, t_min=0.0, t_max=np.inf, any_hit=False, n_tests=None):
+        to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x
+        return host_ray_cast(self.vertices, self.faces, to_np(origins), to_np(directions), t_min, t_max, any_hit)
 
 
 def _prepare(mesh, device, name):
