@@ -244,7 +244,7 @@ typedef struct {
 } PsnMlpLayer;
 
 typedef struct {
-    int n_layers;
+    int n_layers; /* hidden layers + the final layer (n_out > 0); a final layer alone (n_layers == 1, n_out > 0) is refused */
     int n_out;    /* real outputs of the final layer (<= 32; <= 64 in a 256-wide chain launch: final n_mt = 2, two weight stages) */
     int out_act;  /* PSN_OUT_* */
     int in_kt_a;  /* K tiles (of 32 floats) per row of feature table A (1..4) */

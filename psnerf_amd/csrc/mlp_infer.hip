@@ -651,8 +651,10 @@ __global__ __launch_bounds__(256, 2) void mlp_infer_kernel(InferArgs g) {
         if (g.init_b != nullptr && g.tb_lds != 0 && g.n_bias + g.d.init_stride <= PSN_MLP_MAX_LAYERS * 256) {
             const int64_t r_first = blk_ * (kWaves * 16), r_last_ = r_first + kWaves * 16 - 1;
             const int64_t r_last = r_last_ < n_rows_eff ? r_last_ : n_rows_eff - 1;
-            const int64_t ib0 = (r_first / g.b_div) % g.b_mod;
-            if (ib0 == (r_last / g.b_div) % g.b_mod) {  // (uniform over the workgroup)
+            // (the same QUOTIENT, not the same table row: with b_div * b_mod < 64 -- point-major rows, b_div = 1 -- the first and the
+            //  last row of a block can wrap around to one B row while the rows between them visit all the others)
+            if (r_first / g.b_div == r_last / g.b_div) {  // (uniform over the workgroup)
+                const int64_t ib0 = (r_first / g.b_div) % g.b_mod;
                 float* dst = bias_lds + PSN_MLP_MAX_LAYERS * 256 - g.d.init_stride;
                 const float* src = g.init_b + ib0 * (int64_t)g.d.init_stride;
                 for (int i = tid; i < g.d.init_stride; i += kWaves * 64) dst[i] = src[i];
@@ -1362,7 +1364,10 @@ static int mlp_infer_impl(const PsnMlpDesc* desc, const float* packed_w, const f
     PSN_CHECK_ARG((((uintptr_t)tab_a | (uintptr_t)tab_b | (uintptr_t)packed_w | (uintptr_t)packed_b) & 15) == 0,
                   "mlp_infer: buffers must be 16-byte aligned");
     // hidden width: 256 (8 output tiles of 32) or 128 (4), the same for every hidden layer of the network
-    const int hid = (d.n_out > 0 && d.n_layers == 1) ? 8 : d.layers[0].n_mt;
+    // A network that is only a final layer is refused: the barrier that publishes bias_lds sits in the hidden-layer loop, so with no
+    // hidden layer the final layer would read its bias from LDS before any barrier (nothing in the project launches that shape).
+    PSN_CHECK_ARG(d.n_out == 0 || d.n_layers >= 2, "mlp_infer: a final layer needs at least one hidden layer in front of it (n_layers=%d)", d.n_layers);
+    const int hid = d.layers[0].n_mt;
     PSN_CHECK_ARG(hid == 8 || hid == 4 || hid == 2, "mlp_infer: hidden layers must be 256, 128 or 64 wide (n_mt = 8, 4, 2), got n_mt=%d", hid);
     const int width = hid * 32;
     for (int l = 0; l < d.n_layers; ++l) {

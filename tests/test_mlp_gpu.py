@@ -1,0 +1,428 @@
+"""The fused MLP engine (csrc/mlp_infer.hip) against float64, launch path by launch path, on the cases of tests/mlp_cases.py
+(whose coverage of the dispatcher tests/test_mlp_cpu.py asserts without a GPU): the packers bit for bit against the stage order of
+the header comment, the lean engine (plain, index maps, dumps and sign bits, padded row sets, both block orders), the chain-only
+features (rank-k init, dump tile masks, the 33..64-output final layer, the single-dump programs, masks as tensors and as sign
+bits, initial activations), the encoding prologue (psn_mlp_infer_pe, its indirect form, psn_march_sweep) and the argument checks.
+
+Bound: helpers.assert_vs_truth, rtol 1e-5, atol 'max', per tensor, with the float32 CPU definition as the reference arithmetic;
+test_mlp_cpu.py shows that this reference never passes half the bound, so the kernel is allowed no element beyond it.  Every
+output and dump buffer starts as NaNs of a fixed bit pattern inside a larger buffer: what the launch must not write keeps its bits.
+
+Measured worst r_hip per instantiation (units of the bound) on an MI355X:
+    instantiation          r_hip   r_ref   worst tensor
+    chain/16               0.120   0.072   F-tiles-w256-00f0 second1
+    chain/16/froma         0.043   0.033   F-softplus_bwd_a out
+    chain/16/trim          0.043   0.023   F-chain-trim dump1
+    chain/16/trim/froma    0.041   0.028   F-froma-trim out
+    chain/4                0.017   0.022   F-act_init-w64 dump1
+    chain/8                0.082   0.045   F-tiles-w128-ffff second1
+    lean/16                0.088   0.057   C-pair-P128-G3-init out
+    lean/16/src2/trim      0.104   0.038   G-rows129 out
+    lean/16/src3/trim      0.117   0.058   G-sweep-rays3-steps192 occ
+    lean/16/trim           0.076   0.037   B-trim217 out
+    lean/4                 0.134   0.021   B-rows1-w64 out
+    lean/8                 0.711   0.133   B-rows1-w128 out   (one row, one output: the bound is purely relative there)
+212 tests, 3.5 s of wall time for the module.
+
+Finding of this suite (fixed in csrc/mlp_infer.hip, cases C-pointmajor-rows and C-pointmajor-rows-G7 kept): the lean engine took the
+B-side init row through LDS whenever the first and the last row of a workgroup mapped to the same B-table row.  With b_div * b_mod
+< 64 (point-major rows, b_div = 1) the index wraps inside the block -- 63 % 3 == 63 % 7 == 0 -- and all 64 rows were given the
+init row of the first one (168 of 300 outputs wrong, up to 6e4 x the bound).  The test is now the same quotient row / b_div.
+"""
+import numpy as np
+import pytest
+import torch
+
+from tests import mlp_cases as mc
+from tests.helpers import assert_vs_truth
+
+pytestmark = pytest.mark.gpu
+_WORST = {}      # instantiation -> (worst r_hip, r_ref there, case and tensor)
+NAN_BITS = 0x7FC12345
+G_OUT, G_DUMP = mc.GUARD, 130   # guard rows (dumps: more than the largest save_row0, a row index taken without it lands there)
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _report():
+    yield
+    if _WORST:
+        print('\n==== fused MLP engine vs float64: worst r_hip per instantiation (r_ref in the same tensor), in units of the bound ====')
+        for name, (rh, rr, where) in sorted(_WORST.items()):
+            print('%-22s r_hip %6.3f  r_ref %6.3f  (%s)' % (name, rh, rr, where))
+
+
+@pytest.fixture(scope='module')
+def mods(cuda):
+    from psnerf_amd import hip, fused
+    return hip, fused
+
+
+def nan_buffer(rows, cols, cuda, guard):
+    """(whole, view): ``rows`` x ``cols`` floats of NAN_BITS with ``guard`` rows of the same in front and behind."""
+    whole = torch.full((rows + 2 * guard, cols), NAN_BITS, dtype=torch.int32, device=cuda).view(torch.float32)
+    return whole, whole[guard:guard + rows]
+
+
+def untouched(t):
+    return bool((t.view(torch.int32) == NAN_BITS).all())
+
+
+def guards_intact(whole, rows, guard):
+    return untouched(whole[:guard]) and untouched(whole[guard + rows:])
+
+
+def check(c, path, name, got, truth, ref):
+    got = got.detach().cpu().numpy()
+    assert got.shape == tuple(truth.shape), '%s %s: shape %s vs %s' % (c['id'], name, got.shape, tuple(truth.shape))
+    rh, rr = assert_vs_truth('%s %s' % (c['id'], name), got, ref.numpy(), truth.numpy(), mc.RTOL, 'max')
+    print('%s %-10s r_hip %.3f r_ref %.3f' % (c['id'], name, rh, rr))
+    if rh > _WORST.get(path, (-1.0,))[0]:
+        _WORST[path] = (rh, rr, '%s %s' % (c['id'], name))
+
+
+def pack_net(net, mods, cuda):
+    hip, fused = mods
+    names = dict(none='NONE', relu='RELU', softplus='SOFTPLUS100')
+    code = lambda a: getattr(hip, 'ACT_' + names.get(a, a.upper()))
+    spec = net.pack_spec(lambda t: t.to(cuda), code, fused.DIRECT_INIT)
+    pk = fused.pack_layers(spec, net.ka, net.kb, net.n_out, getattr(hip, 'OUT_' + net.out_act.upper()), cuda,
+                           has_final=net.n_out > 0, width=net.width)
+    for l, L in enumerate(net.layers):
+        assert pk.desc.layers[l].act == mc.ACT[L['act']]
+    assert [(pk.desc.layers[l].n_kt_in, pk.desc.layers[l].n_kt_act, pk.desc.layers[l].init_off >= 0)
+            for l in range(len(net.layers))] == mc.layer_shape(net)
+    return pk
+
+
+# --------------------------------------------------------------------------- A: the packers
+def _pack_views(items, cuda):
+    views = []
+    for it in items:
+        store, view = mc.pack_matrix(it)
+        v = store.to(cuda)[:, it['col0']:it['col0'] + view.shape[1]]
+        assert v.stride(0) == view.shape[1] + it['ldw_extra'] and v.stride(1) == 1
+        views.append((v, mc.pack_reference(view.numpy(), it['n_mt'], it['k_tiles'], it['transpose'])))
+    return views
+
+
+def _same_bits(got, ref):
+    return np.array_equal(got.cpu().numpy().view(np.int32), ref.view(np.int32))
+
+
+@pytest.mark.parametrize('item', mc.PACK_ITEMS, ids=mc.case_id)
+def test_pack_layer_equals_stage_order(mods, cuda, item):
+    hip, _ = mods
+    (v, ref), = _pack_views([item], cuda)
+    size = item['n_mt'] * item['k_tiles'] * 1024
+    whole, dst = nan_buffer(1, size, cuda, 1)
+    hip.mlp_pack_layer(v, item['n_mt'], item['k_tiles'], dst[0], transpose=item['transpose'])
+    assert _same_bits(dst[0], ref) and guards_intact(whole, 1, 1)
+    # the grouped packer on the same block, alone
+    whole2, dst2 = nan_buffer(1, size, cuda, 1)
+    hip.mlp_pack_layers([(v, item['transpose'], item['n_mt'], item['k_tiles'], dst2[0])])
+    assert _same_bits(dst2[0], ref) and guards_intact(whole2, 1, 1)
+
+
+@pytest.mark.parametrize('n_items', mc.PACK_GROUP_SIZES)
+def test_pack_layers_groups(mods, cuda, n_items):
+    """1, 24 (one full launch) and 25 items (a second launch): every block equals the single packer's reference, the floats
+    between the blocks keep their bits."""
+    hip, _ = mods
+    items = [mc.PACK_ITEMS[i % len(mc.PACK_ITEMS)] for i in range(n_items)]
+    views = _pack_views(items, cuda)
+    gap = 4
+    sizes = [it['n_mt'] * it['k_tiles'] * 1024 for it in items]
+    whole = torch.full((sum(sizes) + gap * (n_items + 1),), NAN_BITS, dtype=torch.int32, device=cuda).view(torch.float32)
+    plan, offs, o = [], [], gap
+    for it, (v, _), sz in zip(items, views, sizes):
+        plan.append((v, it['transpose'], it['n_mt'], it['k_tiles'], whole[o:o + sz]))
+        offs.append(o)
+        o += sz + gap
+    hip.mlp_pack_layers(plan)
+    for it, (_, ref), sz, o in zip(items, views, sizes, offs):
+        assert _same_bits(whole[o:o + sz], ref), it['id']
+        assert untouched(whole[o - gap:o]) and untouched(whole[o + sz:o + sz + gap]), it['id']
+
+
+# --------------------------------------------------------------------------- B - E: the lean engine
+def run_lean(c, net, pk, mods, cuda, order=None, live=None, dumps=True, res=None):
+    hip, _ = mods
+    n = c['n']
+    a_div, a_mod, b_div, b_mod = net.maps
+    ta = net.tab_a.to(cuda)
+    tb = None if net.tab_b is None else net.tab_b.to(cuda)
+    res = {} if res is None else res   # (the caller's dict: the buffers stay inspectable when the launch is refused)
+    res['bufs'] = []
+    whole, out = nan_buffer(n, net.n_out, cuda, G_OUT)
+    res['bufs'].append((whole, n, G_OUT))
+    row0 = c['save_row0'] if c['save_row0'] is not None else 0
+    save = bits = None
+    if dumps and c['save'] is not None:
+        save, bits = [], []
+        want_bits = c['bits'] if isinstance(c['bits'], tuple) else (bool(c['bits']),) * len(c['save'])
+        for l, on in enumerate(c['save']):
+            if not on:
+                save.append(None)
+                bits.append(None)
+                continue
+            w_, d_ = nan_buffer(n - row0, net.width, cuda, G_DUMP)
+            res['bufs'].append((w_, n - row0, G_DUMP))
+            save.append(d_)
+            bits.append(torch.full((n - row0, 4), -1, dtype=torch.int64, device=cuda) if want_bits[l] else None)
+        if not any(b is not None for b in bits):
+            bits = None
+    kw = {}
+    if live is not None:
+        kw['live'] = (torch.tensor([float(live)], device=cuda), c['period'])
+    call = lambda: pk(ta, n, a_div=a_div, a_mod=a_mod, tab_b=tb, b_div=b_div, b_mod=b_mod, out=out, save=save,
+                      save_row0=row0, save_bits=bits, **kw)
+    if order is None:
+        call()
+    else:
+        with hip.block_order(order):
+            call()
+    res.update(out=out, save=save, bits=bits)
+    for w_, rows, g_ in res['bufs']:
+        assert guards_intact(w_, rows, g_), '%s: a guard row was written' % c['id']
+    return res
+
+
+def equal_results(a, b):
+    ok = torch.equal(a['out'].view(torch.int32), b['out'].view(torch.int32))
+    for x, y in zip(a['save'] or [], b['save'] or []):
+        ok = ok and (x is None or torch.equal(x.view(torch.int32), y.view(torch.int32)))
+    for x, y in zip(a['bits'] or [], b['bits'] or []):
+        ok = ok and (x is None or torch.equal(x, y))
+    return ok
+
+
+@pytest.mark.parametrize('c', mc.LEAN_CASES, ids=mc.case_id)
+def test_lean_engine_vs_float64(mods, cuda, c):
+    net, t64, t32 = mc.reference(c)
+    pk = pack_net(net, mods, cuda)
+    path = mc.dispatch(c, net)['name']
+    first = None
+    for order in c['orders']:
+        r = run_lean(c, net, pk, mods, cuda, order=order)
+        if first is not None:
+            assert equal_results(r, first), '%s: block order %s changes the result' % (c['id'], order)
+            continue
+        first = r
+        check(c, path, 'out', r['out'], t64['out'], t32['out'])
+        row0 = c['save_row0'] or 0
+        for l, d in enumerate(r['save'] or []):
+            if d is None:
+                continue
+            check(c, path, 'dump%d' % l, d, t64['d1'][l][row0:], t32['d1'][l][row0:])
+            if r['bits'] is not None and r['bits'][l] is not None:
+                # the words of the header's formula, applied to the kernel's own dump
+                assert np.array_equal(r['bits'][l].cpu().numpy(), mc.sign_words(d.cpu().numpy())), '%s: sign bits of layer %d' % (c['id'], l)
+        if c['save'] is not None:
+            # the rows ride along: the launch without dumps gives the same outputs bit for bit
+            plain = run_lean(c, net, pk, mods, cuda, order=order, dumps=False)
+            assert torch.equal(plain['out'].view(torch.int32), r['out'].view(torch.int32))
+
+
+@pytest.mark.parametrize('c', mc.E_CASES, ids=mc.case_id)
+def test_padded_row_sets(mods, cuda, c):
+    """psn_mlp_infer_padded: the all-padding blocks (stated from live and period) are exact zeros, every other row and every dump
+    equals the plain launch bit for bit, in both block orders; the plain launch meets the float64 bound."""
+    net, t64, t32 = mc.reference(c)
+    pk = pack_net(net, mods, cuda)
+    path = mc.dispatch(c, net)['name']
+    plain = run_lean(c, net, pk, mods, cuda, order='row')
+    check(c, path, 'out', plain['out'], t64['out'], t32['out'])
+    row0 = c['save_row0']
+    for l, d in enumerate(plain['save'] or []):
+        check(c, path, 'dump%d' % l, d, t64['d1'][l][row0:], t32['d1'][l][row0:])
+    for order in c['orders']:
+        assert equal_results(run_lean(c, net, pk, mods, cuda, order=order), plain)
+        for live in c['live']:
+            r = run_lean(c, net, pk, mods, cuda, order=order, live=live)
+            dead = torch.from_numpy(mc.dead_rows(c, live)).to(cuda)
+            what = '%s order=%s live=%d' % (c['id'], order, live)
+            assert bool((r['out'][dead].view(torch.int32) == 0).all()), what + ': a dead block is not exact zeros'
+            assert torch.equal(r['out'][~dead].view(torch.int32), plain['out'][~dead].view(torch.int32)), what + ': live rows differ'
+            for x, y in zip(r['save'] or [], plain['save'] or []):
+                assert torch.equal(x.view(torch.int32), y.view(torch.int32)), what + ': dumps differ'
+
+
+# --------------------------------------------------------------------------- F: chain-only features
+def run_chain(c, net, pk, mods, cuda, masks=None, res=None):
+    hip, _ = mods
+    n, W, nl = c['n'], net.width, len(net.layers)
+    nh = net.n_hidden
+    dv = lambda t: None if t is None else t.to(cuda)
+    res = {} if res is None else res   # (the caller's dict: the buffers stay inspectable when the launch is refused)
+    res['bufs'] = []
+    out = None
+    if net.n_out > 0:
+        whole, out = nan_buffer(n, net.n_out, cuda, G_OUT)
+        res['bufs'].append((whole, n, G_OUT))
+    save, save2 = [], []
+    for l in range(nl):
+        L = net.layers[l]
+        hidden = l < nh
+        for lst, on in ((save, hidden), (save2, hidden and L['act'] in mc.SECOND)):
+            if on:
+                w_, d_ = nan_buffer(n, W, cuda, G_OUT)
+                res['bufs'].append((w_, n, G_OUT))
+                lst.append(d_)
+            else:
+                lst.append(None)
+    save = save[:nh]
+    mask = [dv(masks[l]) if (masks is not None and l in masks) else dv(net.mask.get(l)) for l in range(nl)]
+    aux2 = [dv(net.aux2.get(l)) for l in range(nl)]
+    kw = {}
+    if c['tile_masks'] is not None:
+        kw['save_tiles'], kw['save2_tiles'] = [c['tile_masks'][0]] * nh, [c['tile_masks'][1]] * nh
+    elif c['force_chain']:
+        kw['save_tiles'] = []
+    if net.rk is not None:
+        kw['rank_init'] = (dv(net.rk[0]).contiguous(), dv(net.rk[1]).contiguous())
+    hip.mlp_infer(pk.desc, pk.w, pk.b, dv(net.tab_a), 1, n, None, 1, 1, n, out=out, init_a=dv(net.init_direct), save=save, save_row0=0,
+                  mask=mask if any(m is not None for m in mask) else None, aux2=aux2 if any(m is not None for m in aux2) else None,
+                  save2=save2 if any(m is not None for m in save2) else None, act_init=dv(net.act_init),
+                  act_init_rows=net.act_init_rows, **kw)
+    for w_, rows, g_ in res['bufs']:
+        assert guards_intact(w_, rows, g_), '%s: a guard row was written' % c['id']
+    res.update(out=out, save=save, save2=save2)
+    return res
+
+
+def tile_columns(mask, W):
+    cols = np.zeros(W, dtype=bool)
+    for mt in range(W // 16):
+        if (mask >> mt) & 1:
+            cols[16 * mt:16 * mt + 16] = True
+    return cols
+
+
+@pytest.mark.parametrize('c', mc.F_CASES, ids=mc.case_id)
+def test_chain_features_vs_float64(mods, cuda, c):
+    net, t64, t32 = mc.reference(c)
+    masks = None
+    if c['bits_from_lean']:
+        # the masks of a RELU_BITS chain: the sign-bit words a lean forward of the same width left behind; the definition reads
+        # that launch's dumps
+        src = mc.lean(c['id'] + '-forward', n=c['n'], width=c['width'], depth=2, skip=None, save_row0=0, save=(True, True), bits=True, n_out=1)
+        snet = mc.build(src)
+        fwd = run_lean(src, snet, pack_net(snet, mods, cuda), mods, cuda)
+        net = mc.build(c)
+        net.mask = {l: fwd['save'][l].cpu() for l in range(2)}
+        masks = {l: fwd['bits'][l] for l in range(2)}
+        t64, t32 = mc.evaluate(net, torch.float64), mc.evaluate(net, torch.float32)
+    pk = pack_net(net, mods, cuda)
+    path = mc.dispatch(c, net)['name']
+    r = run_chain(c, net, pk, mods, cuda, masks=masks)
+    W = net.width
+    m1, m2 = c['tile_masks'] if c['tile_masks'] is not None else (0xFFFF, 0xFFFF)
+    want = dict(mc.checked_tensors(c, t64))
+    ref = dict(mc.checked_tensors(c, t32))
+    if net.n_out > 0:
+        check(c, path, 'out', r['out'], want['out'], ref['out'])
+    for l in range(net.n_hidden):
+        for key, buf, m in (('dump%d' % l, r['save'][l], m1), ('second%d' % l, r['save2'][l], m2)):
+            if buf is None:
+                continue
+            sel = torch.from_numpy(tile_columns(m, W))
+            dsel = sel.to(cuda)
+            assert untouched(buf[:, ~dsel]), '%s %s: an unselected dump tile was written' % (c['id'], key)
+            check(c, path, key, buf[:, dsel], want[key][:, sel], ref[key][:, sel])
+
+
+# --------------------------------------------------------------------------- G: the encoding prologue
+@pytest.mark.parametrize('c', mc.G_CASES, ids=mc.case_id)
+def test_encoding_prologue_vs_float64(mods, cuda, c):
+    hip, _ = mods
+    net, t64, t32 = mc.reference(c)
+    pk = pack_net(net, mods, cuda)
+    path = mc.dispatch(c, net)['name']
+    pts = net.points.to(cuda).contiguous()
+    if c['src'] == 3:
+        s = net.sweep
+        occ, skip = hip.march_sweep(pk.desc, pk.w, pk.b, s['origin'].to(cuda), s['direction'].to(cuda), s['far'].to(cuda), s['u'].to(cuda),
+                                    s['omu'].to(cuda), s['near'], c['steps'], 0.5, c['octaves'], c['pe_scale'], early_exit=False)
+        assert skip is None and occ.shape == (c['rays'], c['steps'])
+        check(c, path, 'occ', occ.reshape(-1, 1), t64['out'], t32['out'])
+        # the same points through the table-free point launch: bit-identical
+        direct = pk.on_points(pts, c['octaves'], c['pe_scale'])
+        assert torch.equal(direct.view(torch.int32), occ.reshape(-1, 1).view(torch.int32))
+        return
+    Q = pts.shape[0]
+    whole, out = nan_buffer(Q, net.n_out, cuda, G_OUT)
+    pk.on_points(pts, c['octaves'], c['pe_scale'], out=out)
+    assert guards_intact(whole, Q, G_OUT)
+    if c['count'] is None:
+        check(c, path, 'out', out, t64['out'], t32['out'])
+        return
+    cnt = c['count']
+    count = torch.tensor([cnt], dtype=torch.int64, device=cuda)
+    if not c['scatter']:
+        w2, o2 = nan_buffer(Q, net.n_out, cuda, G_OUT)
+        pk.on_points(pts, c['octaves'], c['pe_scale'], out=o2, n_rows_dev=count)
+        assert guards_intact(w2, Q, G_OUT) and untouched(o2[cnt:]), '%s: a row behind the count was written' % c['id']
+        got = o2[:cnt]
+    else:
+        perm = torch.randperm(mc.SCATTER_ROWS, generator=torch.Generator().manual_seed(cnt))[:Q].to(cuda)
+        w2, o2 = nan_buffer(mc.SCATTER_ROWS, net.n_out, cuda, G_OUT)
+        pk.on_points(pts, c['octaves'], c['pe_scale'], out=o2, n_rows_dev=count, out_rows=perm)
+        named = torch.zeros(mc.SCATTER_ROWS, dtype=torch.bool, device=cuda)
+        named[perm[:cnt]] = True
+        assert guards_intact(w2, mc.SCATTER_ROWS, G_OUT) and untouched(o2[~named]), '%s: an entry no out_rows names was written' % c['id']
+        got = o2[perm[:cnt]]
+    assert torch.equal(got.view(torch.int32), out[:cnt].view(torch.int32)), '%s: differs from the plain launch' % c['id']
+    check(c, path, 'out', got, t64['out'][:cnt], t32['out'][:cnt])
+
+
+# --------------------------------------------------------------------------- argument checks
+@pytest.mark.parametrize('c', mc.ARG_CASES, ids=mc.case_id)
+def test_argument_checks_refuse_and_launch_nothing(mods, cuda, c):
+    """PSN_E_ARG with the message of the very check the case is built for; no output or dump buffer is written."""
+    import re
+    net = mc.build(c)
+    pk = pack_net(net, mods, cuda)
+    res = {}
+    with pytest.raises(RuntimeError, match=re.escape(c['refusal'])):
+        if c['kind'] == 'lean':
+            run_lean(c, net, pk, mods, cuda, res=res)
+        else:
+            run_chain(c, net, pk, mods, cuda, res=res)
+    torch.cuda.synchronize()
+    assert res['bufs'] and all(untouched(w_) for w_, _, _ in res['bufs'])
+
+
+def test_live_count_on_a_chain_launch_is_refused_by_the_library(mods, cuda):
+    """psn_mlp_infer_padded takes no chain operands, so a chain launch reaches it only through a program that needs none (HEAD):
+    called through the C ABI directly, the `!chain` clause of mlp_infer_impl answers PSN_E_ARG."""
+    import ctypes
+    hip, _ = mods
+    n, row0 = 128, 64
+    c = mc.chain('ARG-live-on-chain-abi', n=n, prog=('relu', 'head'), n_out=3)
+    net = mc.build(c)
+    pk = pack_net(net, mods, cuda)
+    whole, out = nan_buffer(n, 3, cuda, G_OUT)
+    dumps = [nan_buffer(n - row0, 256, cuda, G_OUT) for _ in range(2)]
+    save = (ctypes.c_void_p * 2)(*[d.data_ptr() for _, d in dumps])
+    ta, live = net.tab_a.to(cuda), torch.tensor([3.0], device=cuda)
+    rc = hip._lib.psn_mlp_infer_padded(ctypes.byref(pk.desc), pk.w.data_ptr(), pk.b.data_ptr(), ta.data_ptr(), 1, n, None, 1, 1, None, None,
+                                       save, row0, n, out.data_ptr(), live.data_ptr(), 64, hip._stream())
+    assert rc != 0
+    with pytest.raises(RuntimeError, match='mlp_infer_padded: needs the lean variant'):
+        hip._check(rc, 'mlp_infer_padded')
+    torch.cuda.synchronize()
+    assert untouched(whole) and all(untouched(w_) for w_, _ in dumps)
+
+
+def test_live_count_on_a_chain_launch_is_refused_by_the_wrapper(mods, cuda):
+    """hip.mlp_infer refuses the same before any C call (the library's own check: the test above)."""
+    hip, _ = mods
+    c = mc.chain('ARG-live-on-chain', n=128, prog=('relu_mask', 'none'), n_out=3)
+    net = mc.build(c)
+    pk = pack_net(net, mods, cuda)
+    whole, out = nan_buffer(128, 3, cuda, G_OUT)
+    with pytest.raises(RuntimeError, match='live count is for plain forward launches'):
+        hip.mlp_infer(pk.desc, pk.w, pk.b, net.tab_a.to(cuda), 1, 128, None, 1, 1, 128, out=out, mask=[net.mask[0].to(cuda), None, None],
+                      save_row0=64, live=(torch.tensor([3.0], device=cuda), 64))
+    torch.cuda.synchronize()
+    assert untouched(whole)
