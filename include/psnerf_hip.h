@@ -927,6 +927,59 @@ int psn_cc_compact(const double* vertices, const void* normals, int normal_bytes
                    int64_t* out_faces, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Mesh simplification: quadric vertex clustering on a uniform grid (csrc/meshsimplify.hip; the numpy definition, which these
+ * kernels repeat operation for operation in float64, is psnerf_amd/meshsimplify.py:host_*).  The reference has no such step;
+ * the extractor's lineage had one behind a native library (Occupancy Networks' simplify_nfaces).  The sorts and scans between
+ * the kernels are the caller's (torch); compaction is psn_cc_compact on (positions, g).
+ *   vertices float64 [V, 3], finite;  faces int64 [F, 3];  0 <= V <= PSN_CC_MAX_VERTICES, 0 <= F <= PSN_VC_MAX_FACES.
+ *   grid     origin (ox, oy, oz) = the per-axis minimum of the vertices, cell edge h > 0, dims (dx, dy, dz) =
+ *            floor(extent / h) + 1 per axis, each 1 .. PSN_VC_MAX_RESOLUTION + 1; computed by the caller on the host.
+ *   status   int32 [1] on the device, bits PSN_VC_E_*, zeroed by the caller; the caller reads it with its counts and raises.
+ *
+ * psn_vc_cell_keys: keys int64 [V] = (c_z dy + c_y) dx + c_x with c_a = min(max(floor((v_a - origin_a) / h), 0), dims_a - 1).
+ *   The caller's stable sort of the keys gives the clusters (the occupied cells ascending by key; cluster[v] = the rank of v's
+ *   cell) and each cluster's vertex run in ascending vertex index.
+ * psn_vc_face_keys: cluster int64 [V] -> g int64 [F, 3] = the faces re-indexed; face_keys int64 [F] = -1 for a face that names a
+ *   cluster twice, else (g0' 2^21 + g1') 2^21 + g2' of the face rotated so that its smallest id comes first, orientation kept
+ *   (equal keys are duplicates; the same three clusters in opposite orientation are not); corner_keys int64 [3 F] (or null:
+ *   not written) = cluster * 3 F + 3 f + k per corner k, which sorted give every cluster its run of (face, corner) pairs in
+ *   ascending order.  A face with an index outside 0 .. V - 1 is SKIPPED (key -1, g = 0, corner keys behind every run) and
+ *   PSN_VC_E_INDEX is set; a cluster id outside 0 .. PSN_VC_MAX_CLUSTERS - 1 likewise with PSN_VC_E_CLUSTER (three ids
+ *   share one 63-bit key: more clusters are refused by the caller).
+ * psn_vc_solve: per cluster c (a wave each) -> positions float64 [C, 3], clamped bytes [C].  vertex_order int64 [V] = the
+ *   stable sort's permutation, cell_key_sorted int64 [V] its keys, vertex_start int64 [C + 1] the run bounds in them;
+ *   corner_sorted int64 [3 F] = the sorted corner keys, corner_start int64 [C + 1] their run bounds.
+ *     x0 = (the sum of the run's vertices, one after the other) / count
+ *     per (face, corner) of the run, in order, n = (b - a) x (c - a) unnormalised:  A += n n^T (six entries),
+ *       r += n ((n_x (a_x - x0_x) + n_y (a_y - x0_y)) + n_z (a_z - x0_z)),  a = the face's first vertex
+ *     t = (A00 + A11) + A22;  t == 0: x = x0;  else (A + regularisation t I) delta = r by the LDL^T sequence written out in
+ *       meshsimplify.py, x = x0 + delta;  x clamped per axis into its cell [origin + c h, origin + (c + 1) h]; clamped[c] = 1
+ *       where that moved a coordinate.
+ *   Additions happen in exactly that order (lanes share the loads and the products, one lane owns each accumulator); no
+ *   floating-point atomics; two runs give the same bits, and they are numpy's.
+ * psn_vc_face_flags: face_keep bytes [F] (not degenerate, first of its key in face order) -> vertex_keep bytes [C] (zeroed
+ *   here) = 1 for every cluster a kept face names; flipped bytes [F] = 1 for a kept face whose new normal
+ *   (x[g1] - x[g0]) x (x[g2] - x[g0]) has a strictly negative dot product with its old one.
+ * Errors: PSN_E_ARG for null pointers and bad arguments; PSN_E_UNSUPPORTED for sizes beyond the limits; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_VC_MAX_RESOLUTION 4096
+#define PSN_VC_MAX_CLUSTERS 2097151
+#define PSN_VC_MAX_FACES 274877906944LL
+#define PSN_VC_E_INDEX 1
+#define PSN_VC_E_CLUSTER 2
+int psn_vc_cell_keys(const double* vertices, int64_t n_vertices, double ox, double oy, double oz, double h, int dx, int dy, int dz,
+                     int64_t* keys, void* stream);
+int psn_vc_face_keys(const int64_t* faces, int64_t n_faces, int64_t n_vertices, const int64_t* cluster, int64_t* corner_keys,
+                     int64_t* face_keys, int64_t* g, int* status, void* stream);
+int psn_vc_solve(const double* vertices, const int64_t* faces, int64_t n_faces, int64_t n_vertices, const int64_t* vertex_order,
+                 const int64_t* vertex_start, const int64_t* cell_key_sorted, const int64_t* corner_sorted,
+                 const int64_t* corner_start, int64_t n_clusters, double ox, double oy, double oz, double h, int dx, int dy, int dz,
+                 double regularisation, double* positions, unsigned char* clamped, void* stream);
+int psn_vc_face_flags(const double* vertices, const int64_t* faces, int64_t n_faces, int64_t n_vertices, const int64_t* g,
+                      const double* positions, int64_t n_clusters, const unsigned char* face_keep, unsigned char* vertex_keep,
+                      unsigned char* flipped, void* stream);
+
+/* ------------------------------------------------------------------------
  * Image evaluation: what the reference's evaluation.py computes per image pair and per view (csrc/imgmetrics.hip; the float64
  * numpy definition is psnerf_amd/imgmetrics.py:host_*).  float64 arithmetic, no floating-point atomics: each call writes one row
  * of partial sums per tile / chunk into ``partial`` (psn_img_workspace doubles; every row written on every call) and a second,

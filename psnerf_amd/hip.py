@@ -1626,6 +1626,73 @@ def cc_compact(vertices, faces, normals, face_keep, vertex_keep, face_pos, verte
     return out_v, out_f, out_n
 
 
+# --------------------------------------------------------------------------- mesh simplification (csrc/meshsimplify.hip)
+def _vc_grid(grid):
+    """(origin, h, dims) of meshsimplify.make_grid -> the seven scalars of the C ABI."""
+    origin, h, dims = grid
+    return float(origin[0]), float(origin[1]), float(origin[2]), float(h), int(dims[0]), int(dims[1]), int(dims[2])
+
+
+def vc_cell_keys(vertices, grid):
+    """psn_vc_cell_keys: vertices float64 [V, 3] -> keys int64 [V], the key of each vertex's grid cell."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError('vc_cell_keys: vertices [V, 3] expected, got %s' % (tuple(vertices.shape),))
+    n_v = vertices.shape[0]
+    keys = torch.empty(n_v, dtype=torch.int64, device=vertices.device)
+    with _Prof('vc_cell_keys', 32 * n_v):
+        _check(_lib.psn_vc_cell_keys(_tptr(vertices, 'vertices', torch.float64), n_v, *_vc_grid(grid), keys.data_ptr(), _stream()), 'vc_cell_keys')
+    return keys
+
+
+def vc_face_keys(faces, cluster, status, want_corners=True):
+    """psn_vc_face_keys: faces int64 [F, 3], cluster int64 [V] -> (corner_keys int64 [3 F] or None, face_keys int64 [F], g int64 [F, 3]).
+    status (int32 [1] on the device, zeroed by the caller) collects VC_E_* bits; the caller reads it with its counts."""
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError('vc_face_keys: faces [F, 3] expected, got %s' % (tuple(faces.shape),))
+    n_f, n_v = faces.shape[0], cluster.numel()
+    assert status.numel() == 1
+    dev = faces.device
+    corner_keys = torch.empty(3 * n_f, dtype=torch.int64, device=dev) if want_corners else None
+    face_keys = torch.empty(n_f, dtype=torch.int64, device=dev)
+    g = torch.empty(n_f, 3, dtype=torch.int64, device=dev)
+    with _Prof('vc_face_keys', (24 + 24 + 8 + 24 + (24 if want_corners else 0)) * n_f):
+        _check(_lib.psn_vc_face_keys(_tptr(faces, 'faces', torch.int64), n_f, n_v, _tptr(cluster, 'cluster', torch.int64),
+                                     None if corner_keys is None else corner_keys.data_ptr(), face_keys.data_ptr(), g.data_ptr(),
+                                     _tptr(status, 'status', torch.int32), _stream()), 'vc_face_keys')
+    return corner_keys, face_keys, g
+
+
+def vc_solve(vertices, faces, vertex_order, vertex_start, cell_key_sorted, corner_sorted, corner_start, n_clusters, grid, regularisation):
+    """psn_vc_solve -> (positions float64 [C, 3], clamped uint8 [C]): per cluster the centroid over its vertex run, the quadric over its
+    corner run, the solve and the clamp, every sum in the definition's order."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    n_v, n_f, n_c = vertices.shape[0], faces.shape[0], int(n_clusters)
+    assert vertex_order.numel() == cell_key_sorted.numel() == n_v and corner_sorted.numel() == 3 * n_f
+    assert vertex_start.numel() == corner_start.numel() == n_c + 1
+    positions = torch.empty(n_c, 3, dtype=torch.float64, device=vertices.device)
+    clamped = torch.empty(n_c, dtype=torch.uint8, device=vertices.device)
+    with _Prof('vc_solve', 32 * n_v + 3 * n_f * (8 + 24 + 72) + 25 * n_c):
+        _check(_lib.psn_vc_solve(vp, fp, n_f, n_v, _tptr(vertex_order, 'vertex_order', torch.int64), _tptr(vertex_start, 'vertex_start', torch.int64),
+                                 _tptr(cell_key_sorted, 'cell_key_sorted', torch.int64), _tptr(corner_sorted, 'corner_sorted', torch.int64),
+                                 _tptr(corner_start, 'corner_start', torch.int64), n_c, *_vc_grid(grid), float(regularisation),
+                                 positions.data_ptr(), clamped.data_ptr(), _stream()), 'vc_solve')
+    return positions, clamped
+
+
+def vc_face_flags(vertices, faces, g, positions, face_keep):
+    """psn_vc_face_flags -> (vertex_keep uint8 [C]: the clusters a kept face names, flipped uint8 [F]: kept faces whose normal turned)."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    n_v, n_f, n_c = vertices.shape[0], faces.shape[0], positions.shape[0]
+    assert g.numel() == 3 * n_f and face_keep.numel() == n_f
+    vertex_keep = torch.empty(n_c, dtype=torch.uint8, device=vertices.device)
+    flipped = torch.empty(n_f, dtype=torch.uint8, device=vertices.device)
+    with _Prof('vc_face_flags', n_c + n_f * (2 + 48 + 144)):
+        _check(_lib.psn_vc_face_flags(vp, fp, n_f, n_v, _tptr(g, 'g', torch.int64), _tptr(positions, 'positions', torch.float64), n_c,
+                                      _tptr(face_keep, 'face_keep', torch.uint8), vertex_keep.data_ptr(), flipped.data_ptr(), _stream()),
+               'vc_face_flags')
+    return vertex_keep, flipped
+
+
 # --------------------------------------------------------------------------- image evaluation (csrc/imgmetrics.hip)
 IMG_TYPES = {torch.float32: IMG_F32, torch.uint8: IMG_U8}  # noqa: F821
 

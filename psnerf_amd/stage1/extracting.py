@@ -23,6 +23,9 @@ Clean-up (not in the reference; opt-in): ``Extractor3D(..., keep_components=K, m
   connected components of the extracted mesh among those with at least N faces (psnerf_amd/meshclean.py; on the device
   csrc/meshclean.hip, applied to the device tensors before the copy-back and before the normals are estimated).  With both at
   their defaults (None, 0) the extraction is bit for bit what it was.
+Simplification (the lineage's ``simplify_nfaces``, which UNISURF and the reference dropped with its native library; opt-in):
+  ``Extractor3D(..., simplify_nfaces=N)`` reduces the mesh to at most N faces by quadric vertex clustering (psnerf_amd/meshsimplify.py;
+  on the device csrc/meshsimplify.hip), after the clean-up and before the copy-back and the normals.  None (the default) = off.
 Vertex refinement (extracting.py:237-323): ``Extractor3D.refine_mesh(mesh, steps=N)`` / tools/refine_mesh.py run the reference's
   RMSprop refinement of the vertices against the field (``refine_loss`` / ``refine_vertices`` below).  The reference's method calls
   ``self.model.decoder``, which its own NeuralNetwork does not have, so it cannot run there; it is restated with
@@ -293,7 +296,7 @@ class Extractor3D(object):
 
     def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0, device=None, resolution0=16,
                  upsampling_steps=3, with_normals=False, padding=0.4, refine_max_faces=10000, keep_components=None,
-                 min_component_faces=0):
+                 min_component_faces=0, simplify_nfaces=None):
         if device is None and isinstance(model, torch.nn.Module):
             device = next(model.parameters()).device   # (the reference leaves the model where it is; so do we, and follow it)
         self.model = model.to(device) if (model is not None and hasattr(model, 'to')) else model
@@ -309,6 +312,8 @@ class Extractor3D(object):
         # clean-up (meshclean.py): keep the K largest connected components among those with at least N faces; (None, 0) = off
         self.keep_components = keep_components
         self.min_component_faces = min_component_faces
+        # simplification (meshsimplify.py): quadric vertex clustering to at most this many faces, after the clean-up; None = off
+        self.simplify_nfaces = simplify_nfaces
         self.last_grid = None   # the dense value grid of the last generate_* call (device tensor or numpy array)
         self.phase_events = None  # a list: (phase, start event, end event) of the device phases are appended (measurement runs)
         self.last_known = None  # which of its points were evaluated (bool, same shape; None without upsampling: all of them)
@@ -398,6 +403,15 @@ class Extractor3D(object):
                     v, f, _, report = meshclean._device_clean(v, f, None, self.keep_components, self.min_component_faces, 'faces')
                 torch.cuda.synchronize(occ_hat.device)
                 t0 += self._clean_stats(stats_dict, report, time.time() - t1)   # ('time (marching cubes)' stays what it was)
+            if self.simplify_nfaces is not None:   # likewise on the device tensors, after the clean-up
+                from .. import meshsimplify
+                torch.cuda.synchronize(occ_hat.device)
+                t1 = time.time()
+                n_from = f.shape[0]
+                with _Phase(self.phase_events, 'simplify'):
+                    v, f, report = meshsimplify._device_simplify(v, f, target_faces=self.simplify_nfaces)
+                torch.cuda.synchronize(occ_hat.device)
+                t0 += self._simplify_stats(stats_dict, report, n_from, time.time() - t1)
             with _Phase(self.phase_events, 'copy-back'):
                 vertices, faces = v.cpu().numpy(), f.cpu().numpy()
             stats_dict['time (marching cubes)'] = time.time() - t0
@@ -411,6 +425,12 @@ class Extractor3D(object):
                 t1 = time.time()
                 vertices, faces, _, report = meshclean.host_clean(vertices, faces, None, self.keep_components, self.min_component_faces)
                 self._clean_stats(stats_dict, report, time.time() - t1)
+            if self.simplify_nfaces is not None:
+                from .. import meshsimplify
+                t1 = time.time()
+                n_from = faces.shape[0]
+                vertices, faces, report = meshsimplify.host_simplify(vertices, faces, target_faces=self.simplify_nfaces)
+                self._simplify_stats(stats_dict, report, n_from, time.time() - t1)
         normals = None
         if self.with_normals and vertices.shape[0] != 0:
             t0 = time.time()
@@ -422,6 +442,12 @@ class Extractor3D(object):
     def _clean_stats(stats_dict, report, seconds):
         stats_dict['n_components'], stats_dict['n_faces_removed'] = report['n_components'], report['n_faces_removed']
         stats_dict['time (components)'] = seconds
+        return seconds
+
+    @staticmethod
+    def _simplify_stats(stats_dict, report, n_faces_from, seconds):
+        stats_dict['n_faces_simplified_from'], stats_dict['simplify_resolution'] = int(n_faces_from), report['resolution']
+        stats_dict['time (simplify)'] = seconds
         return seconds
 
     def estimate_normals(self, vertices, c=None):

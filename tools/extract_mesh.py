@@ -3,13 +3,14 @@
 
     python tools/extract_mesh.py --obj_name bear --expname test_1 [--exp_folder out] [--test_out_dir test_out]
                                  [--load_iter N] [--upsampling-steps S] [--mesh_extension obj|ply] [--clip]
-                                 [--keep-components K] [--min-component-faces N]
+                                 [--keep-components K] [--min-component-faces N] [--simplify-nfaces N]
 
 reads <exp_folder>/<obj_name>/<expname>/config.yaml and models/model[_N].pt, writes <test_out_dir>/<obj_name>/<expname>/mesh.<ext>.
 On a GPU the whole extraction runs on the device (psnerf_amd/stage1/extracting.py); --no-cuda takes the numpy host path with the
 model evaluated by the CPU oracle.  --keep-components K / --min-component-faces N (not in the reference; off when absent) keep the K
 largest connected components of the mesh among those with at least N faces (psnerf_amd/meshclean.py): the floaters and inner shells
-of a field trained from few views go before the mesh is written."""
+of a field trained from few views go before the mesh is written.  --simplify-nfaces N (off when absent) then reduces the mesh to at
+most N faces by quadric vertex clustering (psnerf_amd/meshsimplify.py)."""
 import argparse
 import os
 import sys
@@ -36,6 +37,7 @@ def main(argv=None):
     parser.add_argument('--clip', action='store_true', default=False, help='clip the bottom area')
     parser.add_argument('--keep-components', type=int, default=None, help='keep the K largest connected components')
     parser.add_argument('--min-component-faces', type=int, default=0, help='drop connected components with fewer faces')
+    parser.add_argument('--simplify-nfaces', type=int, default=None, help='simplify the mesh to at most this many faces')
     args = parser.parse_args(argv)
 
     torch.manual_seed(0)
@@ -56,7 +58,7 @@ def main(argv=None):
     CheckpointIO(os.path.join(out_dir, 'models'), model=model).load('model_%d.pt' % args.load_iter if args.load_iter else 'model.pt')
     generator = Extractor3D(model, resolution0=cfg['extraction']['resolution'], upsampling_steps=cfg['extraction']['upsampling_steps'],
                             refinement_step=max(args.refinement_step, 0), device=device, keep_components=args.keep_components,
-                            min_component_faces=args.min_component_faces)
+                            min_component_faces=args.min_component_faces, simplify_nfaces=args.simplify_nfaces)
     model.eval()
     test_out_path = os.path.join(args.test_out_dir, args.obj_name, args.expname)
     os.makedirs(test_out_path, exist_ok=True)
@@ -68,6 +70,8 @@ def main(argv=None):
         mesh_out_file, len(mesh.vertices), len(mesh.faces), stats['n_points_evaluated'], stats['n_rounds'], time.time() - t0))
     if 'n_components' in stats:
         print('%d connected components, %d faces removed' % (stats['n_components'], stats['n_faces_removed']))
+    if 'n_faces_simplified_from' in stats:
+        print('simplified from %d faces (grid resolution %s)' % (stats['n_faces_simplified_from'], stats['simplify_resolution']))
     return mesh_out_file
 
 
