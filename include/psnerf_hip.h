@@ -890,6 +890,33 @@ int psn_ray_cast(const PsnTriGrid* grid, const double* vertices, const int64_t* 
                  unsigned char* hit, long long* n_tests, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Crossing counts of an axis-parallel line with the mesh, over the same index (csrc/meshinside.hip; the float64 numpy definition is
+ * psnerf_amd/meshdist.py:host_crossings): the inside test behind volume IoU.  The reference has no such query.  grid, vertices,
+ * faces, cell_start, list, over_list, n_over: as psn_closest_point takes them.
+ *
+ * psn_mesh_crossings: points float64 [Q, 3]; order = null or a permutation of 0 .. Q - 1 in which the points are worked on (sorted
+ *   by column, then by cell along the axis; outputs are written at the point's own row either way).  axis = 0, 1 or 2: the line
+ *   through a point runs along it.  With kz = axis, kx = (axis + 1) % 3, ky = (axis + 2) % 3 the corners are translated by -p and
+ *   U, V, W are the watertight test's edge functions without its shear; an edge function that is exactly 0 is decided by simulation
+ *   of simplicity (p moved by (+d, +d^2) in (kx, ky)): sign(e), else sign(Qy - Py), else sign(Px - Qx).  The rule is antisymmetric
+ *   in the edge's two ends, so of two triangles on opposite sides of a shared edge exactly one owns a point on it.  A triangle is
+ *   accepted when p lies in the closed bounding box of its projection (exact; it keeps slivers whose U, V, W are rounding noise
+ *   from counting far from where they are), the three sides are equal and non-zero and det = U + V + W != 0;
+ *   z = (U Az + V Bz + W Cz) / det.
+ *   above int32 [Q] = accepted triangles of the WHOLE mesh with z > 0; below int32 [Q] or null: z < 0; on int32 [Q] or null:
+ *   z == 0 -- each triangle once, bitwise reproducible, independent of the order of the lists.  inside = above & 1;
+ *   (above + below + on) & 1 = the line does not see a closed surface.  Without below the walk starts at the point's own cell;
+ *   above and on do not change.  Zero-area and edge-on triangles are never counted; a point with a non-finite coordinate, or
+ *   outside the bounding box in kx or ky, gets zeros.  n_tests: null, or an int64 counter to which the number of line-triangle
+ *   tests is added (at most Q F).  Q = 0 is a no-op.
+ * Errors: PSN_E_ARG for null pointers, an axis outside 0 .. 2, F or Q out of range, a bad PsnTriGrid; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_CROSSINGS_MAX_POINTS 137438953408LL
+int psn_mesh_crossings(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
+                       const int* list, const int* over_list, int64_t n_over, const double* points, const int64_t* order,
+                       int64_t n_points, int axis, int* above, int* below, int* on, long long* n_tests, void* stream);
+
+/* ------------------------------------------------------------------------
  * Mesh clean-up: connected components of a triangle mesh, per-component statistics and compaction (csrc/meshclean.hip; the numpy
  * definition is psnerf_amd/meshclean.py:host_*).  The reference has no such step (its only answer to floaters is --clip,
  * stage1/model/extracting.py:130-132); users of the pipeline take trimesh's split() on the host.

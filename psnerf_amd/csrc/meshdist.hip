@@ -12,21 +12,6 @@
 
 namespace psn {
 
-__device__ __forceinline__ double md_min3(double a, double b, double c) { return fmin(a, fmin(b, c)); }
-__device__ __forceinline__ double md_max3(double a, double b, double c) { return fmax(a, fmax(b, c)); }
-
-// the cell range of a triangle's bounding box; returns the number of cells
-__device__ __forceinline__ int64_t md_range(const PsnTriGrid& g, const MdTri& t, int* c0, int* c1) {
-    const double inv = 1.0 / g.cell;
-    c0[0] = md_cell(md_min3(t.ax, t.bx, t.cx), g.lo[0], inv, g.n[0]);
-    c1[0] = md_cell(md_max3(t.ax, t.bx, t.cx), g.lo[0], inv, g.n[0]);
-    c0[1] = md_cell(md_min3(t.ay, t.by, t.cy), g.lo[1], inv, g.n[1]);
-    c1[1] = md_cell(md_max3(t.ay, t.by, t.cy), g.lo[1], inv, g.n[1]);
-    c0[2] = md_cell(md_min3(t.az, t.bz, t.cz), g.lo[2], inv, g.n[2]);
-    c1[2] = md_cell(md_max3(t.az, t.bz, t.cz), g.lo[2], inv, g.n[2]);
-    return (int64_t)(c1[0] - c0[0] + 1) * (c1[1] - c0[1] + 1) * (c1[2] - c0[2] + 1);
-}
-
 __global__ __launch_bounds__(256) void tri_grid_count_kernel(PsnTriGrid g, const double* __restrict__ vertices, const int64_t* __restrict__ faces,
                                                              int64_t n_faces, int* __restrict__ cell_count, int* __restrict__ over_list,
                                                              unsigned long long* __restrict__ n_over) {

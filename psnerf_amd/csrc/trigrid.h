@@ -1,6 +1,6 @@
-// The uniform grid of triangle lists (PsnTriGrid) as its builder and its two queries see it: csrc/meshdist.hip builds it and asks
-// for the closest point, csrc/meshray.hip casts rays through it.  Both must map a coordinate to a cell in exactly one way, so the
-// mapping lives here.
+// The uniform grid of triangle lists (PsnTriGrid) as its builder and its queries see it: csrc/meshdist.hip builds it and asks
+// for the closest point, csrc/meshray.hip casts rays through it, csrc/meshinside.hip counts a line's crossings in it.  All must map
+// a coordinate to a cell, and a triangle to its range of cells, in exactly one way, so both mappings live here.
 #pragma once
 #include "common.h"
 
@@ -22,6 +22,21 @@ struct MdTri {
 __device__ __forceinline__ MdTri md_load(const double* __restrict__ v, const int64_t* __restrict__ f, int64_t t) {
     const int64_t i = f[3 * t], j = f[3 * t + 1], k = f[3 * t + 2];
     return MdTri{v[3 * i], v[3 * i + 1], v[3 * i + 2], v[3 * j], v[3 * j + 1], v[3 * j + 2], v[3 * k], v[3 * k + 1], v[3 * k + 2]};
+}
+
+__device__ __forceinline__ double md_min3(double a, double b, double c) { return fmin(a, fmin(b, c)); }
+__device__ __forceinline__ double md_max3(double a, double b, double c) { return fmax(a, fmax(b, c)); }
+
+// the cell range of a triangle's bounding box; returns the number of cells
+__device__ __forceinline__ int64_t md_range(const PsnTriGrid& g, const MdTri& t, int* c0, int* c1) {
+    const double inv = 1.0 / g.cell;
+    c0[0] = md_cell(md_min3(t.ax, t.bx, t.cx), g.lo[0], inv, g.n[0]);
+    c1[0] = md_cell(md_max3(t.ax, t.bx, t.cx), g.lo[0], inv, g.n[0]);
+    c0[1] = md_cell(md_min3(t.ay, t.by, t.cy), g.lo[1], inv, g.n[1]);
+    c1[1] = md_cell(md_max3(t.ay, t.by, t.cy), g.lo[1], inv, g.n[1]);
+    c0[2] = md_cell(md_min3(t.az, t.bz, t.cz), g.lo[2], inv, g.n[2]);
+    c1[2] = md_cell(md_max3(t.az, t.bz, t.cz), g.lo[2], inv, g.n[2]);
+    return (int64_t)(c1[0] - c0[0] + 1) * (c1[1] - c0[1] + 1) * (c1[2] - c0[2] + 1);
 }
 
 static inline int md_check_grid(const PsnTriGrid* g, const char* what) {

@@ -1561,6 +1561,32 @@ def ray_cast(grid, vertices, faces, cell_start, lst, over_list, n_over, origins,
     return t, tri, bary, hit
 
 
+# --------------------------------------------------------------------------- crossing counts (csrc/meshinside.hip)
+def mesh_crossings(grid, vertices, faces, cell_start, lst, over_list, n_over, points, axis=2, order=None, want_below=True, want_on=True,
+                   n_tests=None):
+    """psn_mesh_crossings: points float64 [Q, 3] -> (above int32 [Q], below int32 [Q] or None, on int32 [Q] or None): the triangles of
+    the whole mesh that the line through each point along ``axis`` crosses above, below and exactly at the point.  order = the
+    permutation in which the points are worked on (or None); n_tests (int64 [1]) accumulates the number of line-triangle tests."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    _tptr(points, 'mesh_crossings: points', torch.float64)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError('mesh_crossings: points [Q, 3] expected, got %s' % (tuple(points.shape),))
+    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
+    q = points.shape[0]
+    assert order is None or order.numel() == q
+    dev = vertices.device
+    above = torch.empty(q, dtype=torch.int32, device=dev)
+    below = torch.empty(q, dtype=torch.int32, device=dev) if want_below else None
+    on = torch.empty(q, dtype=torch.int32, device=dev) if want_on else None
+    with _Prof('mesh_crossings', q):
+        _check(_lib.psn_mesh_crossings(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cell_start, 'cell_start', torch.int32),
+                                       _tptr(lst, 'list', torch.int32), _tptr(over_list, 'over_list', torch.int32), int(n_over),
+                                       points.data_ptr(), None if order is None else _tptr(order, 'order', torch.int64), q, int(axis),
+                                       above.data_ptr(), None if below is None else below.data_ptr(), None if on is None else on.data_ptr(),
+                                       None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'mesh_crossings')
+    return above, below, on
+
+
 # --------------------------------------------------------------------------- mesh clean-up (csrc/meshclean.hip)
 def cc_label(faces, n_vertices, status):
     """psn_cc_label: faces int64 [F, 3] -> labels int32 [n_vertices], the smallest vertex index reachable from each vertex.  status

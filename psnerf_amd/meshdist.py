@@ -29,6 +29,12 @@ culling and with t_min <= t <= t_max; the result per ray is the minimum of (t, t
 triangles; a miss is t = inf, triangle -1, NaN barycentrics.  With ``any_hit`` only the boolean is defined.
 Stated differences from what a plain Moeller-Trumbore caster returns: a triangle with det == 0 (zero area, or seen edge-on) is never
 hit; a ray with a NaN (or infinite) component or a zero direction misses.
+
+The inside test (the reference has none either) likewise: ``host_crossings`` is the definition, csrc/meshinside.hip through
+``MeshIndex.crossings`` / ``contains`` the device path.  Definition.  The line through a point along a coordinate axis crosses a
+triangle by the same edge functions without the shear, with an edge function that is exactly 0 decided by simulation of simplicity,
+so that a line through a shared edge or a vertex crosses exactly one of the triangles around it; per point the triangles of the
+WHOLE mesh crossed above it, below it and at it are counted, and inside = the parity of those above.
 """
 import os
 
@@ -237,6 +243,69 @@ def host_ray_cast(vertices, faces, origins, directions, t_min=0.0, t_max=np.inf,
     return t, tri, bary, hit
 
 
+def _side(e, Px, Py, Qx, Qy):
+    """The side of the directed edge (P, Q) on which the line lies, by simulation of simplicity (the line moved by (+d, +d^2) in
+    (kx, ky)): sign(e), or where e == 0 sign(Qy - Py), or where that is 0 sign(Px - Qx) -> int8; antisymmetric in (P, Q).  A NaN e
+    gives 0."""
+    one, zero = np.int8(1), np.int8(0)
+    sign = lambda pos, neg: np.where(pos, one, np.where(neg, -one, zero))
+    tie = sign(Qy > Py, Qy < Py)
+    return np.where(e == 0.0, np.where(tie != 0, tie, sign(Px > Qx, Px < Qx)), sign(e > 0.0, e < 0.0))
+
+
+def _line_triangles(p, a, b, c):
+    """The line through p along kz against triangles (a, b, c), operation for operation as csrc/meshinside.hip:mi_count.  p, a, b, c:
+    lists of three broadcastable arrays in (kx, ky, kz) order -> (accepted, z): the watertight ray test with S = (0, 0, 1), written
+    without the shear, and with ties on an edge function decided by ``_side``."""
+    with np.errstate(all='ignore'):
+        Ax, Ay, Az = a[0] - p[0], a[1] - p[1], a[2] - p[2]
+        Bx, By, Bz = b[0] - p[0], b[1] - p[1], b[2] - p[2]
+        Cx, Cy, Cz = c[0] - p[0], c[1] - p[1], c[2] - p[2]
+        box = ((np.minimum(np.minimum(Ax, Bx), Cx) <= 0.0) & (np.maximum(np.maximum(Ax, Bx), Cx) >= 0.0) &
+               (np.minimum(np.minimum(Ay, By), Cy) <= 0.0) & (np.maximum(np.maximum(Ay, By), Cy) >= 0.0))
+        U = Cx * By - Cy * Bx
+        V = Ax * Cy - Ay * Cx
+        W = Bx * Ay - By * Ax
+        sU, sV, sW = _side(U, Bx, By, Cx, Cy), _side(V, Cx, Cy, Ax, Ay), _side(W, Ax, Ay, Bx, By)
+        det = U + V + W
+        ok = box & (sU != 0) & (sU == sV) & (sU == sW) & (det != 0.0)
+        z = (U * Az + V * Bz + W * Cz) / det
+        return ok & np.isfinite(z), z
+
+
+def host_crossings(vertices, faces, points, axis=2):
+    """How often the line through each of points [Q, 3] along ``axis`` crosses the mesh, by brute force over all triangles in chunks
+    of points -> (above int32 [Q], below int32 [Q], on int32 [Q]): the triangles crossed above the point (z > 0), below it and exactly
+    at it.  inside = above & 1; (above + below + on) & 1 = the line does not see a closed surface.
+
+    Definition.  kz = axis, kx = (axis + 1) % 3, ky = (axis + 2) % 3.  Per triangle the corners are translated by -p, U, V, W are the
+    edge functions of ``_ray_triangles`` and each one's side is ``_side``: a point exactly on an edge or a vertex of the projected
+    mesh belongs to exactly one of two triangles on opposite sides of that edge, so a parity over a closed surface is exact also for
+    lines through vertices and edges.  A triangle counts when the line lies in the closed bounding box of its projection (exact
+    comparisons; implied by the sides in exact arithmetic, and there for slivers whose U, V, W are all rounding noise: their signs
+    can agree for a point anywhere on the slivers' line), the three sides are equal and non-zero and det = U + V + W != 0, with
+    z = (U Az + V Bz + W Cz) / det; a non-finite z counts nowhere.  Zero-area and edge-on triangles are never counted; a point with a
+    non-finite coordinate gets three zeros."""
+    v, f = _as_mesh_arrays(vertices, faces)
+    if f.shape[0] == 0:
+        raise ValueError('host_crossings: the mesh has no faces')
+    if axis not in (0, 1, 2):
+        raise ValueError('host_crossings: axis=%r (0, 1 or 2)' % (axis,))
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+    k = [(axis + 1) % 3, (axis + 2) % 3, axis]
+    counts = np.zeros((3, pts.shape[0]), dtype=np.int32)
+    rows = np.nonzero(np.isfinite(pts).all(axis=1))[0]
+    corners = [[v[f[:, j], k[i]][None, :] for i in range(3)] for j in range(3)]
+    step = max(1, _PAIRS_PER_CHUNK // f.shape[0])
+    for q0 in range(0, len(rows), step):
+        r = rows[q0:q0 + step]
+        ok, z = _line_triangles([pts[r, k[i]][:, None] for i in range(3)], *corners)
+        counts[0, r] = (ok & (z > 0.0)).sum(axis=1)
+        counts[1, r] = (ok & (z < 0.0)).sum(axis=1)
+        counts[2, r] = (ok & (z == 0.0)).sum(axis=1)
+    return counts[0], counts[1], counts[2]
+
+
 def host_face_areas(vertices, faces):
     v, f = _as_mesh_arrays(vertices, faces)
     a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
@@ -340,14 +409,15 @@ class MeshIndex(object):
     def index_bytes(self):
         return 4 * (self.cell_start.numel() + self.list.numel() + self.over_list.numel())
 
-    def home_order(self, points):
+    def home_order(self, points, axes=(0, 1, 2)):
         """The permutation that sorts the points by their (clamped) home cell: plumbing that keeps a wave's lanes in neighbouring
-        cells.  It only orders the work; the kernel forms the home cell itself."""
+        cells.  It only orders the work; the kernel forms the home cell itself.  ``axes``: the grid axes from the slowest to the
+        fastest digit of the sort key (the default is the cells' own linear index)."""
         lo = torch.tensor(self.lo, dtype=torch.float64, device=points.device)
         top = torch.tensor(self.n, dtype=torch.float64, device=points.device) - 1.0
         c = torch.nan_to_num(torch.floor((points - lo) / self.cell), nan=0.0)
         c = torch.minimum(torch.clamp(c, min=0.0), top).to(torch.int64)
-        key = (c[:, 0] * self.n[1] + c[:, 1]) * self.n[2] + c[:, 2]
+        key = (c[:, axes[0]] * self.n[axes[1]] + c[:, axes[1]]) * self.n[axes[2]] + c[:, axes[2]]
         return torch.sort(key).indices
 
     def closest_point(self, points, n_tests=None):
@@ -387,6 +457,30 @@ class MeshIndex(object):
         t, tri, bary, hit = hip.ray_cast(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over,
                                          origins, directions, t_min, t_max, order=order, any_hit=any_hit, n_tests=n_tests)
         return t, tri, bary, hit.bool()
+
+    def crossings(self, points, axis=2, below=True, n_tests=None, sort=True):
+        """points float64 [Q, 3] on the index's device -> (above, below, on) int32 [Q], device tensors: host_crossings on the device
+        (csrc/meshinside.hip).  below=False: only the part of the line above each point is walked; ``below`` is then None, ``above``
+        and ``on`` are the same integers.  The points are worked on sorted by column, then by cell along ``axis`` (sort=False: in
+        the order given); that only orders the work.  n_tests: an int64 [1] device tensor to which the number of line-triangle tests
+        is added."""
+        from . import hip
+        if not (torch.is_tensor(points) and points.is_cuda):
+            raise RuntimeError('MeshIndex.crossings: points must be a device tensor (host arrays: host_crossings)')
+        if axis not in (0, 1, 2):
+            raise ValueError('MeshIndex.crossings: axis=%r (0, 1 or 2)' % (axis,))
+        points = points.to(torch.float64).reshape(-1, 3).contiguous()
+        axes = ((axis + 1) % 3, (axis + 2) % 3, axis)
+        order = self.home_order(points, axes) if sort and points.shape[0] > 64 else None   # (one wave: nothing to order)
+        return hip.mesh_crossings(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over, points,
+                                  axis=axis, order=order, want_below=below, n_tests=n_tests)
+
+    def contains(self, points, axis=2, vote=False):
+        """Is each of points [Q, 3] inside the mesh -> bool [Q]: the parity of the crossings above the point along ``axis``.  Exact
+        for a closed surface, also for points whose line runs through vertices and edges (see host_crossings); for a point ON the
+        surface the answer depends on the axis.  vote=True: the majority of the three axes (``axis`` is not used), for scans with
+        holes, where a line through a hole has the wrong parity."""
+        return _contains(self, points, axis, vote)
 
     def face_areas_cumulative(self):
         v, f = self.vertices, self.faces
@@ -431,6 +525,21 @@ class _HostMesh(object):
     def ray_cast(self, origins, directions, t_min=0.0, t_max=np.inf, any_hit=False, n_tests=None):
         to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x
         return host_ray_cast(self.vertices, self.faces, to_np(origins), to_np(directions), t_min, t_max, any_hit)
+
+    def crossings(self, points, axis=2, below=True, n_tests=None):
+        above, under, on = host_crossings(self.vertices, self.faces, points.detach().cpu().numpy() if torch.is_tensor(points) else points, axis)
+        return above, (under if below else None), on
+
+    def contains(self, points, axis=2, vote=False):
+        return _contains(self, points, axis, vote)
+
+
+def _contains(mesh, points, axis, vote):
+    """MeshIndex.contains / _HostMesh.contains: the parity of ``above``, or the majority of the three axes' parities."""
+    if not vote:
+        return (mesh.crossings(points, axis, below=False)[0] & 1) == 1
+    votes = sum(mesh.crossings(points, a, below=False)[0] & 1 for a in range(3))
+    return votes >= 2
 
 
 def _prepare(mesh, device, name):

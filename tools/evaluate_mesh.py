@@ -1,0 +1,60 @@
+#!/usr/bin/env python
+"""The evaluation table of a predicted mesh against the ground-truth scan: Chamfer distance, accuracy / completeness, F-score at
+distance thresholds, normal consistency and volume IoU (psnerf_amd/mesheval.py).
+
+    python tools/evaluate_mesh.py PRED GT [--samples 10000] [--thresholds T [T ...]] [--iou-points 100000] [--seed S] [--vote]
+                                  [--device cuda|cpu] [--json]
+
+Meshes: .obj / .ply (psnerf_amd.meshdist.load_mesh).  --thresholds are distances in mesh units (default: 0.5 %, 1 % and 2 % of the
+diagonal of GT's bounding box).  --iou-points 0 skips the volume block; --vote takes the majority of the three axes' inside tests,
+for scans with holes.  On a GPU (--device cuda, the default where one is present) the meshes are uploaded once and sampling, the
+distance queries and the inside tests run on the device; otherwise the numpy host path.  --seed makes the samples reproducible.
+--json prints the result as one JSON object instead of the table."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description='Mesh evaluation')
+    parser.add_argument('pred', type=str)
+    parser.add_argument('gt', type=str)
+    parser.add_argument('--samples', type=int, default=10000)
+    parser.add_argument('--thresholds', type=float, nargs='+', default=None)
+    parser.add_argument('--iou-points', type=int, default=100000)
+    parser.add_argument('--seed', type=int, default=None)
+    parser.add_argument('--vote', action='store_true')
+    parser.add_argument('--device', type=str, default=None, choices=('cuda', 'cpu'))
+    parser.add_argument('--json', action='store_true')
+    args = parser.parse_args(argv)
+    from psnerf_amd.meshdist import load_mesh
+    from psnerf_amd.mesheval import evaluate_mesh
+    device = args.device if args.device is not None else ('cuda' if torch.cuda.is_available() else 'cpu')
+    rng = np.random.RandomState(args.seed) if args.seed is not None else None
+    result = evaluate_mesh(load_mesh(args.pred), load_mesh(args.gt), num_samples=args.samples, thresholds=args.thresholds,
+                           iou_points=args.iou_points, rng=rng, device='cuda' if device == 'cuda' else None, vote=args.vote)
+    del result['raw']
+    if args.json:
+        print(json.dumps(result))
+        return result
+    print('Chamfer distance   %.6g   (accuracy %.6g, completeness %.6g)' % (result['chamfer'], result['accuracy'], result['completeness']))
+    print('squared            %.6g   (accuracy %.6g, completeness %.6g)' % (result['chamfer2'], result['accuracy2'], result['completeness2']))
+    for t in result['thresholds']:
+        print('F-score @ %-8.4g %.4f     (precision %.4f, recall %.4f)' % (t, result['fscore'][t], result['precision'][t], result['recall'][t]))
+    print('Normal consistency %.4f     (accuracy %.4f, completeness %.4f)' % (result['normals'], result['normals_accuracy'],
+                                                                              result['normals_completeness']))
+    if result['iou_points'] > 0:
+        print('Volume IoU         %.4f     (volume pred %.6g, gt %.6g; lines not closed: pred %.2f %%, gt %.2f %%)' % (
+            result['iou'], result['volume_pred'], result['volume_gt'], 100.0 * result['open_pred'], 100.0 * result['open_gt']))
+    return result
+
+
+if __name__ == '__main__':
+    main()
