@@ -120,6 +120,22 @@ int psn_gemm(int trans_a, int trans_b, int64_t M, int N, int K, const float* A, 
              int64_t ldb, float* C, int64_t ldc, const float* bias, int epilogue, const float* aux_in,
              int64_t ld_aux_in, const float* aux_in2, int64_t ld_aux_in2, float* aux_out, int64_t ld_aux_out,
              int split_k, float* workspace, float* colsum_a, void* stream);
+/* What psn_gemm would launch for these arguments (M > 0): a host-only query of its dispatcher, the same function the launcher
+ * calls.  No device or HIP call; a pure function of the shapes, the leading dimensions, the requested split and the operand
+ * addresses, which are passed as integers (only their low four bits count, and 0 = absent for the aux operands). */
+typedef struct {
+    int bn;                     /* tile width in columns: 128 (gemm_kernel<.,.,2>) or 256 (gemm_kernel<.,.,4>) */
+    int split_k, k_chunk;       /* slices actually launched and the rows of one (a multiple of 16) */
+    int64_t tiles_m; int tiles_n;
+    int64_t blocks;             /* tiles_m * tiles_n * split_k workgroups */
+    int a_vec, b_vec, c_vec, auxin_vec, auxin2_vec, auxout_vec;   /* 16-byte accesses allowed per operand */
+    int reduce;                 /* 0: one slice, straight to C;  1: scalar split-K reduction;  2: vector reduction */
+    int nt, nt_last;            /* 16-row k-tiles of the first and of the last slice */
+    int last_tile_rows;         /* rows in the last k-tile of the last slice (1..16) */
+} PsnGemmPlan;
+int psn_gemm_plan(int64_t M, int N, int K, int64_t a_addr, int64_t lda, int64_t b_addr, int64_t ldb, int64_t c_addr,
+                  int64_t ldc, int64_t aux_in_addr, int64_t ld_aux_in, int64_t aux_in2_addr, int64_t ld_aux_in2,
+                  int64_t aux_out_addr, int64_t ld_aux_out, int split_k, int64_t workspace_addr, PsnGemmPlan* plan);
 
 /* Grouped weight gradients of one backward pass (nn.Linear backward of every layer of a network at once):
  *   C_i [M_i, N_i] (+)= A_i^T B_i (+ A2_i^T B2_i),    colsum_a_i [M_i] = column sums of A_i      for i < n_items
@@ -148,6 +164,33 @@ typedef struct {
 } PsnGemmTnItem;
 int psn_gemm_tn_grouped(int n_items, const PsnGemmTnItem* items, int64_t K, int split_k, float* workspace,
                         int64_t workspace_floats, void* stream);
+/* What psn_gemm_tn_grouped (and _x3) would launch for these items: a host-only query of its dispatcher, the same function the
+ * launcher calls, with the launcher's argument checks.  No device or HIP call: the pointers of the items are looked at as
+ * integers only (low four bits, null or not) and never followed, so any integers with the right low bits will do. */
+#define PSN_TN_TILE 0          /* kind: 128 x 128 tiles (gemm_tn_grouped_kernel) */
+#define PSN_TN_BIG 1           /*       one 256 x 256 tile per workgroup (gemm_tn256_grouped_kernel, or the x3 kernel) */
+#define PSN_TN_TALL 2          /*       one 256 x 64 tile per workgroup (gemm_tn_tall_grouped_kernel) */
+#define PSN_TN_INDEX_FAST 1    /* index_path bits: some slice maps k to a table row with the float reciprocal ... */
+#define PSN_TN_INDEX_DIV 2     /* ... and some slice (one that ends above 2^24) with integer division */
+typedef struct {
+    int split_k, k_chunk;             /* slices per product and rows per slice of the 128 x 128-tile path ... */
+    int split_big, k_chunk_big;       /* ... of the 256 x 256-tile path (k-tiles of 32 rows) ... */
+    int split_tall, k_chunk_tall;     /* ... and of the 256 x 64-tile path (k-tiles of 16 rows) */
+    int64_t workspace_floats;         /* floats of workspace the launch needs */
+    int kind[PSN_GEMM_TN_MAX_ITEMS];
+    int dma[PSN_GEMM_TN_MAX_ITEMS];             /* kind BIG: operand B arrives by LDS-DMA (N == 256), else through registers */
+    int splits[PSN_GEMM_TN_MAX_ITEMS];          /* workgroups per tile: slices x products */
+    int live_slices[PSN_GEMM_TN_MAX_ITEMS];     /* slices that hold rows (fewer than the slices of the path under k_rows) */
+    int nt[PSN_GEMM_TN_MAX_ITEMS];              /* k-tiles of a full slice (0 when only one slice holds rows) */
+    int nt_last[PSN_GEMM_TN_MAX_ITEMS];         /* k-tiles of the last slice that holds rows */
+    int last_tile_rows[PSN_GEMM_TN_MAX_ITEMS];  /* rows in its last k-tile */
+    int b_mod[PSN_GEMM_TN_MAX_ITEMS], b2_mod[PSN_GEMM_TN_MAX_ITEMS];   /* as passed to the kernel: 0 = cannot wrap */
+    int index_path[PSN_GEMM_TN_MAX_ITEMS];      /* 0 = no table, else PSN_TN_INDEX_* bits */
+    int a_vec[PSN_GEMM_TN_MAX_ITEMS], b_vec[PSN_GEMM_TN_MAX_ITEMS], c_vec[PSN_GEMM_TN_MAX_ITEMS];
+    int reduce_vec[PSN_GEMM_TN_MAX_ITEMS];      /* the reduction of this item takes its float4 path */
+} PsnGemmTnPlan;
+int psn_gemm_tn_plan(int n_items, const PsnGemmTnItem* items, int64_t K, int split_k, int64_t workspace_addr,
+                     PsnGemmTnPlan* plan);
 /* Partial products per multiply of the psn_gemm_tn_grouped_x3 launches that follow: 6 (default; three bf16 pieces per operand,
  * fp32-class), 3 (two pieces: hi hi + hi mid + mid hi, ~16 significant bits) or 1 (plain bf16 operands, fp32 accumulation -- the
  * "bf16 MFMA path" of BASELINE configs[4] in its literal sense).  Process-wide; returns the previous value. */
@@ -165,6 +208,13 @@ int psn_gemm_tn_grouped_x3(int n_items, const PsnGemmTnItem* items, int64_t K, i
  * n_w x N weight gradient g^T H of a layer with few outputs.  workspace >= 2048*N floats */
 int psn_colsum(const float* X, const float* row_weight, int n_w, int64_t ldw, int64_t M, int N, int64_t ldx, float* out,
                int accumulate, float* workspace, void* stream);
+/* What psn_colsum would launch (host-only, as psn_gemm_plan): x_addr and workspace_addr are addresses as integers. */
+typedef struct {
+    int vec;            /* 1: colsum_partial_vec_kernel (N <= 256, float4 loads), 0: colsum_partial_kernel */
+    int nblocks;        /* row blocks of the partial kernel (at most 2048 / max(n_w, 1)) */
+    int64_t rows_per_block;
+} PsnColsumPlan;
+int psn_colsum_plan(int64_t x_addr, int n_w, int64_t M, int N, int64_t ldx, int64_t workspace_addr, PsnColsumPlan* plan);
 
 /* ------------------------------------------------------------------------
  * Points along rays.  Replaces the depth-profile arithmetic of stage1/model/rendering.py:110-176 (interval

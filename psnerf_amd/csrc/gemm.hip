@@ -1178,6 +1178,52 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
 
 }  // namespace psn
 
+// Every launch decision of psn_gemm as a pure host function of the shapes, the leading dimensions, the operand addresses (only
+// their low four bits and whether they are null are looked at), the workspace address and the requested split: psn_gemm launches
+// what this says, psn_gemm_plan reports it.  M > 0.
+static void gemm_plan(int64_t M, int N, int K, uintptr_t A, int64_t lda, uintptr_t B, int64_t ldb, uintptr_t C, int64_t ldc,
+                      uintptr_t aux_in, int64_t ld_aux_in, uintptr_t aux_in2, int64_t ld_aux_in2, uintptr_t aux_out,
+                      int64_t ld_aux_out, int split_k, uintptr_t workspace, PsnGemmPlan* p) {
+    using namespace psn;
+    if (split_k < 1) split_k = 1;
+    p->tiles_m = (M + BM - 1) / BM;
+    // 256-column tiles read each A row-panel once (measured +0-5 % on the Q x 256 x 256 layer GEMMs) but halve the
+    // workgroup count; keep them only when the grid still covers the 256 CUs several times over.
+    int bn = N > 128 ? 256 : 128;
+    if (bn == 256 && p->tiles_m * ((N + 255) / 256) * split_k < 2048) bn = 128;
+    p->bn = bn;
+    p->tiles_n = (N + bn - 1) / bn;
+    p->a_vec = ((A & 15) == 0) && (lda % 4 == 0);
+    p->b_vec = ((B & 15) == 0) && (ldb % 4 == 0);
+    p->auxin_vec = aux_in && ((aux_in & 15) == 0) && (ld_aux_in % 4 == 0);
+    p->auxin2_vec = aux_in2 && ((aux_in2 & 15) == 0) && (ld_aux_in2 % 4 == 0);
+    p->auxout_vec = aux_out && ((aux_out & 15) == 0) && (ld_aux_out % 4 == 0);
+    int kc = (K + split_k - 1) / split_k;
+    kc = ((kc + BK - 1) / BK) * BK;
+    split_k = (K + kc - 1) / kc;
+    p->k_chunk = kc;
+    p->split_k = split_k;
+    const int64_t MN = M * (int64_t)N;
+    // the tiles go to the caller's C, or with more than one slice to [split_k][M][N] partials in the workspace
+    p->c_vec = split_k > 1 ? ((workspace & 15) == 0) && (N % 4 == 0) && (MN % 4 == 0) : ((C & 15) == 0) && (ldc % 4 == 0);
+    p->reduce = split_k == 1 ? 0 : (N % 4 == 0 && ldc % 4 == 0 && ((C | workspace) & 15) == 0 && MN / 128 < (1ll << 31)) ? 2 : 1;
+    p->blocks = p->tiles_m * p->tiles_n * split_k;
+    p->nt = (kc < K ? kc : K) / BK + ((kc < K ? kc : K) % BK ? 1 : 0);
+    const int last = K - (split_k - 1) * kc;
+    p->nt_last = (last + BK - 1) / BK;
+    p->last_tile_rows = last - (p->nt_last - 1) * BK;
+}
+
+extern "C" int psn_gemm_plan(int64_t M, int N, int K, int64_t a_addr, int64_t lda, int64_t b_addr, int64_t ldb, int64_t c_addr,
+                             int64_t ldc, int64_t aux_in_addr, int64_t ld_aux_in, int64_t aux_in2_addr, int64_t ld_aux_in2,
+                             int64_t aux_out_addr, int64_t ld_aux_out, int split_k, int64_t workspace_addr, PsnGemmPlan* plan) {
+    PSN_CHECK_ARG(plan, "gemm_plan: null plan");
+    PSN_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm_plan: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
+    gemm_plan(M, N, K, (uintptr_t)a_addr, lda, (uintptr_t)b_addr, ldb, (uintptr_t)c_addr, ldc, (uintptr_t)aux_in_addr, ld_aux_in,
+              (uintptr_t)aux_in2_addr, ld_aux_in2, (uintptr_t)aux_out_addr, ld_aux_out, split_k, (uintptr_t)workspace_addr, plan);
+    return PSN_OK;
+}
+
 extern "C" int psn_gemm(int trans_a, int trans_b, int64_t M, int N, int K, const float* A, int64_t lda,
                         const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, int epilogue,
                         const float* aux_in, int64_t ld_aux_in, const float* aux_in2, int64_t ld_aux_in2,
@@ -1204,24 +1250,17 @@ extern "C" int psn_gemm(int trans_a, int trans_b, int64_t M, int N, int K, const
     g.bias = bias; g.epi = epilogue; g.aux_in = aux_in; g.ld_aux_in = ld_aux_in; g.aux_out = aux_out;
     g.aux_in2 = aux_in2; g.ld_aux_in2 = ld_aux_in2;
     g.ld_aux_out = ld_aux_out;
-    int64_t tiles_m = (M + BM - 1) / BM;
-    // 256-column tiles read each A row-panel once (measured +0-5 % on the Q x 256 x 256 layer GEMMs) but halve the
-    // workgroup count; keep them only when the grid still covers the 256 CUs several times over.
-    const int64_t tiles_m_ = (M + BM - 1) / BM;
-    int bn = N > 128 ? 256 : 128;
-    if (bn == 256 && tiles_m_ * ((N + 255) / 256) * (split_k < 1 ? 1 : split_k) < 2048) bn = 128;
-    g.tiles_n = (N + bn - 1) / bn;
-    g.n_tiles = tiles_m * g.tiles_n;
-    PSN_CHECK_ARG(g.n_tiles < (1ll << 31), "gemm: too many tiles");
-    g.a_vec = (((uintptr_t)A & 15) == 0) && (lda % 4 == 0);
-    g.b_vec = (((uintptr_t)B & 15) == 0) && (ldb % 4 == 0);
-    g.auxin_vec = aux_in && (((uintptr_t)aux_in & 15) == 0) && (ld_aux_in % 4 == 0);
-    g.auxin2_vec = aux_in2 && (((uintptr_t)aux_in2 & 15) == 0) && (ld_aux_in2 % 4 == 0);
-    g.auxout_vec = aux_out && (((uintptr_t)aux_out & 15) == 0) && (ld_aux_out % 4 == 0);
-    int kc = (K + split_k - 1) / split_k;
-    kc = ((kc + BK - 1) / BK) * BK;
-    split_k = (K + kc - 1) / kc;
-    g.k_chunk = kc;
+    PsnGemmPlan pl;
+    gemm_plan(M, N, K, (uintptr_t)A, lda, (uintptr_t)B, ldb, (uintptr_t)C, ldc, (uintptr_t)aux_in, ld_aux_in, (uintptr_t)aux_in2,
+              ld_aux_in2, (uintptr_t)aux_out, ld_aux_out, split_k, (uintptr_t)workspace, &pl);
+    PSN_CHECK_ARG(pl.tiles_m * pl.tiles_n < (1ll << 31), "gemm: too many tiles");
+    const int bn = pl.bn;
+    g.tiles_n = pl.tiles_n;
+    g.n_tiles = pl.tiles_m * pl.tiles_n;
+    g.a_vec = pl.a_vec; g.b_vec = pl.b_vec;
+    g.auxin_vec = pl.auxin_vec; g.auxin2_vec = pl.auxin2_vec; g.auxout_vec = pl.auxout_vec;
+    split_k = pl.split_k;
+    g.k_chunk = pl.k_chunk;
     g.split_stride = 0;
     if (split_k > 1) {
         g.C = workspace;
@@ -1229,7 +1268,7 @@ extern "C" int psn_gemm(int trans_a, int trans_b, int64_t M, int N, int K, const
         g.split_stride = M * (int64_t)N;
         g.epi = PSN_EPI_NONE;
     }
-    g.c_vec = (((uintptr_t)g.C & 15) == 0) && (g.ldc % 4 == 0) && (g.split_stride % 4 == 0);
+    g.c_vec = pl.c_vec;
     g.split_k = split_k;
     // column sums of A: straight to the caller's buffer, or per-split partials behind the C partials
     g.colsum = colsum_a == nullptr ? nullptr : (split_k > 1 ? workspace + (int64_t)split_k * M * N : colsum_a);
@@ -1248,7 +1287,7 @@ extern "C" int psn_gemm(int trans_a, int trans_b, int64_t M, int N, int K, const
     if (split_k > 1) {
         int64_t MN = M * (int64_t)N;
         const int acc = epilogue == PSN_EPI_ACCUM ? 1 : 0;
-        if (N % 4 == 0 && ldc % 4 == 0 && (((uintptr_t)C | (uintptr_t)workspace) & 15) == 0 && MN / 128 < (1ll << 31)) {
+        if (pl.reduce == 2) {
             hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3((unsigned)((MN + 127) / 128)), dim3(256), 0, st, workspace, MN, N,
                                ldc, split_k, acc, C);
         } else {
@@ -1264,6 +1303,100 @@ extern "C" int psn_gemm(int trans_a, int trans_b, int64_t M, int N, int K, const
         }
     }
     return PSN_OK;
+}
+
+// Every launch decision of psn_gemm_tn_grouped (and its argument checks) as a pure host function: the pointers of the items are
+// looked at as integers only (low four bits, null or not) and never followed.  The launcher launches what this says,
+// psn_gemm_tn_plan reports it.
+static int gemm_tn_plan(int n_items, const PsnGemmTnItem* items, int64_t K, int split_k, uintptr_t workspace, PsnGemmTnPlan* p) {
+    using namespace psn;
+    PSN_CHECK_ARG(items && n_items >= 1 && n_items <= kMaxGroup, "gemm_tn_grouped: n_items=%d (1..%d)", n_items, kMaxGroup);
+    PSN_CHECK_ARG(K > 0 && K < (1ll << 31), "gemm_tn_grouped: bad K");
+    if (split_k < 1) split_k = 1;
+    int kc = (int)((K + split_k - 1) / split_k);
+    kc = ((kc + BK - 1) / BK) * BK;
+    split_k = (int)((K + kc - 1) / kc);
+    // Products with 128 < M, N <= 256 (the hidden-layer gradients) take the one-tile-per-workgroup kernel: exactly one
+    // workgroup per (product, K slice), one workgroup per CU, so the slice count is chosen to fill 256 CUs once.
+    int big_products = 0, tall_products = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const PsnGemmTnItem& it = items[i];
+        PSN_CHECK_ARG(it.A && it.B && it.C && it.M > 0 && it.N > 0, "gemm_tn_grouped: item %d has a null operand or empty shape", i);
+        PSN_CHECK_ARG((it.A2 == nullptr) == (it.B2 == nullptr), "gemm_tn_grouped: item %d needs both A2 and B2", i);
+        const bool vec = (((uintptr_t)it.A | (uintptr_t)it.B | (uintptr_t)it.A2 | (uintptr_t)it.B2) & 15) == 0 && it.lda % 4 == 0 &&
+                         it.ldb % 4 == 0 && it.lda >= 4 && it.ldb >= 4 && (!it.A2 || (it.lda2 % 4 == 0 && it.ldb2 % 4 == 0 && it.lda2 >= 4 && it.ldb2 >= 4));
+        const bool big = vec && it.b_div == 0 && it.M > 128 && it.N > 128 && it.M <= T256 && it.N <= T256;
+        const bool tall = vec && it.b_div == 0 && it.M > 128 && it.M <= T256 && it.N <= T64;
+        p->kind[i] = big ? PSN_TN_BIG : tall ? PSN_TN_TALL : PSN_TN_TILE;
+        if (big) big_products += it.A2 ? 2 : 1;
+        if (tall) tall_products += it.A2 ? 2 : 1;
+        PSN_CHECK_ARG(it.b_div == 0 || (it.b_div > 0 && it.b_mod > 0 && !it.A2), "gemm_tn_grouped: item %d bad table mapping", i);
+        PSN_CHECK_ARG(it.B_tab2 == nullptr || (it.b_div > 0 && it.b2_div > 0 && it.b2_mod > 0 && it.b_split > 0 && it.b_split % 4 == 0 &&
+                                                it.b_split < it.N), "gemm_tn_grouped: item %d bad second table", i);
+        PSN_CHECK_ARG(it.k_rows >= 0 && it.k_rows <= K, "gemm_tn_grouped: item %d k_rows=%lld of K=%lld", i, (long long)it.k_rows, (long long)K);
+    }
+    int split_big = 1, kc_big = 0;
+    if (big_products > 0) {
+        int64_t want = 256 / big_products;
+        if (want < 1) want = 1;
+        if (want > K / 256) want = K / 256 > 0 ? K / 256 : 1;
+        kc_big = (int)((K + want - 1) / want);
+        kc_big = ((kc_big + TK - 1) / TK) * TK;
+        split_big = (int)((K + kc_big - 1) / kc_big);
+    }
+    // 256 x (<= 64) products (input-block gradients): HBM- / MFMA-co-limited, about one workgroup per CU in total
+    int split_tall = 1, kc_tall = 0;
+    if (tall_products > 0) {
+        int64_t want = 256 / tall_products;  // measured 192 ... 1024: 256 - 512 are best (kernel + reduction of the partial tiles)
+        if (want < 1) want = 1;
+        if (want > K / 256) want = K / 256 > 0 ? K / 256 : 1;
+        kc_tall = (int)((K + want - 1) / want);
+        kc_tall = ((kc_tall + BK - 1) / BK) * BK;
+        split_tall = (int)((K + kc_tall - 1) / kc_tall);
+    }
+    p->split_k = split_k; p->k_chunk = kc;
+    p->split_big = split_big; p->k_chunk_big = kc_big;
+    p->split_tall = split_tall; p->k_chunk_tall = kc_tall;
+    int64_t ws_off = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const PsnGemmTnItem& it = items[i];
+        const bool big = p->kind[i] == PSN_TN_BIG, tall = p->kind[i] == PSN_TN_TALL;
+        const int sk = big ? split_big : tall ? split_tall : split_k;
+        const int kci = big ? kc_big : tall ? kc_tall : kc;
+        const int kt = big ? TK : BK;  // rows of a k-tile
+        const int64_t Ki = it.k_rows > 0 ? it.k_rows : K;
+        p->dma[i] = big && it.N == T256;
+        p->splits[i] = sk * (it.A2 ? 2 : 1);
+        // the slices that hold rows of this product: all but the last are full
+        const int64_t live = (Ki + kci - 1) / kci, last = Ki - (live - 1) * kci;
+        p->live_slices[i] = (int)live;
+        p->nt[i] = live > 1 ? kci / kt : 0;
+        p->nt_last[i] = (int)((last + kt - 1) / kt);
+        p->last_tile_rows[i] = (int)(last - (int64_t)(p->nt_last[i] - 1) * kt);
+        // a modulo that cannot wrap ((K - 1) / div < mod) is passed as 0 = identity
+        p->b_mod[i] = (it.b_div > 0 && (K - 1) / it.b_div < it.b_mod) ? 0 : (int)it.b_mod;
+        p->b2_mod[i] = (it.b2_div > 0 && (K - 1) / it.b2_div < it.b2_mod) ? 0 : (int)it.b2_mod;
+        // which row-index arithmetic the slices of a table product run: float reciprocal while a slice ends at or below 2^24
+        p->index_path[i] = it.b_div == 0 ? 0 : ((kci < Ki ? kci : Ki) <= (1 << 24) ? PSN_TN_INDEX_FAST : 0) | (Ki > (1 << 24) ? PSN_TN_INDEX_DIV : 0);
+        p->a_vec[i] = (((uintptr_t)it.A & 15) == 0) && (it.lda % 4 == 0) && (!it.A2 || ((((uintptr_t)it.A2 & 15) == 0) && (it.lda2 % 4 == 0)));
+        p->b_vec[i] = (((uintptr_t)it.B & 15) == 0) && (it.ldb % 4 == 0) && (!it.B2 || ((((uintptr_t)it.B2 & 15) == 0) && (it.ldb2 % 4 == 0))) &&
+                      (!it.B_tab2 || ((((uintptr_t)it.B_tab2 & 15) == 0) && (it.ldb_tab2 % 4 == 0)));
+        const int64_t MN = (int64_t)it.M * it.N;
+        p->c_vec[i] = ((ws_off % 4) == 0) && (it.N % 4 == 0) && (MN % 4 == 0) && ((workspace & 15) == 0);
+        p->reduce_vec[i] = p->c_vec[i] && (it.ldc % 4 == 0) && (((uintptr_t)it.C & 15) == 0);
+        ws_off += MN * p->splits[i];
+        ws_off = (ws_off + 3) / 4 * 4;
+        if (it.colsum_a) ws_off += (int64_t)sk * it.M;
+        ws_off = (ws_off + 3) / 4 * 4;
+    }
+    p->workspace_floats = ws_off;
+    return PSN_OK;
+}
+
+extern "C" int psn_gemm_tn_plan(int n_items, const PsnGemmTnItem* items, int64_t K, int split_k, int64_t workspace_addr,
+                                PsnGemmTnPlan* plan) {
+    PSN_CHECK_ARG(plan, "gemm_tn_plan: null plan");
+    return gemm_tn_plan(n_items, items, K, split_k, (uintptr_t)workspace_addr, plan);
 }
 
 static int gemm_tn_grouped_impl(int n_items, const PsnGemmTnItem* items, int64_t K, int split_k, float* workspace,
@@ -1286,46 +1419,12 @@ extern "C" int psn_gemm_tn_grouped_x3(int n_items, const PsnGemmTnItem* items, i
 static int gemm_tn_grouped_impl(int n_items, const PsnGemmTnItem* items, int64_t K, int split_k, float* workspace,
                                 int64_t workspace_floats, void* stream, bool x3) {
     using namespace psn;
-    PSN_CHECK_ARG(items && n_items >= 1 && n_items <= kMaxGroup, "gemm_tn_grouped: n_items=%d (1..%d)", n_items, kMaxGroup);
-    PSN_CHECK_ARG(K > 0 && K < (1ll << 31) && workspace, "gemm_tn_grouped: bad K or null workspace");
-    if (split_k < 1) split_k = 1;
-    int kc = (int)((K + split_k - 1) / split_k);
-    kc = ((kc + BK - 1) / BK) * BK;
-    split_k = (int)((K + kc - 1) / kc);
-    // Products with 128 < M, N <= 256 (the hidden-layer gradients) take the one-tile-per-workgroup kernel: exactly one
-    // workgroup per (product, K slice), one workgroup per CU, so the slice count is chosen to fill 256 CUs once.
-    int big_products = 0, tall_products = 0;
-    for (int i = 0; i < n_items; ++i) {
-        const PsnGemmTnItem& it = items[i];
-        PSN_CHECK_ARG(it.A && it.B && it.C && it.M > 0 && it.N > 0, "gemm_tn_grouped: item %d has a null operand or empty shape", i);
-        PSN_CHECK_ARG((it.A2 == nullptr) == (it.B2 == nullptr), "gemm_tn_grouped: item %d needs both A2 and B2", i);
-        const bool vec = (((uintptr_t)it.A | (uintptr_t)it.B | (uintptr_t)it.A2 | (uintptr_t)it.B2) & 15) == 0 && it.lda % 4 == 0 &&
-                         it.ldb % 4 == 0 && it.lda >= 4 && it.ldb >= 4 && (!it.A2 || (it.lda2 % 4 == 0 && it.ldb2 % 4 == 0 && it.lda2 >= 4 && it.ldb2 >= 4));
-        if (vec && it.b_div == 0 && it.M > 128 && it.N > 128 && it.M <= T256 && it.N <= T256) big_products += it.A2 ? 2 : 1;
-        if (vec && it.b_div == 0 && it.M > 128 && it.M <= T256 && it.N <= T64) tall_products += it.A2 ? 2 : 1;
-        PSN_CHECK_ARG(it.b_div == 0 || (it.b_div > 0 && it.b_mod > 0 && !it.A2), "gemm_tn_grouped: item %d bad table mapping", i);
-        PSN_CHECK_ARG(it.B_tab2 == nullptr || (it.b_div > 0 && it.b2_div > 0 && it.b2_mod > 0 && it.b_split > 0 && it.b_split % 4 == 0 &&
-                                                it.b_split < it.N), "gemm_tn_grouped: item %d bad second table", i);
-    }
-    int split_big = 1, kc_big = 0;
-    if (big_products > 0) {
-        int64_t want = 256 / big_products;
-        if (want < 1) want = 1;
-        if (want > K / 256) want = K / 256 > 0 ? K / 256 : 1;
-        kc_big = (int)((K + want - 1) / want);
-        kc_big = ((kc_big + TK - 1) / TK) * TK;
-        split_big = (int)((K + kc_big - 1) / kc_big);
-    }
-    // 256 x (<= 64) products (input-block gradients): HBM- / MFMA-co-limited, about one workgroup per CU in total
-    int split_tall = 1, kc_tall = 0;
-    if (tall_products > 0) {
-        int64_t want = 256 / tall_products;  // measured 192 ... 1024: 256 - 512 are best (kernel + reduction of the partial tiles)
-        if (want < 1) want = 1;
-        if (want > K / 256) want = K / 256 > 0 ? K / 256 : 1;
-        kc_tall = (int)((K + want - 1) / want);
-        kc_tall = ((kc_tall + BK - 1) / BK) * BK;
-        split_tall = (int)((K + kc_tall - 1) / kc_tall);
-    }
+    PSN_CHECK_ARG(workspace, "gemm_tn_grouped: null workspace");
+    PsnGemmTnPlan pl;
+    const int rc = gemm_tn_plan(n_items, items, K, split_k, (uintptr_t)workspace, &pl);
+    if (rc != PSN_OK) return rc;
+    split_k = pl.split_k;
+    const int kc = pl.k_chunk, split_big = pl.split_big, kc_big = pl.k_chunk_big, split_tall = pl.split_tall, kc_tall = pl.k_chunk_tall;
     GroupedArgs gg, gb, gt;  // 128 x 128 tiles | 256 x 256 tiles | 256 x 64 tiles
     GroupedReduceArgs ra;
     gg.n = gb.n = gt.n = 0;
@@ -1334,19 +1433,14 @@ static int gemm_tn_grouped_impl(int n_items, const PsnGemmTnItem* items, int64_t
     for (int i = 0; i < n_items; ++i) {
         const PsnGemmTnItem& it = items[i];
         const int n_seg = it.A2 ? 2 : 1;
-        const bool vec = (((uintptr_t)it.A | (uintptr_t)it.B | (uintptr_t)it.A2 | (uintptr_t)it.B2) & 15) == 0 && it.lda % 4 == 0 &&
-                         it.ldb % 4 == 0 && it.lda >= 4 && it.ldb >= 4 && (!it.A2 || (it.lda2 % 4 == 0 && it.ldb2 % 4 == 0 && it.lda2 >= 4 && it.ldb2 >= 4));
-        const bool big = vec && it.b_div == 0 && it.M > 128 && it.N > 128 && it.M <= T256 && it.N <= T256;
-        const bool tall = vec && it.b_div == 0 && it.M > 128 && it.M <= T256 && it.N <= T64;
+        const bool big = pl.kind[i] == PSN_TN_BIG, tall = pl.kind[i] == PSN_TN_TALL;
         const int sk = big ? split_big : tall ? split_tall : split_k;
         GemmArgs& g = big ? gb.g[gb.n] : tall ? gt.g[gt.n] : gg.g[gg.n];
-        PSN_CHECK_ARG(it.k_rows >= 0 && it.k_rows <= K, "gemm_tn_grouped: item %d k_rows=%lld of K=%lld", i, (long long)it.k_rows, (long long)K);
         g.M = it.M; g.N = it.N; g.K = (int)(it.k_rows > 0 ? it.k_rows : K); g.A = it.A; g.lda = it.lda; g.B = it.B; g.ldb = it.ldb;
         g.A2 = it.A2; g.lda2 = it.lda2; g.B2 = it.B2; g.ldb2 = it.ldb2;
-        // a modulo that cannot wrap ((K - 1) / div < mod) is passed as 0 = identity
-        g.b_div = (int)it.b_div; g.b_mod = (it.b_div > 0 && (K - 1) / it.b_div < it.b_mod) ? 0 : (int)it.b_mod;
+        g.b_div = (int)it.b_div; g.b_mod = pl.b_mod[i];  // (0 = a modulo that cannot wrap)
         g.Bt2 = it.B_tab2; g.ldbt2 = it.ldb_tab2; g.b2_div = (int)it.b2_div; g.b_split = it.b_split;
-        g.b2_mod = (it.b2_div > 0 && (K - 1) / it.b2_div < it.b2_mod) ? 0 : (int)it.b2_mod;
+        g.b2_mod = pl.b2_mod[i];
         g.bias = nullptr; g.epi = PSN_EPI_NONE; g.aux_in = g.aux_in2 = nullptr; g.aux_out = nullptr;
         g.ld_aux_in = g.ld_aux_in2 = g.ld_aux_out = 0;
         g.tiles_n = (big || tall) ? 1 : (it.N + 127) / 128;
@@ -1354,22 +1448,21 @@ static int gemm_tn_grouped_impl(int n_items, const PsnGemmTnItem* items, int64_t
         g.k_chunk = big ? kc_big : tall ? kc_tall : kc;
         g.split_k = sk * n_seg;
         g.seg_splits = sk;
-        g.a_vec = (((uintptr_t)it.A & 15) == 0) && (it.lda % 4 == 0) && (!it.A2 || ((((uintptr_t)it.A2 & 15) == 0) && (it.lda2 % 4 == 0)));
-        g.b_vec = (((uintptr_t)it.B & 15) == 0) && (it.ldb % 4 == 0) && (!it.B2 || ((((uintptr_t)it.B2 & 15) == 0) && (it.ldb2 % 4 == 0))) &&
-                  (!it.B_tab2 || ((((uintptr_t)it.B_tab2 & 15) == 0) && (it.ldb_tab2 % 4 == 0)));
+        g.a_vec = pl.a_vec[i];
+        g.b_vec = pl.b_vec[i];
         g.auxin_vec = g.auxin2_vec = g.auxout_vec = 0;
         const int64_t MN = (int64_t)it.M * it.N;
         g.C = workspace + ws_off;
         g.ldc = it.N;
         g.split_stride = MN;
-        g.c_vec = ((ws_off % 4) == 0) && (it.N % 4 == 0) && (MN % 4 == 0) && (((uintptr_t)workspace & 15) == 0);
+        g.c_vec = pl.c_vec[i];
         ws_off += MN * g.split_k;
         ws_off = (ws_off + 3) / 4 * 4;
         g.colsum = it.colsum_a ? workspace + ws_off : nullptr;
         ReduceItem& r = ra.it[i];
         r.ws = g.C; r.cs_ws = g.colsum; r.C = it.C; r.colsum = it.colsum_a; r.MN = MN; r.ldc = it.ldc; r.N = it.N; r.M = it.M;
         r.splits = g.split_k; r.cs_splits = sk; r.accumulate = it.accumulate ? 1 : 0;
-        r.vec = g.c_vec && (it.ldc % 4 == 0) && (((uintptr_t)it.C & 15) == 0);
+        r.vec = pl.reduce_vec[i];
         r.blocks = (int)(r.vec ? (MN + 127) / 128 : (MN + 255) / 256);
         const int rb = r.blocks + (it.colsum_a ? (it.M + 255) / 256 : 0);
         if (rb > max_rblocks) max_rblocks = rb;
@@ -1412,6 +1505,26 @@ static int gemm_tn_grouped_impl(int n_items, const PsnGemmTnItem* items, int64_t
     return PSN_OK;
 }
 
+// The launch decisions of psn_colsum as a pure host function (psn_colsum_plan reports them).
+static void colsum_plan(uintptr_t X, int n_w, int64_t M, int N, int64_t ldx, uintptr_t workspace, PsnColsumPlan* p) {
+    const int nw1 = n_w > 0 ? n_w : 1;
+    int nblocks = (int)((M + 127) / 128);
+    if (nblocks > 2048 / nw1) nblocks = 2048 / nw1;  // workspace: 2048 * N floats
+    if (nblocks < 1) nblocks = 1;
+    int64_t rpb = (M + nblocks - 1) / nblocks;
+    if (rpb < 1) rpb = 1;
+    p->nblocks = nblocks;
+    p->rows_per_block = rpb;
+    p->vec = N <= 256 && N % 4 == 0 && ldx % 4 == 0 && ((X | workspace) & 15) == 0;
+}
+
+extern "C" int psn_colsum_plan(int64_t x_addr, int n_w, int64_t M, int N, int64_t ldx, int64_t workspace_addr, PsnColsumPlan* plan) {
+    PSN_CHECK_ARG(plan, "colsum_plan: null plan");
+    PSN_CHECK_ARG(N > 0 && M >= 0 && n_w >= 0 && n_w <= 4, "colsum_plan: bad shape");
+    colsum_plan((uintptr_t)x_addr, n_w, M, N, ldx, (uintptr_t)workspace_addr, plan);
+    return PSN_OK;
+}
+
 extern "C" int psn_colsum(const float* X, const float* row_weight, int n_w, int64_t ldw, int64_t M, int N, int64_t ldx,
                           float* out, int accumulate, float* workspace, void* stream) {
     using namespace psn;
@@ -1420,12 +1533,11 @@ extern "C" int psn_colsum(const float* X, const float* row_weight, int n_w, int6
     PSN_CHECK_ARG(row_weight == nullptr ? n_w == 0 : (n_w >= 1 && n_w <= 4 && ldw >= n_w), "colsum: n_w=%d (1..4 with weights, 0 without)", n_w);
     hipStream_t st = (hipStream_t)stream;
     const int nw1 = n_w > 0 ? n_w : 1;
-    int nblocks = (int)((M + 127) / 128);
-    if (nblocks > 2048 / nw1) nblocks = 2048 / nw1;  // workspace: 2048 * N floats
-    if (nblocks < 1) nblocks = 1;
-    int64_t rpb = (M + nblocks - 1) / nblocks;
-    if (rpb < 1) rpb = 1;
-    const bool vec = N <= 256 && N % 4 == 0 && ldx % 4 == 0 && (((uintptr_t)X | (uintptr_t)workspace) & 15) == 0;
+    PsnColsumPlan pl;
+    colsum_plan((uintptr_t)X, n_w, M, N, ldx, (uintptr_t)workspace, &pl);
+    const int nblocks = pl.nblocks;
+    const int64_t rpb = pl.rows_per_block;
+    const bool vec = pl.vec != 0;
     if (vec) {
         switch (n_w) {
             case 0: hipLaunchKernelGGL(colsum_partial_vec_kernel<0>, dim3(nblocks), dim3(256), 0, st, X, row_weight, ldw, M, N, ldx, rpb, workspace); break;

@@ -905,6 +905,82 @@ class wgrad_precision(object):
         return False
 
 
+def _tn_shape(it, K):
+    """(M, N) of the result of one item of gemm_tn_grouped, after the shape rules of its operands."""
+    A, B = it['A'], it['B']
+    if it.get('b_div') or it.get('b_mod'):  # B is a table: row k of the product reads B[(k // b_div) % b_mod]
+        assert A.shape[0] == K and int(it.get('b_mod') or B.shape[0]) <= B.shape[0] and it.get('A2') is None
+    else:
+        # a product may cover a row PREFIX of the pass (operands with fewer rows than items[0]): k_rows
+        assert A.shape[0] == B.shape[0] <= K, 'gemm_tn_grouped: a product has at most the K rows of the first one'
+    M, N = A.shape[1], B.shape[1]
+    Bt2 = it.get('B_tab2')
+    if Bt2 is not None:  # second table side by side: columns N .. N + Bt2.shape[1] - 1 of the virtual operand
+        assert N % 4 == 0 and int(it.get('b2_div', 0)) > 0
+        N += Bt2.shape[1]
+    return M, N
+
+
+def _tn_fill(e, it, K, ptr):
+    """The operand fields of one PsnGemmTnItem (everything but C and colsum_a); ptr(tensor, name) -> address."""
+    A, B = it['A'], it['B']
+    M, N = _tn_shape(it, K)
+    b_div, b_mod = int(it.get('b_div', 0)), int(it.get('b_mod', 0))
+    if b_div or b_mod:
+        b_div, b_mod = max(b_div, 1), (b_mod if b_mod else B.shape[0])
+    Bt2 = it.get('B_tab2')
+    A2, B2 = it.get('A2'), it.get('B2')
+    e.A, e.lda, e.B, e.ldb = ptr(A, 'A'), _ld(A), ptr(B, 'B'), _ld(B)
+    if A2 is not None:
+        assert A2.shape == A.shape and B2.shape == B.shape
+        e.A2, e.lda2, e.B2, e.ldb2 = ptr(A2, 'A2'), _ld(A2), ptr(B2, 'B2'), _ld(B2)
+    e.M, e.N = M, N
+    e.accumulate = int(bool(it.get('accumulate')))
+    e.b_div, e.b_mod = b_div, b_mod
+    if Bt2 is not None:
+        e.B_tab2, e.ldb_tab2 = ptr(Bt2, 'B_tab2'), _ld(Bt2)
+        e.b2_div, e.b2_mod, e.b_split = int(it['b2_div']), int(it.get('b2_mod', Bt2.shape[0])), B.shape[1]
+    e.k_rows = 0 if A.shape[0] == K else A.shape[0]
+
+
+def _addr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def gemm_plan(A, B, out, trans_a=False, trans_b=False, aux_in=None, aux_in2=None, aux_out=None, split_k=1, workspace_addr=0):
+    """What ``gemm`` would launch for operands placed like these: a host-only query (psn_gemm_plan), so the tensors may live
+    on any device -- only their shapes, row strides and the low bits of their addresses are looked at."""
+    K, M = A.shape if trans_a else A.shape[::-1]
+    N = B.shape[0] if trans_b else B.shape[1]
+    pl = PsnGemmPlan()  # noqa: F821
+    ld = lambda t: 0 if t is None else _ld(t)
+    _check(_lib.psn_gemm_plan(M, N, K, _addr(A), _ld(A), _addr(B), _ld(B), _addr(out), _ld(out), _addr(aux_in), ld(aux_in),
+                              _addr(aux_in2), ld(aux_in2), _addr(aux_out), ld(aux_out), split_k, workspace_addr,
+                              ctypes.addressof(pl)), 'gemm_plan')
+    return pl
+
+
+def gemm_tn_plan(items, split_k, workspace_addr=0):
+    """What one launch of ``gemm_tn_grouped`` would run for these items (at most GEMM_TN_MAX_ITEMS, explicit split_k): a
+    host-only query (psn_gemm_tn_plan); tensors on any device, 'out' required."""
+    K = items[0]['A'].shape[0]
+    arr = (PsnGemmTnItem * len(items))()  # noqa: F821
+    for e, it in zip(arr, items):
+        _tn_fill(e, it, K, lambda t, name: t.data_ptr())
+        e.C, e.ldc = it['out'].data_ptr(), _ld(it['out'])
+        e.colsum_a = 16 if it.get('colsum') else None
+    pl = PsnGemmTnPlan()  # noqa: F821
+    _check(_lib.psn_gemm_tn_plan(len(items), ctypes.addressof(arr), K, split_k, workspace_addr, ctypes.addressof(pl)), 'gemm_tn_plan')
+    return pl
+
+
+def colsum_plan(X, n_w=0, workspace_addr=0):
+    """What ``colsum`` would launch for an X placed like this one (host-only, psn_colsum_plan)."""
+    pl = PsnColsumPlan()  # noqa: F821
+    _check(_lib.psn_colsum_plan(_addr(X), n_w, X.shape[0], X.shape[1], _ld(X), workspace_addr, ctypes.addressof(pl)), 'colsum_plan')
+    return pl
+
+
 def gemm_tn_grouped(items, split_k=None, x3=None):
     """Weight gradients of one backward pass in one launch.  items: list of dicts with A [K,M], B [K,N] (row-major
     views, row stride allowed), optional A2 / B2 (second product summed into the same result), optional out [M,N]
@@ -950,38 +1026,17 @@ def gemm_tn_grouped(items, split_k=None, x3=None):
             kc = (kc + 15) // 16 * 16
             split_tall = -(-K // kc)
         for i, it in enumerate(chunk):
-            A, B = it['A'], it['B']
-            b_div, b_mod = int(it.get('b_div', 0)), int(it.get('b_mod', 0))
-            if b_div or b_mod:  # B is a table: row k of the product reads B[(k // b_div) % b_mod]
-                b_div, b_mod = max(b_div, 1), (b_mod if b_mod else B.shape[0])
-                assert A.shape[0] == K and b_mod <= B.shape[0] and it.get('A2') is None
-            else:
-                # a product may cover a row PREFIX of the pass (operands with fewer rows than items[0]): k_rows
-                assert A.shape[0] == B.shape[0] <= K, 'gemm_tn_grouped: a product has at most the K rows of the first one'
-            M, N = A.shape[1], B.shape[1]
-            Bt2 = it.get('B_tab2')
-            if Bt2 is not None:  # second table side by side: columns N .. N + Bt2.shape[1] - 1 of the virtual operand
-                assert N % 4 == 0 and int(it.get('b2_div', 0)) > 0
-                N += Bt2.shape[1]
+            M, N = _tn_shape(it, K)
             C = it.get('out')
             if C is None:
                 C = torch.empty(M, N, device=dev, dtype=torch.float32)
             assert C.shape == (M, N)
             cs = torch.empty(M, device=dev, dtype=torch.float32) if it.get('colsum') else None
-            A2, B2 = it.get('A2'), it.get('B2')
+            A2 = it.get('A2')
             e = arr[i]
-            e.A, e.lda, e.B, e.ldb = _mat_ptr(A, 'A'), _ld(A), _mat_ptr(B, 'B'), _ld(B)
-            if A2 is not None:
-                assert A2.shape == A.shape and B2.shape == B.shape
-                e.A2, e.lda2, e.B2, e.ldb2 = _mat_ptr(A2, 'A2'), _ld(A2), _mat_ptr(B2, 'B2'), _ld(B2)
-            e.C, e.ldc, e.M, e.N = _mat_ptr(C, 'out'), _ld(C), M, N
-            e.accumulate = int(bool(it.get('accumulate')))
-            e.b_div, e.b_mod = b_div, b_mod
-            if Bt2 is not None:
-                e.B_tab2, e.ldb_tab2 = _mat_ptr(Bt2, 'B_tab2'), _ld(Bt2)
-                e.b2_div, e.b2_mod, e.b_split = int(it['b2_div']), int(it.get('b2_mod', Bt2.shape[0])), B.shape[1]
+            _tn_fill(e, it, K, _mat_ptr)
+            e.C, e.ldc = _mat_ptr(C, 'out'), _ld(C)
             e.colsum_a = None if cs is None else cs.data_ptr()
-            e.k_rows = 0 if A.shape[0] == K else A.shape[0]
             sk = max(split_k, split_big) if is_big(it) else (max(split_k, split_tall) if kinds[id(it)] == 'tall' else split_k)
             need += (2 if A2 is not None else 1) * sk * M * N + sk * M + 16
             keep.append((C, cs))
@@ -1001,13 +1056,16 @@ def colsum(X, out=None, accumulate=False, row_weight=None):
     M, N = X.shape
     n_w, ldw, wp = 0, 0, None
     if row_weight is not None:
-        w2 = row_weight.reshape(M, -1)
+        w2 = row_weight if row_weight.dim() == 2 else row_weight.reshape(M, 1)  # (reshape(0, -1) is ambiguous: M may be 0)
         assert w2.stride(1) == 1 and 1 <= w2.shape[1] <= 4
         n_w, ldw, wp = w2.shape[1], w2.stride(0), _mat_ptr(w2, 'row_weight')
     if out is None:
         out = torch.empty((n_w, N) if n_w else (N,), device=X.device, dtype=torch.float32)
     ws = workspace(2048 * N, X.device)
-    _check(_lib.psn_colsum(_mat_ptr(X, 'X'), wp, n_w, ldw, M, N, _ld(X), out.data_ptr(), int(accumulate), ws.data_ptr(),
+    xp = _mat_ptr(X, 'X')
+    if M == 0:  # an empty tensor has no address: the workspace stands in for the operands, of which no row is read
+        xp, wp = ws.data_ptr(), (ws.data_ptr() if n_w else None)
+    _check(_lib.psn_colsum(xp, wp, n_w, ldw, M, N, _ld(X), out.data_ptr(), int(accumulate), ws.data_ptr(),
                            _stream()), 'colsum')
     return out
 
