@@ -1252,10 +1252,12 @@ def mlp_infer_bf16(desc, packed_w, final_bias, tab_a, a_div, a_mod, tab_b, b_div
         out = torch.empty(n_rows, desc.n_out, device=packed_w.device, dtype=torch.float32)
     assert packed_w.dtype == torch.bfloat16 and packed_w.is_cuda and packed_w.is_contiguous()
     assert final_bias.numel() == 32
+    ptrs = (_tptr(final_bias, 'final_bias'), _bf16_table(tab_a, 'tab_a'), _bf16_table(tab_b, 'tab_b'), _tptr(out, 'out'))
+    if n_rows == 0:  # validated like any launch; nothing to launch (an empty tensor has no device pointer to hand over)
+        return out
     with _Prof('mlp_infer_bf16', n_rows):
-        _check(_lib.psn_mlp_infer_bf16(ctypes.byref(desc), packed_w.data_ptr(), _tptr(final_bias, 'final_bias'),
-                                       _bf16_table(tab_a, 'tab_a'), a_div, a_mod, _bf16_table(tab_b, 'tab_b'), b_div, b_mod,
-                                       n_rows, _tptr(out, 'out'), _stream()), 'mlp_infer_bf16')
+        _check(_lib.psn_mlp_infer_bf16(ctypes.byref(desc), packed_w.data_ptr(), ptrs[0], ptrs[1], a_div, a_mod, ptrs[2], b_div, b_mod,
+                                       n_rows, ptrs[3], _stream()), 'mlp_infer_bf16')
     return out
 
 
@@ -1281,10 +1283,12 @@ def mlp_infer_bf16_grouped(desc, packed_w, final_bias, tab_a, group_bias, n_grou
             and group_bias.numel() == n_groups * n_in * 4096):
         raise RuntimeError('group_bias: must be a contiguous [n_groups * %d, 4096] bfloat16 HIP tensor' % n_in)
     assert out.numel() == n_groups * rows * desc.n_out
+    ptrs = (_tptr(final_bias, 'final_bias'), _bf16_table(tab_a, 'tab_a'), _tptr(out, 'out'))
+    if n_groups * rows == 0:
+        return out
     with _Prof('mlp_infer_bf16', n_groups * rows):
-        _check(_lib.psn_mlp_infer_bf16_grouped(ctypes.byref(desc), packed_w.data_ptr(), _tptr(final_bias, 'final_bias'),
-                                               _bf16_table(tab_a, 'tab_a'), rows, group_bias.data_ptr(), n_groups,
-                                               _tptr(out, 'out'), _stream()), 'mlp_infer_bf16_grouped')
+        _check(_lib.psn_mlp_infer_bf16_grouped(ctypes.byref(desc), packed_w.data_ptr(), ptrs[0], ptrs[1], rows, group_bias.data_ptr(), n_groups,
+                                               ptrs[2], _stream()), 'mlp_infer_bf16_grouped')
     return out
 
 
@@ -1323,9 +1327,12 @@ def mlp_infer_x3_grouped(desc, packed_w, bias_steps, final_bias, U, V, out=None,
             raise RuntimeError('%s: must be a contiguous bfloat16 HIP tensor' % nm)
     assert U.shape[1] == V.shape[1] == n_in * 256 and bias_steps.numel() == desc.n_hidden * 4096
     assert final_bias.numel() == 32 and out.numel() == n_groups * rows * desc.n_out
+    ptrs = (_tptr(final_bias, 'final_bias'), _tptr(U, 'U'), _tptr(V, 'V'), _tptr(out, 'out'))
+    if n_groups * rows == 0:
+        return out
     with _Prof('mlp_infer_x3', n_groups * rows, None if macs_per_row is None else 2.0 * macs_per_row * n_groups * rows):
-        _check(_lib.psn_mlp_infer_x3_grouped(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _tptr(final_bias, 'final_bias'),
-                                             _tptr(U, 'U'), rows, _tptr(V, 'V'), n_groups, _tptr(out, 'out'), _stream()), 'mlp_infer_x3_grouped')
+        _check(_lib.psn_mlp_infer_x3_grouped(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), ptrs[0],
+                                             ptrs[1], rows, ptrs[2], n_groups, ptrs[3], _stream()), 'mlp_infer_x3_grouped')
     return out
 
 
@@ -1346,11 +1353,14 @@ def mlp_infer_x3_occ(desc, packed_w, bias_steps, final_bias, points, pe_octaves,
         assert n_rows_dev.is_cuda and n_rows_dev.dtype == torch.int64 and n_rows_dev.numel() == 1
     if out_rows is not None:
         assert out_rows.is_cuda and out_rows.dtype == torch.int64 and out_rows.is_contiguous() and out_rows.numel() >= Q
+    ptrs = (_tptr(final_bias, 'final_bias'), _tptr(points, 'points'), _tptr(out, 'out'))
+    if Q == 0:
+        return out
     with _Prof('mlp_infer_x3_occ', Q, None if macs_per_row is None else 2.0 * macs_per_row * Q):
-        _check(_lib.psn_mlp_infer_x3_occ(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _tptr(final_bias, 'final_bias'),
-                                         _tptr(points, 'points'), Q, None if n_rows_dev is None else n_rows_dev.data_ptr(),
+        _check(_lib.psn_mlp_infer_x3_occ(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), ptrs[0],
+                                         ptrs[1], Q, None if n_rows_dev is None else n_rows_dev.data_ptr(),
                                          None if out_rows is None else out_rows.data_ptr(), int(pe_octaves), float(pe_scale),
-                                         int(skip_layer), int(pe_first), _tptr(out, 'out'), _stream()), 'mlp_infer_x3_occ')
+                                         int(skip_layer), int(pe_first), ptrs[2], _stream()), 'mlp_infer_x3_occ')
     return out
 
 
