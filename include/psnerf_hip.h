@@ -648,7 +648,9 @@ int psn_inverse_index(const int64_t* idx, int64_t ns, int64_t n_pix, int* inv, c
  *     width (uv = (pix % width, pix / width) as floats, dataset.py:138-140).
  * Outputs (any may be NULL = not produced; all contiguous): rgb [n_lights, n, 3]; object_mask_out / surface_mask_out [n] bytes;
  * uv [n, 2]; points_out / normal_out [n, 3]; visibility_out [n_lights, n]; vis_train_gt [n_vis, n]; sampling_idx_out [n] int64;
- * light_direction_out [n_lights, 3] = light_direction[lidx]. */
+ * light_direction_out [n_lights, 3] = light_direction[lidx].
+ * n = 0 (after the argument checks): PSN_OK without a launch, and NO output is written -- light_direction_out included, although
+ * its rows do not depend on n: a batch without pixels has no consumer, and the caller's buffer keeps what it held. */
 typedef struct {
     const void* images; int image_type; const float* lut;
     const unsigned char* object_mask; const unsigned char* surface_mask;

@@ -93,7 +93,7 @@ extern "C" int psn_view_batch(const PsnViewBatch* b, void* stream) {
     PSN_CHECK_ARG(b->light_direction_out == nullptr || (b->light_direction != nullptr && b->lidx != nullptr), "view_batch: light_direction table missing");
     PSN_CHECK_ARG(b->n_vis == 0 || (b->vis_plus != nullptr && b->vidx != nullptr && b->vis_train_gt != nullptr), "view_batch: vis_plus operands missing");
     PSN_CHECK_ARG(b->pix != nullptr || (b->pix0 >= 0 && b->pix0 + b->n <= b->hw), "view_batch: identity pixel range outside the view");
-    if (b->n == 0) return PSN_OK;
+    if (b->n == 0) return PSN_OK;  // the contract of the header: nothing is written, light_direction_out included
     const int jobs = b->n_lights + 1 + (b->visibility_out != nullptr ? b->n_lights : 0) + b->n_vis;
     hipLaunchKernelGGL(psn::view_batch_kernel, dim3((unsigned)((b->n + 255) / 256), (unsigned)jobs), dim3(256), 0, (hipStream_t)stream, *b);
     PSN_CHECK_LAUNCH("view_batch");

@@ -89,6 +89,23 @@ def _tptr(t, name, dtype=torch.float32, allow_none=False, contiguous=True):
     return t.data_ptr()
 
 
+def _out(out, shape, like, name, dtype=torch.float32):
+    """The output of a wrapper: a fresh tensor, or the caller's ``out`` (contiguous, of that shape and dtype, on the device of
+    ``like``) -- a view into a larger buffer is fine."""
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=dtype)
+    if not isinstance(out, torch.Tensor) or out.device != like.device or out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise RuntimeError('%s: out must be a contiguous %s device tensor of shape %s' % (name, str(dtype)[len('torch.'):], tuple(shape)))
+    return out
+
+
+def _eptr(t, stand_in):
+    """Device pointer of a tensor that may be EMPTY: torch gives an empty tensor a null data pointer, which the entry points
+    refuse before they look at the count.  An empty operand is never read, so the address of ``stand_in`` (a live tensor of
+    the same call) travels in its place."""
+    return t.data_ptr() if t.numel() else stand_in.data_ptr()
+
+
 def _bits_ptr(t, name):
     """Device pointer of a tensor of sign-bit words ([rows, 4] int64, contiguous)."""
     if t.dim() != 2 or t.shape[1] != 4:
@@ -134,22 +151,24 @@ def composite_bwd(alpha, rgb, d_rgb_out, d_acc, white_bg):
 
 
 # --------------------------------------------------------------------------- positional encoding
-def pe_encode(x, n_freqs, out_stride=None, scale=1.0):
+def pe_encode(x, n_freqs, out_stride=None, scale=1.0, out=None):
     """x [n,3] -> [n, out_stride] = [x, sin(2^k x), cos(2^k x)]_k, zero padded to out_stride."""
     n = x.shape[0]
     width = 3 + 6 * n_freqs
     out_stride = width if out_stride is None else out_stride
-    out = torch.empty(n, out_stride, device=x.device, dtype=torch.float32)
+    out = _out(out, (n, out_stride), x, 'pe_encode')
     _check(_lib.psn_pe_encode(_tptr(x, 'x'), n, n_freqs, float(scale), _tptr(out, 'out'), out_stride, _stream()),
            'pe_encode')
     return out
 
 
-def app_input(p, v, normal, n_freqs):
+def app_input(p, v, normal, n_freqs, out=None):
     """[Q, 64] input table of the stage-1 appearance chain: [p | gamma(v / |v|) | normal | 0] (psn_app_input)."""
     Q = p.shape[0]
     assert p.shape == v.shape == normal.shape == (Q, 3)
-    out = torch.empty(Q, 64, device=p.device, dtype=torch.float32)
+    out = _out(out, (Q, 64), p, 'app_input')
+    if out.data_ptr() % 16:
+        raise RuntimeError('app_input: out must be 16-byte aligned (the kernel stores four columns at a time)')
     p, v, normal = p.contiguous(), v.contiguous(), normal.contiguous()
     if Q:
         _check(_lib.psn_app_input(_tptr(p, 'p'), _tptr(v, 'v'), _tptr(normal, 'normal'), Q, int(n_freqs), out.data_ptr(), _stream()),
@@ -157,20 +176,20 @@ def app_input(p, v, normal, n_freqs):
     return out
 
 
-def pe_encode_jvp(x, t, n_freqs, out_stride, scale=1.0):
+def pe_encode_jvp(x, t, n_freqs, out_stride, scale=1.0, out=None):
     """J_PE(x) t: tangent t [n,3] -> [n, out_stride]."""
     n = x.shape[0]
-    out = torch.empty(n, out_stride, device=x.device, dtype=torch.float32)
+    out = _out(out, (n, out_stride), x, 'pe_encode_jvp')
     _check(_lib.psn_pe_encode_jvp(_tptr(x, 'x'), _tptr(t, 't'), n, n_freqs, float(scale), _tptr(out, 'out'), out_stride,
                                   _stream()), 'pe_encode_jvp')
     return out
 
 
-def pe_encode_bwd(x, d_out, n_freqs, scale=1.0, add=None):
+def pe_encode_bwd(x, d_out, n_freqs, scale=1.0, add=None, out=None):
     """d_out (and ``add``, a second gradient summed in first): row-major views [n, >= 3 + 6 n_freqs] -- column ranges of
     wider tensors are fine (row stride = stride(0))."""
     n = x.shape[0]
-    d_x = torch.empty_like(x)
+    d_x = torch.empty_like(x) if out is None else _out(out, x.shape, x, 'pe_encode_bwd')
     assert d_out.shape[1] >= 3 + 6 * n_freqs and (add is None or add.shape[1] >= 3 + 6 * n_freqs)
     _check(_lib.psn_pe_encode_bwd(_tptr(x, 'x'), _mat_ptr(d_out, 'd_out'), n, n_freqs, float(scale), _ld(d_out),
                                   None if add is None else _mat_ptr(add, 'add'), 0 if add is None else _ld(add),
@@ -274,14 +293,15 @@ def copy_group(pairs):
 
 
 def mask_count(mask_a, mask_b=None, out=None):
-    """Number of elements with mask_a & mask_b (torch.bool tensors of one size) -> float32 device tensor [1], one launch."""
+    """Number of elements with mask_a & mask_b (torch.bool tensors of one size) -> float32 device tensor [1], one launch (empty
+    masks included: the kernel writes the 0)."""
     assert mask_a.is_cuda and mask_a.dtype == torch.bool and mask_a.is_contiguous()
     if mask_b is not None:
         assert mask_b.is_cuda and mask_b.dtype == torch.bool and mask_b.is_contiguous() and mask_b.numel() == mask_a.numel()
     if out is None:
         out = torch.empty(1, device=mask_a.device, dtype=torch.float32)
     assert out.is_cuda and out.dtype == torch.float32 and out.numel() == 1
-    _check(_lib.psn_mask_count(mask_a.data_ptr(), None if mask_b is None else mask_b.data_ptr(), mask_a.numel(), out.data_ptr(), _stream()),
+    _check(_lib.psn_mask_count(_eptr(mask_a, out), None if mask_b is None else _eptr(mask_b, out), mask_a.numel(), out.data_ptr(), _stream()),
            'mask_count')
     return out
 
@@ -321,7 +341,7 @@ def surface_index(mask, capacity):
     assert mask.is_cuda and mask.dtype == torch.bool and mask.dim() == 1 and mask.is_contiguous()
     idx = torch.empty(int(capacity), device=mask.device, dtype=torch.int64)
     count = torch.empty(1, device=mask.device, dtype=torch.float32)
-    _check(_lib.psn_surface_index(mask.data_ptr(), mask.numel(), int(capacity), idx.data_ptr(), count.data_ptr(), _stream()), 'surface_index')
+    _check(_lib.psn_surface_index(_eptr(mask, idx), mask.numel(), int(capacity), idx.data_ptr(), count.data_ptr(), _stream()), 'surface_index')
     return idx, count
 
 
@@ -510,55 +530,61 @@ def row_adam(items, idx, step_sizes_dev=None):
     _check(_lib.psn_row_adam(len(items), ctypes.addressof(arr), idx.data_ptr(), idx.numel(), _stream()), 'row_adam')
 
 
-def normalize_rows_fwd(x, eps=1e-12):
+def normalize_rows_fwd(x, eps=1e-12, out=None):
     """F.normalize(x, dim=-1) for [n, 3] rows in one launch."""
     assert x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()
-    y = torch.empty_like(x)
+    y = torch.empty_like(x) if out is None else _out(out, x.shape, x, 'normalize_rows_fwd')
     _check(_lib.psn_normalize_rows_fwd(_tptr(x, 'x'), x.shape[0], float(eps), y.data_ptr(), _stream()), 'normalize_rows_fwd')
     return y
 
 
-def normalize_rows_bwd(x, g, eps=1e-12):
+def normalize_rows_bwd(x, g, eps=1e-12, out=None):
     assert x.shape == g.shape and x.shape[1] == 3 and x.is_contiguous() and g.is_contiguous()
-    dx = torch.empty_like(x)
+    dx = torch.empty_like(x) if out is None else _out(out, x.shape, x, 'normalize_rows_bwd')
     _check(_lib.psn_normalize_rows_bwd(_tptr(x, 'x'), _tptr(g, 'g'), x.shape[0], float(eps), dx.data_ptr(), _stream()), 'normalize_rows_bwd')
     return dx
 
 
-def light_rows_fwd(dir_table, int_table, idx, eps=1e-12):
-    """(normalize(dir_table[idx]) [L, 3], int_table[idx] [L, 1] or None) in one launch (stage2/trainer.py:376-379)."""
+def light_rows_fwd(dir_table, int_table, idx, eps=1e-12, out=None):
+    """(normalize(dir_table[idx]) [L, 3], int_table[idx] [L, 1] or None) in one launch (stage2/trainer.py:376-379).
+    out: (d [L, 3], it [L, 1] or None) to write into; an empty index list gives empty outputs without a launch."""
     L = idx.shape[0]
     assert dir_table.dim() == 2 and dir_table.shape[1] == 3 and dir_table.is_contiguous() and idx.dtype == torch.int64 and idx.is_contiguous()
-    d = torch.empty(L, 3, device=dir_table.device, dtype=torch.float32)
+    d = _out(None if out is None else out[0], (L, 3), dir_table, 'light_rows_fwd')
     it = None
     if int_table is not None:
         assert int_table.shape == (dir_table.shape[0], 1) and int_table.is_contiguous()
-        it = torch.empty(L, 1, device=dir_table.device, dtype=torch.float32)
+        it = _out(None if out is None else out[1], (L, 1), dir_table, 'light_rows_fwd')
+    if L == 0:
+        return d, it
     _check(_lib.psn_light_rows_fwd(_tptr(dir_table, 'dir_table'), _tptr(int_table, 'int_table', allow_none=True), _tptr(idx, 'idx', torch.int64), L, float(eps),
                                    d.data_ptr(), None if it is None else it.data_ptr(), _stream()), 'light_rows_fwd')
     return d, it
 
 
-def light_rows_bwd(dir_table, idx, g_dir, g_int, eps=1e-12):
-    """Dense table gradients ([n, 3] or None, [n, 1] or None) of light_rows_fwd, one launch, no separate zero fill."""
+def light_rows_bwd(dir_table, idx, g_dir, g_int, eps=1e-12, out=None):
+    """Dense table gradients ([n, 3] or None, [n, 1] or None) of light_rows_fwd, one launch, no separate zero fill (an empty
+    index list still launches: the kernel writes the zeros).  out: (dd, di) to write into."""
     n = dir_table.shape[0]
-    dd = torch.empty(n, 3, device=dir_table.device, dtype=torch.float32) if g_dir is not None else None
-    di = torch.empty(n, 1, device=dir_table.device, dtype=torch.float32) if g_int is not None else None
+    dd = _out(None if out is None else out[0], (n, 3), dir_table, 'light_rows_bwd') if g_dir is not None else None
+    di = _out(None if out is None else out[1], (n, 1), dir_table, 'light_rows_bwd') if g_int is not None else None
     for t in (g_dir, g_int):
         assert t is None or t.is_contiguous()
-    _check(_lib.psn_light_rows_bwd(_tptr(dir_table, 'dir_table'), _tptr(idx, 'idx', torch.int64), idx.shape[0], n, float(eps),
-                                   _tptr(g_dir, 'g_dir', allow_none=True),
-                                   _tptr(g_int, 'g_int', allow_none=True), None if dd is None else dd.data_ptr(), None if di is None else di.data_ptr(),
+    for t in (g_dir, g_int):
+        assert t is None or t.shape[0] == idx.shape[0]
+    ept = lambda t, name, dt=torch.float32: None if t is None else (_tptr(t, name, dt) if t.numel() else _eptr(t, dir_table))
+    _check(_lib.psn_light_rows_bwd(_tptr(dir_table, 'dir_table'), ept(idx, 'idx', torch.int64), idx.shape[0], n, float(eps),
+                                   ept(g_dir, 'g_dir'), ept(g_int, 'g_int'), None if dd is None else dd.data_ptr(), None if di is None else di.data_ptr(),
                                    _stream()), 'light_rows_bwd')
     return dd, di
 
 
-def camera_rays(uv, pose, intrinsics, idx=None, scale=1.0):
+def camera_rays(uv, pose, intrinsics, idx=None, scale=1.0, out=None):
     """Normalised camera rays (rend_util.py:90-147, 4 x 4 pose) of the pixels idx (all when None) -> [n, 3], times scale."""
     assert uv.dim() == 3 and uv.shape[0] == 1 and uv.shape[2] == 2 and uv.is_contiguous()
     assert pose.shape == (1, 4, 4) and intrinsics.shape[0] == 1 and intrinsics.shape[1:] == (4, 4) and pose.is_contiguous() and intrinsics.is_contiguous()
     n = uv.shape[1] if idx is None else idx.shape[0]
-    out = torch.empty(n, 3, device=uv.device, dtype=torch.float32)
+    out = _out(out, (n, 3), uv, 'camera_rays')
     _check(_lib.psn_camera_rays(_tptr(uv, 'uv'), _tptr(pose, 'pose'), _tptr(intrinsics, 'intrinsics'),
                                 _tptr(idx, 'idx', torch.int64, allow_none=True), n, float(scale),
                                 out.data_ptr(), _stream()), 'camera_rays')
@@ -1197,9 +1223,10 @@ def mlp_infer(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod
 
 
 # --------------------------------------------------------------------------- weight normalisation
-def weight_norm_fwd(vs, gs, scales):
-    """[v_l * (g_l / |v_l|_row) * scale_l] for all layers in one launch (<= 16 per launch)."""
-    out = [torch.empty_like(v) for v in vs]
+def weight_norm_fwd(vs, gs, scales, out=None):
+    """[v_l * (g_l / |v_l|_row) * scale_l] for all layers in one launch (<= 16 per launch); out: the list of w_l to write into."""
+    out = [torch.empty_like(v) for v in vs] if out is None else [_out(o, v.shape, v, 'weight_norm_fwd') for o, v in zip(out, vs)]
+    assert len(out) == len(vs) == len(gs)
     for c0 in range(0, len(vs), WN_MAX_ITEMS):
         n = min(WN_MAX_ITEMS, len(vs) - c0)
         arr = (PsnWnItem * n)()
@@ -1213,10 +1240,11 @@ def weight_norm_fwd(vs, gs, scales):
     return out
 
 
-def weight_norm_bwd(vs, gs, scales, dws):
-    """(dv_l, dg_l) of weight_norm_fwd for the output gradients dws (dense, same shapes as vs)."""
-    dvs = [torch.empty_like(v) for v in vs]
-    dgs = [torch.empty_like(g) for g in gs]
+def weight_norm_bwd(vs, gs, scales, dws, out=None):
+    """(dv_l, dg_l) of weight_norm_fwd for the output gradients dws (dense, same shapes as vs); out: (dvs, dgs) to write into."""
+    dvs = [torch.empty_like(v) for v in vs] if out is None else [_out(o, v.shape, v, 'weight_norm_bwd') for o, v in zip(out[0], vs)]
+    dgs = [torch.empty_like(g) for g in gs] if out is None else [_out(o, g.shape, g, 'weight_norm_bwd') for o, g in zip(out[1], gs)]
+    assert len(dvs) == len(dgs) == len(vs) == len(gs) == len(dws)
     for c0 in range(0, len(vs), WN_MAX_ITEMS):
         n = min(WN_MAX_ITEMS, len(vs) - c0)
         arr = (PsnWnItem * n)()
