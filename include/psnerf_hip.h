@@ -58,7 +58,7 @@ int psn_pe_encode(const float* x, int64_t n, int n_freqs, float scale, float* ou
 /* Input table of the stage-1 appearance network, stage1/model/network.py:128-138 (infer_app: cat[p, gamma(view), normal,
  * features]; gamma from :141-150 on the normalised view direction, rendering.py:185-190): out [n, 64] row r =
  * [p (3) | v / |v| (3) | sin, cos bands of v / |v| (6 n_freqs) | normal (3) | zeros].  The 256 features are not part of the
- * table: they are the fused chain's initial activations (psn_mlp_infer act_init). */
+ * table: they are the fused chain's initial activations (psn_mlp_launch act_init). */
 int psn_app_input(const float* p, const float* v, const float* normal, int64_t n, int n_freqs, float* out, void* stream);
 
 /* forward-mode: t [n,3] tangent of x -> d(encoding) [n, out_stride] = J_PE(x) t  (the transpose of
@@ -155,7 +155,7 @@ typedef struct {
     int accumulate;                  /* 0: C = ..., 1: C += ... */
     float* colsum_a;                 /* NULL or [M] */
     int64_t b_div, b_mod;            /* b_div > 0: B is a TABLE and row k of the product reads its row (k / b_div) % b_mod
-                                        (the virtual input rows of psn_mlp_infer: d W_in of a layer whose input block
+                                        (the virtual input rows of psn_mlp_launch: d W_in of a layer whose input block
                                         repeats per light or per point, summed over all K rows without expanding it) */
     const float* B_tab2; int64_t ldb_tab2;   /* optional second table (needs b_div > 0): the columns b_split .. N-1 of the */
     int64_t b2_div, b2_mod;                  /* virtual B come from B_tab2[(k / b2_div) % b2_mod, n - b_split]           */
@@ -264,7 +264,7 @@ enum {
     PSN_ACT_SOFTPLUS_BWD = 6,  /* act = a1 z + 100 (1 - a1) a2     (softplus double-backward combine)        */
     PSN_ACT_HEAD = 7,          /* side output: z is dumped, the activations are left untouched              */
     PSN_ACT_RELU_BITS = 8,     /* act = z * bit: RELU_MASK with the mask as sign bits -- a1 = [n_rows, 4] uint64 words written
-                                  by psn_mlp_infer_bits (bit 4 mt + r of word (row, g) = feature 16 mt + 4 g + r was > 0)    */
+                                  by psn_mlp_launch save_bits_ptrs (bit 4 mt + r of word (row, g) = feature 16 mt + 4 g + r was > 0)    */
     /* single-dump forms of the softplus chains (stage1/model/network.py:85-120): a1 = the dumped softplus OUTPUT a of the forward
        layer; s = sigmoid(100 z) = 1 - exp(-100 a) is re-formed in the kernel (a < 0, impossible for a softplus, gives s = 0) */
     PSN_ACT_MUL_AUX_A = 9,     /* act = z * s(a1);                 second = z                               */
@@ -300,7 +300,7 @@ typedef struct {
     int in_kt_a;  /* K tiles (of 32 floats) per row of feature table A (1..4) */
     int in_kt_b;  /* K tiles per row of table B (0 = unused); in_kt_a + in_kt_b <= 4 */
     int init_stride; /* floats per row of the init tables (multiple of the hidden width), 0 if no layer uses init_off */
-    int w_format; /* PSN_W_F32, or PSN_W_BF16X2 (experiment; 256-wide networks through psn_mlp_infer* / psn_mlp_infer_pe* /
+    int w_format; /* PSN_W_F32, or PSN_W_BF16X2 (experiment; 256-wide networks through psn_mlp_launch / psn_mlp_infer_pe* /
                      psn_march_sweep, not psn_root_find): every block with n_mt >= 2 is packed as two bf16 planes and multiplied as
                      three bf16 partial products, see PsnPackItem.format */
     PsnMlpLayer layers[PSN_MLP_MAX_LAYERS];
@@ -325,20 +325,19 @@ typedef struct {
 } PsnPackItem;
 int psn_mlp_pack_layers(int n_items, const PsnPackItem* items, void* stream);
 
-/* Row q of the virtual input matrix is [ A[(q / a_div) % a_mod, :] | B[(q / b_div) % b_mod, :] ];
- * tables are row-major with strides in_kt_a*32 / in_kt_b*32 floats, 16-byte aligned.
- * Because a layer that reads the input block is linear in it, W_in [A_row | B_row] = W_a A_row + W_b B_row
- * can be precomputed once per table row instead of once per (A,B) pair: init_a / init_b
- * ([rows, init_stride], indexed like tab_a / tab_b; init_b may be NULL) hold those partial products and the
- * layers with init_off >= 0 start their accumulators from them (tab_a may then be NULL if no layer has n_kt_in > 0).
- * save_ptrs (HOST array of n_layers-1 device pointers, entries or the array itself may be NULL): for rows >=
- * save_row0 the post-activation output of hidden layer l is also written row-major to save_ptrs[l]
- * [n_rows - save_row0, 256] -- the training rows of stage2/model/renderer.py:251-262 ride along with the
- * gradient-free rows and leave exactly what their backward pass needs.
- * mask_ptrs / aux2_ptrs (HOST arrays of n_layers device pointers or NULL): row-major [n_rows, 256] operands a1 / a2
- * of the layers' activation programs; save2_ptrs: second dumps (same indexing as save_ptrs).  With n_out == 0 there is no final layer and `out` may be NULL: together with
- * transposed weight packs, an init table holding d h of the last hidden layer, masks = the dumped activations and
- * save_ptrs = the d z outputs this runs the ReLU BACKWARD chain d h_{l-1} = W_l^T (d h_l * relu'(h_l)).
+/* The operands of one launch of the fused engine (psn_mlp_launch); {0} = nothing optional (a_div and a_mod must still be >= 1).
+ * Row q of the virtual input matrix is [ A[(q / a_div) % a_mod, :] | B[(q / b_div) % b_mod, :] ]; tables are row-major with
+ * strides in_kt_a*32 / in_kt_b*32 floats, 16-byte aligned.  Because a layer that reads the input block is linear in it,
+ * W_in [A_row | B_row] = W_a A_row + W_b B_row can be precomputed once per table row instead of once per (A,B) pair: init_a /
+ * init_b ([rows, init_stride], indexed like tab_a / tab_b; init_b may be NULL) hold those partial products and the layers with
+ * init_off >= 0 start their accumulators from them (tab_a may then be NULL if no layer has n_kt_in > 0).
+ * save_ptrs (HOST array of n_layers-1 device pointers, entries or the array itself may be NULL): for rows >= save_row0 the
+ * post-activation output of hidden layer l is also written row-major to save_ptrs[l] [n_rows - save_row0, 256] -- the training
+ * rows of stage2/model/renderer.py:251-262 ride along with the gradient-free rows and leave exactly what their backward pass needs.
+ * mask_ptrs / aux2_ptrs (HOST arrays of n_layers device pointers or NULL): row-major [n_rows, 256] operands a1 / a2 of the
+ * layers' activation programs; save2_ptrs: second dumps (same indexing as save_ptrs).  With n_out == 0 there is no final layer
+ * and `out` may be NULL: together with transposed weight packs, an init table holding d h of the last hidden layer, masks = the
+ * dumped activations and save_ptrs = the d z outputs this runs the ReLU BACKWARD chain d h_{l-1} = W_l^T (d h_l * relu'(h_l)).
  * act_init (or NULL): row-major [act_init_rows, 256] initial activations, so that layer 0 may already read them; rows >=
  * act_init_rows (1 .. n_rows) start from zeros (a gradient that exists for a row prefix only: the colour network's d features
  * when the surface-normal points ride behind the render samples, stage1/model/rendering.py:196-212).
@@ -349,42 +348,42 @@ int psn_mlp_pack_layers(int n_items, const PsnPackItem* items, void* stream);
  * dump_tiles (HOST array of 2 * PSN_MLP_MAX_LAYERS words, or NULL = everything): bit mt of word l / word
  * PSN_MLP_MAX_LAYERS + l set = the 16-column tile mt of layer l's first / second dump is written; for dumps of which only
  * a column range is read afterwards (the raw sweep values that feed d logit / d pe, network.py:108-120).
- * out [n_rows, n_out]. */
-int psn_mlp_infer(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* tab_a,
-                  int64_t a_div, int64_t a_mod, const float* tab_b, int64_t b_div, int64_t b_mod,
-                  const float* init_a, const float* init_b, float* const* save_ptrs, int64_t save_row0,
-                  const float* const* mask_ptrs, const float* const* aux2_ptrs, float* const* save2_ptrs,
-                  const float* act_init, int64_t act_init_rows, const float* rk_coef, const float* rk_basis, int rk_k,
-                  const uint32_t* dump_tiles, int64_t n_rows, float* out, void* stream);
-/* psn_mlp_infer (plain forward: no chain operands) over a PADDED row set -- the stage-2 visibility rows of
- * stage2/model/renderer.py:191-200 when the surface-pixel list has a fixed capacity (psn_surface_index: one captured HIP graph
- * serves batches with different surface counts).  The rows [0, save_row0) come in groups of live_period rows (one group per
- * shading light; live_period a multiple of 64, save_row0 a multiple of live_period), of which the first live_count[0] -- a
- * float ON THE DEVICE, psn_surface_index's count -- are real.  64-row blocks that hold padding only are not evaluated: their
- * outputs are zeros.  Every other row is evaluated exactly as by psn_mlp_infer (bit-identical), the rows from save_row0 on
- * (the supervision rows, whose dumps a backward pass reads) all of them.  The grid enumerates the evaluated blocks first, so
- * that the skipped ones do not unbalance the XCDs. */
-int psn_mlp_infer_padded(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* tab_a,
-                         int64_t a_div, int64_t a_mod, const float* tab_b, int64_t b_div, int64_t b_mod,
-                         const float* init_a, const float* init_b, float* const* save_ptrs, int64_t save_row0,
-                         int64_t n_rows, float* out, const float* live_count, int64_t live_period, void* stream);
-/* Workgroup order of the psn_mlp_infer* launches whose rows are (group, point) pairs, row = group * P + point with a_div = 1,
+ * out [n_rows, n_out].
+ * live_count, live_period (NULL, 0: every row is real; one without the other is refused) -- a plain forward launch (no chain
+ * operands) over a PADDED row set, the stage-2 visibility rows of stage2/model/renderer.py:191-200 when the surface-pixel list has
+ * a fixed capacity (psn_surface_index: one captured HIP graph serves batches with different surface counts).  The rows
+ * [0, save_row0) come in groups of live_period rows (one group per shading light; live_period a multiple of 64, save_row0 a
+ * multiple of live_period), of which the first live_count[0] -- a float ON THE DEVICE, psn_surface_index's count -- are real.
+ * 64-row blocks that hold padding only are not evaluated: their outputs are zeros.  Every other row is evaluated exactly as
+ * without a count (bit-identical), the rows from save_row0 on (the supervision rows, whose dumps a backward pass reads) all of
+ * them.  The grid enumerates the evaluated blocks first, so that the skipped ones do not unbalance the XCDs.
+ * save_bits_ptrs (HOST array like save_ptrs, refused without it; NULL, or NULL per layer: none) -- a plain forward launch with
+ * activation dumps (stage2/model/renderer.py:251-262: the supervision rows of the visibility network, :127-143 / :163-189 the
+ * normal / BRDF networks) ALSO leaves the sign bits of every dumped activation behind: save_bits_ptrs[l] [n_rows - save_row0, 4]
+ * uint64.  The ReLU-backward chain (PSN_ACT_RELU_BITS, the words passed as that layer's aux1 in mask_ptrs) reads 32 bytes per row
+ * and layer instead of the 1 KB activation row -- the same d z = d h * (h > 0), bit for bit. */
+typedef struct {
+    const float* tab_a; int64_t a_div, a_mod; const float* tab_b; int64_t b_div, b_mod; const float* init_a; const float* init_b;
+    float* const* save_ptrs; unsigned long long* const* save_bits_ptrs; int64_t save_row0;
+    const float* const* mask_ptrs; const float* const* aux2_ptrs; float* const* save2_ptrs;
+    const float* act_init; int64_t act_init_rows; const float* rk_coef; const float* rk_basis; int rk_k; const uint32_t* dump_tiles;
+    int64_t n_rows; float* out; const float* live_count; int64_t live_period;
+} PsnMlpLaunch;
+/* What a launch ran: the kernel instantiation (chain or lean engine; width16 = hidden width / 16 = 16, 8 or 4; src = where the rows
+ * come from: 0 tables, 1 / 4 the row- / feature-parallel root finder, 2 points, 3 the sweep) and its grid.  `path` (or NULL) is
+ * filled when a launch happens and zeroed otherwise (n_rows <= 0, a refusal); psn_mlp_last_path gives the same for the calling
+ * thread's last launch of the engine through ANY entry (psn_mlp_infer_pe*, psn_march_sweep and psn_root_find included). */
+typedef struct { int chain, width16, src, trim, from_a, x3, tb_lds, pm_groups; int64_t blocks, pm_period; } PsnMlpPath;
+int psn_mlp_launch(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const PsnMlpLaunch* launch, PsnMlpPath* path,
+                   void* stream);
+int psn_mlp_last_path(PsnMlpPath* path);
+/* Workgroup order of the psn_mlp_launch launches whose rows are (group, point) pairs, row = group * P + point with a_div = 1,
  * b_div = a_mod = P, n_rows = P * b_mod -- the light-major row set of stage2/model/renderer.py:163,183-193.  1 (default): the
  * 64-row blocks are visited point-tile-major with the group (light) running fastest and every XCD takes a contiguous eighth of
  * that order, so that the workgroups resident at one time share a few point tiles and the per-point init table is read from
  * the fabric once instead of once per light; 0: row order (the light-major sweep).  A row's result does not depend on the
  * order (bit-identical outputs and dumps).  Process-wide; returns the previous value. */
 int psn_mlp_block_order(int point_major);
-/* psn_mlp_infer, plain forward with activation dumps (stage2/model/renderer.py:251-262: the supervision rows of the visibility
- * network, :127-143 / :163-189 the normal / BRDF networks), that ALSO leaves the sign bits of every dumped activation behind:
- * save_bits_ptrs[l] [n_rows - save_row0, 4] uint64 (NULL per layer: none).  The ReLU-backward chain (PSN_ACT_RELU_BITS, the words
- * passed as that layer's aux1 in mask_ptrs) reads 32 bytes per row and layer instead of the 1 KB activation row -- the same
- * d z = d h * (h > 0), bit for bit.  live_count / live_period as for psn_mlp_infer_padded (NULL, 0: every row is real). */
-int psn_mlp_infer_bits(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* tab_a,
-                       int64_t a_div, int64_t a_mod, const float* tab_b, int64_t b_div, int64_t b_mod,
-                       const float* init_a, const float* init_b, float* const* save_ptrs,
-                       unsigned long long* const* save_bits_ptrs, int64_t save_row0, int64_t n_rows, float* out,
-                       const float* live_count, int64_t live_period, void* stream);
 
 /* Dense per-pixel outputs of the stage-2 model, stage2/model/renderer.py:145-152,204-264: dense [B, N, C] = fill
  * everywhere except dense[b, idx[r], c] = rows[(b Ns + r) row_stride + c col_stride] (light-major surface rows;
@@ -431,8 +430,8 @@ int psn_shadow_points(const float* surf, const float* ldir, int64_t n_surf, int 
 /* Positional encoding + network in one launch (stage1/model/network.py:141-150 feeding :85-101; the occupancy queries of
  * the march sweep, rendering.py:410-470, and of the shadow rays, :378-408): points [n_rows, 3]; the encoding
  * gamma(pe_scale * p) with pe_octaves bands is formed in the kernel prologue, in registers, with the expressions of
- * psn_pe_encode -- out equals psn_pe_encode (stride 64) followed by psn_mlp_infer bit for bit, and the [n_rows, 64] table
- * never exists.  desc / packed_w / packed_b as for psn_mlp_infer, restricted to: 256-wide hidden layers without init tables,
+ * psn_pe_encode -- out equals psn_pe_encode (stride 64) followed by psn_mlp_launch bit for bit, and the [n_rows, 64] table
+ * never exists.  desc / packed_w / packed_b as for psn_mlp_launch, restricted to: 256-wide hidden layers without init tables,
  * in_kt_a = 2 (one 64-column block), biases packed back to back, n_out <= 32.  out [n_rows, n_out]. */
 int psn_mlp_infer_pe(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* points, int64_t n_rows,
                      int pe_octaves, float pe_scale, float* out, void* stream);
@@ -460,7 +459,7 @@ int psn_march_sweep(const PsnMlpDesc* desc, const float* packed_w, const float* 
 
 /* Fused secant refinement, stage1/model/rendering.py:525-555: n_iter regula-falsi iterations for every ray inside ONE
  * launch -- query point origin + d_pred * dir, its positional encoding (pe_octaves bands, input scaled by pe_scale), the
- * occupancy network (desc / packed_w / packed_b as for psn_mlp_infer: 256-wide, one output, PSN_OUT_OCC, input block =
+ * occupancy network (desc / packed_w / packed_b as for psn_mlp_launch: 256-wide, one output, PSN_OUT_OCC, input block =
  * one 64-column encoding) and the bracket update -- instead of one encoding + network + update launch per iteration.
  * bracket [4, n_rays] as written by psn_first_crossing (not modified); d_out [n_rays] = the final d_pred. */
 int psn_root_find(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* origin, const float* dir,
@@ -703,7 +702,7 @@ int psn_weight_norm_bwd(int n_items, const PsnWnItem* items, void* stream);
  * the 256-wide ReLU networks of stage2/model/renderer.py:34-49 on v_mfma_f32_32x32x16_bf16 -- weights, input
  * features and post-ReLU activations rounded to bf16 (RNE), fp32 accumulation, fp32 output.  Replaces the no-grad
  * evaluation of visibility_net in stage2/eval.py:199-218 (via renderer.py:191-200) when the caller opts in; training
- * and every parity-gated path use psn_mlp_infer (exact fp32).
+ * and every parity-gated path use psn_mlp_launch (exact fp32).
  *
  * Network: n_hidden hidden layers of width 256 with ReLU; layer 0 reads the input block only, layer l >= 1 reads the
  * previous activations and, if has_in[l], the input block again (skip connection cat[y, x]); a final layer with
@@ -766,7 +765,7 @@ int psn_bf16_pack_group_bias(const float* V, int64_t n, uint16_t* dst, void* str
  *     stages of 2 k-steps: every hidden layer >= 1 = its 16 activation k-steps; final layer = one stage [16 k-steps][3 planes],
  *     + 56 KB of padding); bias_steps [n_hidden][8 KB] (used for the layers without an input block).  The layers that read
  *     the input block start from U[n] + V[g] (both fp32, [., n_input_layers * 256]): U = W_a x_n per row, V = W_b x_g + b per
- *     group, as the init tables of psn_mlp_infer; layer 0 is that sum alone.  out [n_groups * rows_per_group, n_out] fp32.
+ *     group, as the init tables of psn_mlp_launch; layer 0 is that sum alone.  out [n_groups * rows_per_group, n_out] fp32.
  * ---------------------------------------------------------------------- */
 int psn_x3_pack(const float* W, int64_t ldw, int rows, int cols, int permuted, int n_ot, int ks0, int n_ks, uint16_t* dst, void* stream);
 int psn_x3_pack_bias(const float* V, int64_t n, uint16_t* dst, void* stream);

@@ -79,7 +79,7 @@ struct InferArgs {
     int n_steps;
     int* skip;               // [n_rays] or nullptr: INT_MAX - b = block b of this ray holds a sign change (the lowest such b wins), 0 = none
     unsigned long long* n_blocks;  // optional: counts the 64-step blocks that were evaluated (measurement only)
-    // SRC == 0, lean variant, optional (psn_mlp_infer_padded): the rows in front of save_row0 come in groups of live_period
+    // SRC == 0, lean variant, optional (PsnMlpLaunch.live_count): the rows in front of save_row0 come in groups of live_period
     // (one group per light), of which only the first live_count[0] (a device-side float: psn_surface_index's count) are real;
     // the all-padding 64-row blocks are not evaluated (zeros)
     const float* live_count;
@@ -489,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void mlp_infer_kernel(InferArgs g) {
     const int lj = lane & 15, lg = lane >> 4;
     int64_t blk_ = (int64_t)blockIdx.x;
     if constexpr (SRC == 0 && !CHAIN) {
-        // psn_mlp_infer_padded: the rows [0, save_row0) are groups of live_period rows (64 | live_period, 64 | save_row0) of which
+        // padded row sets (live_count): the rows [0, save_row0) are groups of live_period rows (64 | live_period, 64 | save_row0) of which
         // the first live_count[0] are real.  The hardware hands workgroup i to XCD i % 8, and the all-padding blocks sit at the END
         // of every group: skipped where they stand they all fall on the same XCDs while the others carry the full work (measured:
         // the launch no faster than without the skip).  So the grid enumerates the REAL blocks first -- row order: workgroup i
@@ -1336,15 +1336,73 @@ extern "C" int psn_mlp_block_order(int point_major) {
     return g_point_major.exchange(point_major != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
-static int mlp_infer_impl(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* tab_a,
-                          int64_t a_div, int64_t a_mod, const float* tab_b, int64_t b_div, int64_t b_mod,
-                          const float* init_a, const float* init_b, float* const* save_ptrs, int64_t save_row0,
-                          const float* const* mask_ptrs, const float* const* aux2_ptrs, float* const* save2_ptrs,
-                          const float* act_init, int64_t act_init_rows, const float* rk_coef, const float* rk_basis, int rk_k,
-                          const uint32_t* dump_tiles, int64_t n_rows, float* out, const float* live_count, int64_t live_period,
-                          unsigned long long* const* save_bits_ptrs, void* stream) {
+// Every instantiation of mlp_infer_kernel, keyed (chain, NMT, SRC, trim, from_a, x3), and the feature-parallel root finder under
+// SRC = kSrcRootFp.  This is the one list of them, and launch_infer below the one place that launches from it.
+constexpr int kSrcRootFp = 4;
+#define PSN_MLP_KERNELS(K)                                                    \
+    K(false, 16, 0, true, false, true)   K(false, 16, 0, false, false, true)  \
+    K(true, 16, 0, true, true, true)     K(true, 16, 0, false, true, true)    \
+    K(true, 16, 0, true, false, true)    K(true, 16, 0, false, false, true)   \
+    K(true, 16, 0, true, true, false)    K(true, 16, 0, false, true, false)   \
+    K(true, 16, 0, true, false, false)   K(false, 16, 0, true, false, false)  \
+    K(true, 16, 0, false, false, false)  K(false, 16, 0, false, false, false) \
+    K(true, 8, 0, false, false, false)   K(false, 8, 0, false, false, false)  \
+    K(true, 4, 0, false, false, false)   K(false, 4, 0, false, false, false)  \
+    K(false, 16, 2, true, false, true)   K(false, 16, 2, true, false, false)  \
+    K(false, 16, 3, true, false, true)   K(false, 16, 3, true, false, false)  \
+    K(false, 16, 1, true, false, false)
+struct InferKernel { int chain, nmt, src, trim, from_a, x3; void (*fn)(psn::InferArgs); };
+#define PSN_KERNEL_ROW(C, N, S, T, F, X) {C, N, S, T, F, X, psn::mlp_infer_kernel<C, N, S, T, F, X>},
+static const InferKernel kInferKernels[] = {PSN_MLP_KERNELS(PSN_KERNEL_ROW){0, 16, kSrcRootFp, 1, 0, 0, psn::root_find_fp_kernel}};
+#undef PSN_KERNEL_ROW
+
+static PsnMlpPath mlp_path(int chain, int nmt, int src, int trim, int from_a, int x3, int64_t blocks) {
+    PsnMlpPath p = {};
+    p.chain = chain; p.width16 = nmt; p.src = src; p.trim = trim; p.from_a = from_a; p.x3 = x3; p.blocks = blocks;
+    return p;
+}
+
+// The one launch of the engine: p names the instantiation and the grid; what was launched is kept for psn_mlp_last_path.
+static thread_local PsnMlpPath t_last_path;
+extern "C" int psn_mlp_last_path(PsnMlpPath* path) {
+    PSN_CHECK_ARG(path != nullptr, "mlp_last_path: null pointer");
+    *path = t_last_path;
+    return PSN_OK;
+}
+static int launch_infer(const char* what, const psn::InferArgs& a, PsnMlpPath p, void* stream) {
     using namespace psn;
-    PSN_CHECK_ARG(desc && packed_w && packed_b && (out || desc->n_out == 0), "mlp_infer: null pointer");
+    p.tb_lds = a.tb_lds; p.pm_period = a.pm_period; p.pm_groups = a.pm_groups;
+    PSN_CHECK_ARG(p.blocks < (1ll << 31), "%s: too many rows", what);
+    const InferKernel* k = nullptr;
+    for (const InferKernel& r : kInferKernels)
+        if (r.chain == p.chain && r.nmt == p.width16 && r.src == p.src && r.trim == p.trim && r.from_a == p.from_a && r.x3 == p.x3) k = &r;
+    PSN_CHECK_ARG(k != nullptr, "%s: no kernel is built for chain=%d n_mt16=%d src=%d trim=%d from_a=%d x3=%d", what, p.chain, p.width16, p.src,
+                  p.trim, p.from_a, p.x3);
+    // two weight stages + the biases and init rows; the sweep adds one flag per row; the feature-parallel root finder has static LDS
+    const size_t lds_floats = p.src == kSrcRootFp ? 0 : 2 * kStageFloats + PSN_MLP_MAX_LAYERS * 256 + (p.src == 3 ? kWaves * 16 : 0);
+    hipLaunchKernelGGL(k->fn, dim3((unsigned)p.blocks), dim3(kWaves * 64), lds_floats * sizeof(float), (hipStream_t)stream, a);
+    PSN_CHECK_LAUNCH(what);
+    t_last_path = p;
+    return PSN_OK;
+}
+
+// The InferArgs fields every launch fills: the network, identity index maps, the bias count, rows and output, every dump tile selected.
+static psn::InferArgs base_args(const PsnMlpDesc& d, const float* packed_w, const float* packed_b, int64_t n_rows, float* out) {
+    psn::InferArgs a = {};
+    a.d = d; a.w = packed_w; a.b = packed_b; a.a_div = 1; a.a_mod = 1; a.b_div = 1; a.b_mod = 1; a.n_rows = n_rows; a.out = out;
+    const int width = d.layers[0].n_mt * 32;
+    a.n_bias = d.n_out > 0 ? (d.n_layers - 1) * width + (d.n_out > 32 ? 64 : 32) : d.n_layers * width;
+    for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) { a.save_tiles[l] = 0xFFFFFFFFu; a.save2_tiles[l] = 0xFFFFFFFFu; }
+    return a;
+}
+
+// psn_mlp_launch, first half: validates the launch and plans it -- a = the kernel arguments, p = instantiation and grid (p.blocks = 0:
+// no rows, nothing to launch).  The lean / chain rule is stated here and nowhere else.
+static int mlp_infer_plan(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const PsnMlpLaunch& o, psn::InferArgs& a,
+                          PsnMlpPath& p) {
+    using namespace psn;
+    p = {};
+    PSN_CHECK_ARG(desc && packed_w && packed_b && (o.out || desc->n_out == 0), "mlp_infer: null pointer");
     const PsnMlpDesc& d = *desc;
     PSN_CHECK_ARG(d.n_layers >= 1 && d.n_layers <= PSN_MLP_MAX_LAYERS, "mlp_infer: n_layers=%d", d.n_layers);
     PSN_CHECK_ARG(d.in_kt_a >= 0 && d.in_kt_b >= 0 && d.in_kt_a + d.in_kt_b <= 4, "mlp_infer: input tiles %d+%d", d.in_kt_a, d.in_kt_b);
@@ -1353,16 +1411,19 @@ static int mlp_infer_impl(const PsnMlpDesc* desc, const float* packed_w, const f
         uses_in = uses_in || d.layers[l].n_kt_in > 0;
         uses_init = uses_init || d.layers[l].init_off >= 0;
     }
-    PSN_CHECK_ARG(!uses_in || (tab_a && d.in_kt_a >= 1 && (d.in_kt_b == 0 || tab_b)), "mlp_infer: input table missing");
-    PSN_CHECK_ARG((rk_coef == nullptr) == (rk_basis == nullptr) && (rk_coef == nullptr ? rk_k == 0 : (rk_k >= 1 && rk_k <= 4)),
-                  "mlp_infer: rank-k init needs coefficients, basis and 1 <= k <= 4 (k=%d)", rk_k);
-    PSN_CHECK_ARG(!uses_init || ((init_a || rk_coef) && d.init_stride >= 64 && d.init_stride % 4 == 0), "mlp_infer: init table missing");
-    PSN_CHECK_ARG((((uintptr_t)rk_basis) & 15) == 0, "mlp_infer: rk_basis must be 16-byte aligned");
-    PSN_CHECK_ARG((((uintptr_t)init_a | (uintptr_t)init_b) & 15) == 0, "mlp_infer: init tables must be 16-byte aligned");
+    PSN_CHECK_ARG(!uses_in || (o.tab_a && d.in_kt_a >= 1 && (d.in_kt_b == 0 || o.tab_b)), "mlp_infer: input table missing");
+    PSN_CHECK_ARG((o.rk_coef == nullptr) == (o.rk_basis == nullptr) && (o.rk_coef == nullptr ? o.rk_k == 0 : (o.rk_k >= 1 && o.rk_k <= 4)),
+                  "mlp_infer: rank-k init needs coefficients, basis and 1 <= k <= 4 (k=%d)", o.rk_k);
+    PSN_CHECK_ARG(!uses_init || ((o.init_a || o.rk_coef) && d.init_stride >= 64 && d.init_stride % 4 == 0), "mlp_infer: init table missing");
+    PSN_CHECK_ARG((((uintptr_t)o.rk_basis) & 15) == 0, "mlp_infer: rk_basis must be 16-byte aligned");
+    PSN_CHECK_ARG((((uintptr_t)o.init_a | (uintptr_t)o.init_b) & 15) == 0, "mlp_infer: init tables must be 16-byte aligned");
     PSN_CHECK_ARG(d.n_out >= 0 && d.n_out <= 64, "mlp_infer: n_out=%d", d.n_out);
-    PSN_CHECK_ARG(a_div >= 1 && a_mod >= 1 && (d.in_kt_b == 0 || (b_div >= 1 && b_mod >= 1)), "mlp_infer: bad index map");
-    PSN_CHECK_ARG((((uintptr_t)tab_a | (uintptr_t)tab_b | (uintptr_t)packed_w | (uintptr_t)packed_b) & 15) == 0,
+    PSN_CHECK_ARG(o.a_div >= 1 && o.a_mod >= 1 && (d.in_kt_b == 0 || (o.b_div >= 1 && o.b_mod >= 1)), "mlp_infer: bad index map");
+    PSN_CHECK_ARG((((uintptr_t)o.tab_a | (uintptr_t)o.tab_b | (uintptr_t)packed_w | (uintptr_t)packed_b) & 15) == 0,
                   "mlp_infer: buffers must be 16-byte aligned");
+    PSN_CHECK_ARG(o.save_bits_ptrs == nullptr || o.save_ptrs != nullptr, "mlp_infer: save_bits_ptrs needs save_ptrs (the sign bits are those of the dumps)");
+    PSN_CHECK_ARG((o.live_count != nullptr) == (o.live_period != 0), "mlp_infer: live_count and live_period go together (live_count %s, period=%lld)",
+                  o.live_count ? "given" : "is null", (long long)o.live_period);
     // hidden width: 256 (8 output tiles of 32) or 128 (4), the same for every hidden layer of the network
     // A network that is only a final layer is refused: the barrier that publishes bias_lds sits in the hidden-layer loop, so with no
     // hidden layer the final layer would read its bias from LDS before any barrier (nothing in the project launches that shape).
@@ -1378,24 +1439,24 @@ static int mlp_infer_impl(const PsnMlpDesc* desc, const float* packed_w, const f
         PSN_CHECK_ARG(!last || (L.n_kt_in == 0 && L.n_kt_act == hid), "mlp_infer: the final layer reads the hidden activations only");
         PSN_CHECK_ARG(L.b_off == (int64_t)l * width, "mlp_infer: biases must be packed back to back (one hidden width per layer)");
         PSN_CHECK_ARG(L.n_kt_act == 0 || L.n_kt_act == hid || (L.n_kt_act == hid - 1 && hid > 1), "mlp_infer: layer %d n_kt_act=%d (0, n_mt - 1 or n_mt)", l, L.n_kt_act);
-        PSN_CHECK_ARG(l > 0 || L.n_kt_act == 0 || act_init != nullptr, "mlp_infer: layer 0 cannot read activations without act_init");
+        PSN_CHECK_ARG(l > 0 || L.n_kt_act == 0 || o.act_init != nullptr, "mlp_infer: layer 0 cannot read activations without act_init");
         PSN_CHECK_ARG(L.n_kt_in + L.n_kt_act >= 1 || (l == 0 && L.init_off >= 0 && d.n_layers > 1), "mlp_infer: layer %d has no input", l);
         PSN_CHECK_ARG(L.init_off < 0 || (!last && L.init_off + width <= d.init_stride && L.init_off % 4 == 0), "mlp_infer: layer %d bad init_off", l);
         PSN_CHECK_ARG((L.w_off % 4) == 0 && (L.b_off % 4) == 0, "mlp_infer: layer %d offsets must be multiples of 4 floats", l);
     }
-    if (n_rows <= 0) return PSN_OK;
-    InferArgs a = {};
-    a.d = d; a.w = packed_w; a.b = packed_b; a.ta = tab_a; a.a_div = a_div; a.a_mod = a_mod;
-    a.tb = tab_b; a.b_div = b_div > 0 ? b_div : 1; a.b_mod = b_mod > 0 ? b_mod : 1; a.n_rows = n_rows; a.out = out;
-    a.init_a = init_a; a.init_b = init_b;
-    a.n_bias = d.n_out > 0 ? (d.n_layers - 1) * width + (d.n_out > 32 ? 64 : 32) : d.n_layers * width;
-    for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) a.save[l] = (save_ptrs != nullptr && l < (d.n_out > 0 ? d.n_layers - 1 : d.n_layers)) ? save_ptrs[l] : nullptr;
-    a.save_row0 = save_row0;
+    if (o.n_rows <= 0) return PSN_OK;
+    a = base_args(d, packed_w, packed_b, o.n_rows, o.out);
+    a.ta = o.tab_a; a.a_div = o.a_div; a.a_mod = o.a_mod;
+    a.tb = o.tab_b; a.b_div = o.b_div > 0 ? o.b_div : 1; a.b_mod = o.b_mod > 0 ? o.b_mod : 1;
+    a.init_a = o.init_a; a.init_b = o.init_b;
+    const int n_hidden = d.n_out > 0 ? d.n_layers - 1 : d.n_layers;
+    for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) a.save[l] = (o.save_ptrs != nullptr && l < n_hidden) ? o.save_ptrs[l] : nullptr;
+    a.save_row0 = o.save_row0;
     for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) {
         const bool in_range = l < d.n_layers;
-        a.mask[l] = (mask_ptrs != nullptr && in_range) ? mask_ptrs[l] : nullptr;
-        a.aux2[l] = (aux2_ptrs != nullptr && in_range) ? aux2_ptrs[l] : nullptr;
-        a.save2[l] = (save2_ptrs != nullptr && in_range) ? save2_ptrs[l] : nullptr;
+        a.mask[l] = (o.mask_ptrs != nullptr && in_range) ? o.mask_ptrs[l] : nullptr;
+        a.aux2[l] = (o.aux2_ptrs != nullptr && in_range) ? o.aux2_ptrs[l] : nullptr;
+        a.save2[l] = (o.save2_ptrs != nullptr && in_range) ? o.save2_ptrs[l] : nullptr;
         PSN_CHECK_ARG(((((uintptr_t)a.mask[l]) | ((uintptr_t)a.aux2[l]) | ((uintptr_t)a.save2[l])) & 15) == 0,
                       "mlp_infer: aux / dump tensors must be 16-byte aligned");
         if (in_range) {
@@ -1413,47 +1474,43 @@ static int mlp_infer_impl(const PsnMlpDesc* desc, const float* packed_w, const f
     }
     for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) PSN_CHECK_ARG((((uintptr_t)a.save[l]) & 15) == 0, "mlp_infer: save buffers must be 16-byte aligned");
     const int rows_per_block = kWaves * 16;
-    int64_t blocks = (n_rows + rows_per_block - 1) / rows_per_block;
-    PSN_CHECK_ARG(blocks < (1ll << 31), "mlp_infer: too many rows");
-    a.act_init = act_init;
-    a.act_init_rows = act_init_rows;
-    a.rk_coef = rk_coef; a.rk_basis = rk_basis; a.rk_k = rk_k;
-    for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) {
-        a.save_tiles[l] = dump_tiles ? dump_tiles[l] : 0xFFFFFFFFu;
-        a.save2_tiles[l] = dump_tiles ? dump_tiles[PSN_MLP_MAX_LAYERS + l] : 0xFFFFFFFFu;
+    int64_t blocks = (o.n_rows + rows_per_block - 1) / rows_per_block;
+    a.act_init = o.act_init;
+    a.act_init_rows = o.act_init_rows;
+    a.rk_coef = o.rk_coef; a.rk_basis = o.rk_basis; a.rk_k = o.rk_k;
+    for (int l = 0; o.dump_tiles != nullptr && l < PSN_MLP_MAX_LAYERS; ++l) {
+        a.save_tiles[l] = o.dump_tiles[l];
+        a.save2_tiles[l] = o.dump_tiles[PSN_MLP_MAX_LAYERS + l];
     }
-    PSN_CHECK_ARG((((uintptr_t)act_init) & 15) == 0, "mlp_infer: act_init must be 16-byte aligned");
-    PSN_CHECK_ARG(act_init == nullptr || (act_init_rows >= 1 && act_init_rows <= n_rows), "mlp_infer: act_init_rows=%lld of %lld rows", (long long)act_init_rows, (long long)n_rows);
-    bool chain = act_init != nullptr || rk_coef != nullptr || dump_tiles != nullptr;
+    PSN_CHECK_ARG((((uintptr_t)o.act_init) & 15) == 0, "mlp_infer: act_init must be 16-byte aligned");
+    PSN_CHECK_ARG(o.act_init == nullptr || (o.act_init_rows >= 1 && o.act_init_rows <= o.n_rows), "mlp_infer: act_init_rows=%lld of %lld rows", (long long)o.act_init_rows, (long long)o.n_rows);
+    // the chain engine runs whatever the lean one has no code for: initial activations, rank-k init, dump tile masks, the activation
+    // programs behind SOFTPLUS100, second dumps and aux operands
+    bool chain = o.act_init != nullptr || o.rk_coef != nullptr || o.dump_tiles != nullptr;
     for (int l = 0; l < d.n_layers; ++l)
         chain = chain || d.layers[l].act > PSN_ACT_SOFTPLUS100 || a.save2[l] != nullptr || a.mask[l] != nullptr || a.aux2[l] != nullptr;
     PSN_CHECK_ARG(d.n_out <= 32 || (chain && hid == 8), "mlp_infer: 33..64 outputs are built for the 256-wide chain engine only (n_out=%d)", d.n_out);
     for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) {
-        a.save_bits[l] = (save_bits_ptrs != nullptr && l < (d.n_out > 0 ? d.n_layers - 1 : d.n_layers)) ? save_bits_ptrs[l] : nullptr;
+        a.save_bits[l] = (o.save_bits_ptrs != nullptr && l < n_hidden) ? o.save_bits_ptrs[l] : nullptr;
         PSN_CHECK_ARG(a.save_bits[l] == nullptr || (!chain && a.save[l] != nullptr && (((uintptr_t)a.save_bits[l]) & 7) == 0),
                       "mlp_infer: sign-bit words (layer %d) go with an activation dump of a plain forward launch", l);
     }
-    PSN_CHECK_ARG(live_count == nullptr || (!chain && d.n_out >= 1 && live_period >= 64 && live_period % 64 == 0 && save_row0 >= 0 &&
-                                            save_row0 % live_period == 0 && save_row0 <= n_rows),
+    PSN_CHECK_ARG(o.live_count == nullptr || (!chain && d.n_out >= 1 && o.live_period >= 64 && o.live_period % 64 == 0 && o.save_row0 >= 0 &&
+                                              o.save_row0 % o.live_period == 0 && o.save_row0 <= o.n_rows),
                   "mlp_infer_padded: needs the lean variant, outputs, a period that is a multiple of 64 and save_row0 a multiple of the period (period=%lld save_row0=%lld)",
-                  (long long)live_period, (long long)save_row0);
-    a.live_count = live_count; a.live_period = live_period > 0 ? live_period : 1;
-    {
-        static const int tb = [] { const char* e = getenv("PSN_TB_LDS"); return (e != nullptr && e[0] == '0') ? 0 : 1; }();
-        a.tb_lds = tb;
-        // point-major block order (InferArgs.pm_period): pair row sets row = group * P + point of the lean engine (A/B: PSN_POINT_MAJOR=0)
-        const int pm = g_point_major.load(std::memory_order_relaxed);
-        const bool pair = !chain && a_div == 1 && (tab_b != nullptr || init_b != nullptr) && b_div == a_mod && b_div >= rows_per_block &&
-                          b_mod >= 2 && b_mod < (1 << 20) && n_rows == b_div * b_mod && blocks + 8 < (1ll << 31);
-        if (pm && pair && (live_count == nullptr || (live_period == b_div && (n_rows - save_row0) % live_period == 0))) {
-            a.pm_period = b_div;
-            a.pm_groups = (int)b_mod;
-            blocks = live_count != nullptr ? blocks + 7 : (blocks + 7) / 8 * 8;  // (an eighth of the order per XCD: the grid is rounded up)
-        }
+                  (long long)o.live_period, (long long)o.save_row0);
+    a.live_count = o.live_count; a.live_period = o.live_period > 0 ? o.live_period : 1;
+    static const int tb = [] { const char* e = getenv("PSN_TB_LDS"); return (e != nullptr && e[0] == '0') ? 0 : 1; }();
+    a.tb_lds = tb;
+    // point-major block order (InferArgs.pm_period): pair row sets row = group * P + point of the lean engine (A/B: PSN_POINT_MAJOR=0)
+    const bool pair = !chain && o.a_div == 1 && (o.tab_b != nullptr || o.init_b != nullptr) && o.b_div == o.a_mod && o.b_div >= rows_per_block &&
+                      o.b_mod >= 2 && o.b_mod < (1 << 20) && o.n_rows == o.b_div * o.b_mod && blocks + 8 < (1ll << 31);
+    if (g_point_major.load(std::memory_order_relaxed) && pair &&
+        (o.live_count == nullptr || (o.live_period == o.b_div && (o.n_rows - o.save_row0) % o.live_period == 0))) {
+        a.pm_period = o.b_div;
+        a.pm_groups = (int)o.b_mod;
+        blocks = o.live_count != nullptr ? blocks + 7 : (blocks + 7) / 8 * 8;  // (an eighth of the order per XCD: the grid is rounded up)
     }
-    const size_t lds_bytes = (2 * kStageFloats + PSN_MLP_MAX_LAYERS * 256) * sizeof(float);
-    const dim3 grid((unsigned)blocks), block(kWaves * 64);
-    hipStream_t st = (hipStream_t)stream;
     bool trim = false;
     for (int l = 0; l < d.n_layers; ++l) trim = trim || (d.layers[l].n_kt_act > 0 && d.layers[l].n_kt_act < hid);
     PSN_CHECK_ARG(!trim || hid == 8, "mlp_infer: n_kt_act = n_mt - 1 is built for the 256-wide networks only");
@@ -1471,116 +1528,66 @@ static int mlp_infer_impl(const PsnMlpDesc* desc, const float* packed_w, const f
     const bool x3 = d.w_format == PSN_W_BF16X2;
     PSN_CHECK_ARG(d.w_format == PSN_W_F32 || x3, "mlp_infer: unknown weight format %d", d.w_format);
     PSN_CHECK_ARG(!x3 || hid == 8, "mlp_infer: split-bf16 weight stages (PSN_W_BF16X2) are built for the 256-wide networks only");
-    if (x3 && !chain) {
-        if (trim) hipLaunchKernelGGL((mlp_infer_kernel<false, 16, 0, true, false, true>), grid, block, lds_bytes, st, a);
-        else hipLaunchKernelGGL((mlp_infer_kernel<false, 16, 0, false, false, true>), grid, block, lds_bytes, st, a);
-    } else if (x3) {
-        if (from_a) {
-            if (trim) hipLaunchKernelGGL((mlp_infer_kernel<true, 16, 0, true, true, true>), grid, block, lds_bytes, st, a);
-            else hipLaunchKernelGGL((mlp_infer_kernel<true, 16, 0, false, true, true>), grid, block, lds_bytes, st, a);
-        } else {
-            if (trim) hipLaunchKernelGGL((mlp_infer_kernel<true, 16, 0, true, false, true>), grid, block, lds_bytes, st, a);
-            else hipLaunchKernelGGL((mlp_infer_kernel<true, 16, 0, false, false, true>), grid, block, lds_bytes, st, a);
-        }
-    } else if (from_a) {
-        if (trim) hipLaunchKernelGGL((mlp_infer_kernel<true, 16, 0, true, true>), grid, block, lds_bytes, st, a);
-        else hipLaunchKernelGGL((mlp_infer_kernel<true, 16, 0, false, true>), grid, block, lds_bytes, st, a);
-    } else if (trim) {
-        if (chain) hipLaunchKernelGGL((mlp_infer_kernel<true, 16, 0, true>), grid, block, lds_bytes, st, a);
-        else hipLaunchKernelGGL((mlp_infer_kernel<false, 16, 0, true>), grid, block, lds_bytes, st, a);
-    } else if (hid == 8) {
-        if (chain) hipLaunchKernelGGL((mlp_infer_kernel<true, 16>), grid, block, lds_bytes, st, a);
-        else hipLaunchKernelGGL((mlp_infer_kernel<false, 16>), grid, block, lds_bytes, st, a);
-    } else if (hid == 4) {
-        if (chain) hipLaunchKernelGGL((mlp_infer_kernel<true, 8>), grid, block, lds_bytes, st, a);
-        else hipLaunchKernelGGL((mlp_infer_kernel<false, 8>), grid, block, lds_bytes, st, a);
-    } else {
-        if (chain) hipLaunchKernelGGL((mlp_infer_kernel<true, 4>), grid, block, lds_bytes, st, a);
-        else hipLaunchKernelGGL((mlp_infer_kernel<false, 4>), grid, block, lds_bytes, st, a);
-    }
-    PSN_CHECK_LAUNCH("mlp_infer");
+    p = mlp_path(chain, hid * 2, 0, trim, from_a, x3, blocks);
     return PSN_OK;
 }
 
-extern "C" int psn_mlp_infer(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* tab_a,
-                             int64_t a_div, int64_t a_mod, const float* tab_b, int64_t b_div, int64_t b_mod,
-                             const float* init_a, const float* init_b, float* const* save_ptrs, int64_t save_row0,
-                             const float* const* mask_ptrs, const float* const* aux2_ptrs, float* const* save2_ptrs,
-                             const float* act_init, int64_t act_init_rows, const float* rk_coef, const float* rk_basis, int rk_k,
-                             const uint32_t* dump_tiles, int64_t n_rows, float* out, void* stream) {
-    return mlp_infer_impl(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod, init_a, init_b, save_ptrs, save_row0,
-                          mask_ptrs, aux2_ptrs, save2_ptrs, act_init, act_init_rows, rk_coef, rk_basis, rk_k, dump_tiles, n_rows, out,
-                          nullptr, 0, nullptr, stream);
+extern "C" int psn_mlp_launch(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const PsnMlpLaunch* launch,
+                              PsnMlpPath* path, void* stream) {
+    PSN_CHECK_ARG(launch != nullptr, "mlp_infer: null pointer");
+    psn::InferArgs a;
+    PsnMlpPath p;
+    if (path != nullptr) *path = {};
+    int rc = mlp_infer_plan(desc, packed_w, packed_b, *launch, a, p);
+    if (rc != PSN_OK || p.blocks == 0) return rc;
+    rc = launch_infer("mlp_infer", a, p, stream);
+    if (rc == PSN_OK && path != nullptr) *path = t_last_path;
+    return rc;
 }
 
-// psn_mlp_infer, plain forward with activation dumps, that ALSO leaves the sign bits of every dumped activation behind:
-// save_bits_ptrs[l] [n_rows - save_row0, 4] uint64 (or NULL per layer), word (row, g) bit 4 mt + r = (feature 16 mt + 4 g + r of
-// the row's dumped activation > 0).  A ReLU-backward chain (PSN_ACT_RELU_BITS, the words passed as that layer's aux1) then reads
-// 32 bytes per row and layer instead of the activation row; live_count / live_period as for psn_mlp_infer_padded (NULL, 0: none).
-extern "C" int psn_mlp_infer_bits(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* tab_a,
-                                  int64_t a_div, int64_t a_mod, const float* tab_b, int64_t b_div, int64_t b_mod,
-                                  const float* init_a, const float* init_b, float* const* save_ptrs,
-                                  unsigned long long* const* save_bits_ptrs, int64_t save_row0, int64_t n_rows, float* out,
-                                  const float* live_count, int64_t live_period, void* stream) {
-    PSN_CHECK_ARG(save_ptrs != nullptr && save_bits_ptrs != nullptr, "mlp_infer_bits: dump and sign-bit pointer arrays are required");
-    return mlp_infer_impl(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod, init_a, init_b, save_ptrs, save_row0,
-                          nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, n_rows, out, live_count, live_period,
-                          save_bits_ptrs, stream);
-}
-
-// psn_mlp_infer (lean variant: no chain operands) over a PADDED row set: the rows [0, save_row0) come in groups of
-// live_period rows (stage 2: one group per shading light over a surface-pixel list padded to a fixed capacity, so that one
-// captured HIP graph serves batches with different surface counts), of which the first live_count[0] -- a float on the
-// device, psn_surface_index's count -- are real.  Workgroups all of whose 64 rows are padding write zeros and leave; every
-// other row is evaluated as by psn_mlp_infer (bit-identical), the rows from save_row0 on all of them.
-extern "C" int psn_mlp_infer_padded(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* tab_a,
-                                    int64_t a_div, int64_t a_mod, const float* tab_b, int64_t b_div, int64_t b_mod,
-                                    const float* init_a, const float* init_b, float* const* save_ptrs, int64_t save_row0,
-                                    int64_t n_rows, float* out, const float* live_count, int64_t live_period, void* stream) {
-    PSN_CHECK_ARG(live_count != nullptr, "mlp_infer_padded: live_count is null");
-    return mlp_infer_impl(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod, init_a, init_b, save_ptrs, save_row0,
-                          nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, n_rows, out, live_count, live_period, nullptr, stream);
+// The network shape that the in-kernel encoding is written for (SRC = 1, 2, 3): 256-wide hidden layers without init tables behind
+// one 64-column positional encoding.  any_head: 1..32 outputs with any output activation (psn_mlp_infer_pe*) instead of the one
+// occupancy output; fp32_only and strict_act (the final layer is no softplus) are the root finder's.
+static int check_pe_net(const PsnMlpDesc& d, const char* what, int pe_octaves, bool any_head, bool fp32_only, bool strict_act) {
+    const bool depth = d.n_layers >= 2 && d.n_layers <= PSN_MLP_MAX_LAYERS;
+    if (any_head) {
+        PSN_CHECK_ARG(depth && d.n_out >= 1 && d.n_out <= 32, "%s: n_layers=%d n_out=%d", what, d.n_layers, d.n_out);
+    } else {
+        PSN_CHECK_ARG(depth && d.n_out == 1 && d.out_act == PSN_OUT_OCC, "%s: expects an occupancy network (one output, PSN_OUT_OCC)", what);
+    }
+    PSN_CHECK_ARG(!fp32_only || d.w_format == PSN_W_F32, "%s: fp32 weight stages only", what);
+    PSN_CHECK_ARG(d.w_format == PSN_W_F32 || d.w_format == PSN_W_BF16X2, "%s: unknown weight format %d", what, d.w_format);
+    PSN_CHECK_ARG(d.out_act >= PSN_OUT_NONE && d.out_act <= PSN_OUT_OCC, "%s: out_act=%d", what, d.out_act);
+    PSN_CHECK_ARG(d.in_kt_a == 2 && d.in_kt_b == 0 && 3 + 6 * pe_octaves <= 64 && pe_octaves >= 0,
+                  "%s: the input block is one 64-column positional encoding (in_kt_a = 2), got in_kt_a=%d octaves=%d", what, d.in_kt_a, pe_octaves);
+    PSN_CHECK_ARG(d.layers[0].n_kt_in == 2 && d.layers[0].n_kt_act == 0, "%s: layer 0 reads the encoding as k-tiles", what);
+    for (int l = 0; l < d.n_layers; ++l) {
+        const PsnMlpLayer& L = d.layers[l];
+        const bool last = l == d.n_layers - 1;
+        PSN_CHECK_ARG(L.n_mt == (last ? 1 : 8) && L.init_off < 0, "%s: layer %d: 256-wide hidden layers without init tables only", what, l);
+        PSN_CHECK_ARG((L.act == PSN_ACT_SOFTPLUS100 && !(strict_act && last)) || L.act == PSN_ACT_RELU || L.act == PSN_ACT_NONE, "%s: layer %d activation", what, l);
+        PSN_CHECK_ARG(L.b_off == (int64_t)l * 256, "%s: biases must be packed back to back", what);
+        PSN_CHECK_ARG(L.n_kt_in == 0 || L.n_kt_in == 2, "%s: layer %d n_kt_in=%d", what, l, L.n_kt_in);
+        PSN_CHECK_ARG(last ? (L.n_kt_act == 8 && L.n_kt_in == 0) : (L.n_kt_act == 0 || L.n_kt_act == 7 || L.n_kt_act == 8), "%s: layer %d n_kt_act=%d", what, l, L.n_kt_act);
+        PSN_CHECK_ARG(L.n_kt_in + L.n_kt_act >= 1, "%s: layer %d has no input", what, l);
+    }
+    return PSN_OK;
 }
 
 // Lean evaluation of a 256-wide network whose input block is the positional encoding of a 3-vector (the stage-1 occupancy
 // queries, stage1/model/network.py:141-150 + 85-101): `points` [n_rows, 3] in, the encoding gamma(scale * p) is formed
 // in the kernel prologue in the B-operand registers -- the same expressions as pe_encode_kernel, so the result equals
-// psn_pe_encode + psn_mlp_infer bit for bit without the [n_rows, 64] table ever existing in HBM.
+// psn_pe_encode + psn_mlp_launch bit for bit without the [n_rows, 64] table ever existing in HBM.
 static int mlp_infer_pe_impl(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* points,
                              int64_t n_rows, const long long* n_rows_dev, const int64_t* out_rows, int pe_octaves, float pe_scale,
                              float* out, void* stream) {
     using namespace psn;
     PSN_CHECK_ARG(desc && packed_w && packed_b && points && out, "mlp_infer_pe: null pointer");
-    const PsnMlpDesc& d = *desc;
-    PSN_CHECK_ARG(d.n_layers >= 2 && d.n_layers <= PSN_MLP_MAX_LAYERS && d.n_out >= 1 && d.n_out <= 32, "mlp_infer_pe: n_layers=%d n_out=%d", d.n_layers, d.n_out);
-    PSN_CHECK_ARG(d.w_format == PSN_W_F32 || d.w_format == PSN_W_BF16X2, "mlp_infer_pe: unknown weight format %d", d.w_format);
-    PSN_CHECK_ARG(d.out_act >= PSN_OUT_NONE && d.out_act <= PSN_OUT_OCC, "mlp_infer_pe: out_act=%d", d.out_act);
-    PSN_CHECK_ARG(d.in_kt_a == 2 && d.in_kt_b == 0 && 3 + 6 * pe_octaves <= 64 && pe_octaves >= 0,
-                  "mlp_infer_pe: the input block is one 64-column positional encoding (in_kt_a = 2), got in_kt_a=%d octaves=%d", d.in_kt_a, pe_octaves);
-    PSN_CHECK_ARG(d.layers[0].n_kt_in == 2 && d.layers[0].n_kt_act == 0, "mlp_infer_pe: layer 0 reads the encoding as k-tiles");
-    for (int l = 0; l < d.n_layers; ++l) {
-        const PsnMlpLayer& L = d.layers[l];
-        const bool last = l == d.n_layers - 1;
-        PSN_CHECK_ARG(L.n_mt == (last ? 1 : 8) && L.init_off < 0, "mlp_infer_pe: layer %d: 256-wide hidden layers without init tables only", l);
-        PSN_CHECK_ARG(L.act == PSN_ACT_SOFTPLUS100 || L.act == PSN_ACT_RELU || L.act == PSN_ACT_NONE, "mlp_infer_pe: layer %d activation", l);
-        PSN_CHECK_ARG(L.b_off == (int64_t)l * 256, "mlp_infer_pe: biases must be packed back to back");
-        PSN_CHECK_ARG(L.n_kt_in == 0 || L.n_kt_in == 2, "mlp_infer_pe: layer %d n_kt_in=%d", l, L.n_kt_in);
-        PSN_CHECK_ARG(last ? (L.n_kt_act == 8 && L.n_kt_in == 0) : (L.n_kt_act == 0 || L.n_kt_act == 7 || L.n_kt_act == 8), "mlp_infer_pe: layer %d n_kt_act=%d", l, L.n_kt_act);
-        PSN_CHECK_ARG(L.n_kt_in + L.n_kt_act >= 1, "mlp_infer_pe: layer %d has no input", l);
-    }
+    if (const int rc = check_pe_net(*desc, "mlp_infer_pe", pe_octaves, true, false, false)) return rc;
     if (n_rows <= 0) return PSN_OK;
-    InferArgs a = {};
-    a.d = d; a.w = packed_w; a.b = packed_b; a.a_div = 1; a.a_mod = 1; a.b_div = 1; a.b_mod = 1; a.n_rows = n_rows; a.out = out;
-    a.n_bias = (d.n_layers - 1) * 256 + 32;
+    InferArgs a = base_args(*desc, packed_w, packed_b, n_rows, out);
     a.ray_o = points; a.pe_scale = pe_scale; a.pe_octaves = pe_octaves; a.n_rows_dev = n_rows_dev; a.out_rows = out_rows;
-    for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) { a.save_tiles[l] = 0xFFFFFFFFu; a.save2_tiles[l] = 0xFFFFFFFFu; }
-    const int64_t blocks = (n_rows + kWaves * 16 - 1) / (kWaves * 16);
-    PSN_CHECK_ARG(blocks < (1ll << 31), "mlp_infer_pe: too many rows");
-    const size_t lds_bytes = (2 * kStageFloats + PSN_MLP_MAX_LAYERS * 256) * sizeof(float);
-    if (d.w_format == PSN_W_BF16X2) hipLaunchKernelGGL((mlp_infer_kernel<false, 16, 2, true, false, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((mlp_infer_kernel<false, 16, 2, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds_bytes, (hipStream_t)stream, a);
-    PSN_CHECK_LAUNCH("mlp_infer_pe");
-    return PSN_OK;
+    return launch_infer("mlp_infer_pe", a, mlp_path(0, 16, 2, 1, 0, desc->w_format == PSN_W_BF16X2, (n_rows + kWaves * 16 - 1) / (kWaves * 16)), stream);
 }
 
 extern "C" int psn_mlp_infer_pe(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* points,
@@ -1595,7 +1602,6 @@ extern "C" int psn_mlp_infer_pe(const PsnMlpDesc* desc, const float* packed_w, c
 extern "C" int psn_mlp_infer_pe_indirect(const PsnMlpDesc* desc, const float* packed_w, const float* packed_b, const float* points,
                                          int64_t capacity, const long long* n_rows_dev, const int64_t* out_rows, int pe_octaves,
                                          float pe_scale, float* out, void* stream) {
-    using namespace psn;
     PSN_CHECK_ARG(n_rows_dev != nullptr, "mlp_infer_pe_indirect: n_rows_dev is required");
     return mlp_infer_pe_impl(desc, packed_w, packed_b, points, capacity, n_rows_dev, out_rows, pe_octaves, pe_scale, out, stream);
 }
@@ -1609,38 +1615,13 @@ extern "C" int psn_march_sweep(const PsnMlpDesc* desc, const float* packed_w, co
                                int n_steps, float tau, int pe_octaves, float pe_scale, int* skip, unsigned long long* n_blocks, float* occ, void* stream) {
     using namespace psn;
     PSN_CHECK_ARG(desc && packed_w && packed_b && origin && dir && far && u && omu && occ, "march_sweep: null pointer");
-    const PsnMlpDesc& d = *desc;
-    PSN_CHECK_ARG(d.n_layers >= 2 && d.n_layers <= PSN_MLP_MAX_LAYERS && d.n_out == 1 && d.out_act == PSN_OUT_OCC,
-                  "march_sweep: expects an occupancy network (one output, PSN_OUT_OCC)");
-    PSN_CHECK_ARG(d.w_format == PSN_W_F32 || d.w_format == PSN_W_BF16X2, "march_sweep: unknown weight format %d", d.w_format);
-    PSN_CHECK_ARG(d.in_kt_a == 2 && d.in_kt_b == 0 && 3 + 6 * pe_octaves <= 64 && pe_octaves >= 0,
-                  "march_sweep: the input block is one 64-column positional encoding (in_kt_a = 2), got in_kt_a=%d octaves=%d", d.in_kt_a, pe_octaves);
-    PSN_CHECK_ARG(d.layers[0].n_kt_in == 2 && d.layers[0].n_kt_act == 0, "march_sweep: layer 0 reads the encoding as k-tiles");
-    for (int l = 0; l < d.n_layers; ++l) {
-        const PsnMlpLayer& L = d.layers[l];
-        const bool last = l == d.n_layers - 1;
-        PSN_CHECK_ARG(L.n_mt == (last ? 1 : 8) && L.init_off < 0, "march_sweep: layer %d: 256-wide hidden layers without init tables only", l);
-        PSN_CHECK_ARG(L.act == PSN_ACT_SOFTPLUS100 || L.act == PSN_ACT_RELU || L.act == PSN_ACT_NONE, "march_sweep: layer %d activation", l);
-        PSN_CHECK_ARG(L.b_off == (int64_t)l * 256, "march_sweep: biases must be packed back to back");
-        PSN_CHECK_ARG(L.n_kt_in == 0 || L.n_kt_in == 2, "march_sweep: layer %d n_kt_in=%d", l, L.n_kt_in);
-        PSN_CHECK_ARG(last ? (L.n_kt_act == 8 && L.n_kt_in == 0) : (L.n_kt_act == 0 || L.n_kt_act == 7 || L.n_kt_act == 8), "march_sweep: layer %d n_kt_act=%d", l, L.n_kt_act);
-        PSN_CHECK_ARG(L.n_kt_in + L.n_kt_act >= 1, "march_sweep: layer %d has no input", l);
-    }
+    if (const int rc = check_pe_net(*desc, "march_sweep", pe_octaves, false, false, false)) return rc;
     PSN_CHECK_ARG(n_steps >= 64 && n_steps % (kWaves * 16) == 0, "march_sweep: n_steps=%d must be a multiple of 64 (one workgroup = 64 steps of one ray)", n_steps);
     if (n_rays <= 0) return PSN_OK;
-    InferArgs a = {};
-    a.d = d; a.w = packed_w; a.b = packed_b; a.a_div = 1; a.a_mod = 1; a.b_div = 1; a.b_mod = 1; a.n_rows = n_rays * n_steps; a.out = occ;
-    a.n_bias = (d.n_layers - 1) * 256 + 32;
+    InferArgs a = base_args(*desc, packed_w, packed_b, n_rays * n_steps, occ);
     a.ray_o = origin; a.ray_d = dir; a.far = far; a.u = u; a.omu = omu; a.near = near; a.n_steps = n_steps; a.skip = skip; a.n_blocks = n_blocks; a.tau = tau;
     a.pe_scale = pe_scale; a.pe_octaves = pe_octaves;
-    for (int l = 0; l < PSN_MLP_MAX_LAYERS; ++l) { a.save_tiles[l] = 0xFFFFFFFFu; a.save2_tiles[l] = 0xFFFFFFFFu; }
-    const int64_t blocks = n_rays * (n_steps / (kWaves * 16));
-    PSN_CHECK_ARG(blocks < (1ll << 31), "march_sweep: too many rows");
-    const size_t lds_bytes = (2 * kStageFloats + PSN_MLP_MAX_LAYERS * 256 + kWaves * 16) * sizeof(float);
-    if (d.w_format == PSN_W_BF16X2) hipLaunchKernelGGL((mlp_infer_kernel<false, 16, 3, true, false, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((mlp_infer_kernel<false, 16, 3, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds_bytes, (hipStream_t)stream, a);
-    PSN_CHECK_LAUNCH("march_sweep");
-    return PSN_OK;
+    return launch_infer("march_sweep", a, mlp_path(0, 16, 3, 1, 0, desc->w_format == PSN_W_BF16X2, n_rays * (n_steps / (kWaves * 16))), stream);
 }
 
 // Fused secant refinement of the ray march (stage1/model/rendering.py:525-555) on the occupancy network packed by
@@ -1650,42 +1631,15 @@ extern "C" int psn_root_find(const PsnMlpDesc* desc, const float* packed_w, cons
                              float pe_scale, float* d_out, void* stream) {
     using namespace psn;
     PSN_CHECK_ARG(desc && packed_w && packed_b && origin && dir && bracket && d_out, "root_find: null pointer");
-    const PsnMlpDesc& d = *desc;
-    PSN_CHECK_ARG(d.n_layers >= 2 && d.n_layers <= PSN_MLP_MAX_LAYERS && d.n_out == 1 && d.out_act == PSN_OUT_OCC,
-                  "root_find: expects an occupancy network (one output, PSN_OUT_OCC)");
-    PSN_CHECK_ARG(d.w_format == PSN_W_F32, "root_find: fp32 weight stages only");
-    PSN_CHECK_ARG(d.in_kt_a == 2 && d.in_kt_b == 0 && 3 + 6 * pe_octaves <= 64 && pe_octaves >= 0,
-                  "root_find: the input block is one 64-column positional encoding (in_kt_a = 2), got in_kt_a=%d octaves=%d", d.in_kt_a, pe_octaves);
-    PSN_CHECK_ARG(d.layers[0].n_kt_in == 2 && d.layers[0].n_kt_act == 0 && d.layers[0].init_off < 0, "root_find: layer 0 reads the encoding as k-tiles");
-    for (int l = 0; l < d.n_layers; ++l) {
-        const PsnMlpLayer& L = d.layers[l];
-        const bool last = l == d.n_layers - 1;
-        PSN_CHECK_ARG(L.n_mt == (last ? 1 : 8) && L.init_off < 0, "root_find: layer %d: 256-wide hidden layers without init tables only", l);
-        PSN_CHECK_ARG(L.act == (last ? PSN_ACT_NONE : PSN_ACT_SOFTPLUS100) || L.act == PSN_ACT_RELU || L.act == PSN_ACT_NONE, "root_find: layer %d activation", l);
-        PSN_CHECK_ARG(L.b_off == (int64_t)l * 256, "root_find: biases must be packed back to back");
-    }
+    if (const int rc = check_pe_net(*desc, "root_find", pe_octaves, false, true, true)) return rc;
     PSN_CHECK_ARG(n_iter >= 0 && n_iter <= 64, "root_find: n_iter=%d", n_iter);
     if (n_rays <= 0) return PSN_OK;
-    InferArgs a = {};
-    a.d = d; a.w = packed_w; a.b = packed_b; a.a_div = 1; a.a_mod = 1; a.b_div = 1; a.b_mod = 1; a.n_rows = n_rays; a.out = d_out;
-    a.n_bias = (d.n_layers - 1) * 256 + 32;
+    InferArgs a = base_args(*desc, packed_w, packed_b, n_rays, d_out);
     a.ray_o = origin; a.ray_d = dir; a.bracket = bracket; a.tau = tau; a.pe_scale = pe_scale; a.n_iter = n_iter; a.pe_octaves = pe_octaves;
-    const int64_t blocks = (n_rays + kWaves * 16 - 1) / (kWaves * 16);
-    PSN_CHECK_ARG(blocks < (1ll << 31), "root_find: too many rays");
-    const size_t lds_bytes = (2 * kStageFloats + PSN_MLP_MAX_LAYERS * 256) * sizeof(float);
-    // feature-parallel form whenever the network has the shape it is written for (even stage counts per layer: the
-    // 64-column encoding = 2 input k-tiles, 8 activation k-tiles); the row-parallel engine otherwise
-    bool fp = d.n_layers >= 2;
-    for (int l = 0; l < d.n_layers - 1; ++l) fp = fp && (d.layers[l].n_kt_in == 0 || d.layers[l].n_kt_in == 2) && (d.layers[l].n_kt_act == 0 || d.layers[l].n_kt_act >= 7) && d.layers[l].n_kt_act <= 8;
-    fp = fp && d.layers[d.n_layers - 1].n_kt_act == 8 && d.layers[d.n_layers - 1].n_kt_in == 0;
-    if (const char* ev = getenv("PSN_ROOT_FIND_ROW_PARALLEL")) fp = fp && ev[0] != '1';  // test hook: both forms must agree bit for bit
-    if (fp) {
-        const int64_t blocks16 = (n_rays + 15) / 16;
-        PSN_CHECK_ARG(blocks16 < (1ll << 31), "root_find: too many rays");
-        hipLaunchKernelGGL(root_find_fp_kernel, dim3((unsigned)blocks16), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        hipLaunchKernelGGL((mlp_infer_kernel<false, 16, 1, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds_bytes, (hipStream_t)stream, a);
-    }
-    PSN_CHECK_LAUNCH("root_find");
-    return PSN_OK;
+    // the feature-parallel form (16 rays per workgroup) is written for exactly the shape check_pe_net admits (even stage counts per
+    // layer: the 64-column encoding = 2 input k-tiles, 7 or 8 activation k-tiles); the row-parallel engine is its cross-check
+    const char* ev = getenv("PSN_ROOT_FIND_ROW_PARALLEL");  // test hook: both forms must agree bit for bit
+    const bool row_parallel = ev != nullptr && ev[0] == '1';
+    return launch_infer("root_find", a, mlp_path(0, 16, row_parallel ? 1 : kSrcRootFp, 1, 0, 0, (n_rays + (row_parallel ? 63 : 15)) / (row_parallel ? 64 : 16)), stream);
 }
+

@@ -88,16 +88,15 @@ class PackedMLP(object):
         self.init_wa, self.init_wb, self.init_bias = init_wa, init_wb, init_bias
         self.macs_per_row = None  # algorithmic MACs per row inside the kernel (true, unpadded block shapes)
 
-    def on_points(self, points, pe_octaves, pe_scale, out=None, n_rows_dev=None, out_rows=None):
+    def on_points(self, points, pe_octaves, pe_scale, out=None, n_rows_dev=None, out_rows=None, path=None):
         """The network on gamma(pe_scale * points), [Q, 3] -> [Q, n_out], the encoding formed in the kernel prologue
         (hip.mlp_infer_pe): for packs whose input block is one positional encoding and that use no init tables.
-        n_rows_dev / out_rows: a compacted list with a device-resident length, outputs scattered (see hip.mlp_infer_pe)."""
+        n_rows_dev / out_rows: a compacted list with a device-resident length, outputs scattered; path (see hip.mlp_infer_pe)."""
         return hip.mlp_infer_pe(self.desc, self.w, self.b, points, pe_octaves, pe_scale, out=out, macs_per_row=self.macs_per_row,
-                                n_rows_dev=n_rows_dev, out_rows=out_rows)
+                                n_rows_dev=n_rows_dev, out_rows=out_rows, path=path)
 
-    def __call__(self, tab_a, n_rows, a_div=1, a_mod=None, tab_b=None, b_div=1, b_mod=1, out=None, save=None,
-                 save_row0=0, mask=None, init_a_direct=None, aux2=None, save2=None, act_init=None, rank_init=None,
-                 save_tiles=None, save2_tiles=None, act_init_rows=None, live=None, save_bits=None):
+    def __call__(self, tab_a, n_rows, a_div=1, a_mod=None, tab_b=None, b_div=1, b_mod=1, *, init_a_direct=None, rank_init=None, **operands):
+        """The network on the rows of the index maps; ``operands``: every other keyword of hip.mlp_infer (out, save, mask, live, ...)."""
         if a_mod is None:
             a_mod = tab_a.shape[0] if tab_a is not None else n_rows
         init_a = init_b = None
@@ -114,10 +113,8 @@ class PackedMLP(object):
                 init_b = hip.gemm(tab_b, self.init_wb, trans_b=True, bias=self.init_bias, epi=hip.EPI_BIAS)
         uses_in = any(self.desc.layers[i].n_kt_in > 0 for i in range(self.desc.n_layers))
         return hip.mlp_infer(self.desc, self.w, self.b, tab_a if uses_in else None, a_div, a_mod,
-                             tab_b if uses_in else None, b_div, b_mod, n_rows, out=out, init_a=init_a, init_b=init_b,
-                             save=save, save_row0=save_row0, mask=mask, aux2=aux2, save2=save2, act_init=act_init,
-                             macs_per_row=self.macs_per_row, rank_init=rank_init, save_tiles=save_tiles, save2_tiles=save2_tiles,
-                             act_init_rows=act_init_rows, live=live, save_bits=save_bits)
+                             tab_b if uses_in else None, b_div, b_mod, n_rows, init_a=init_a, init_b=init_b,
+                             macs_per_row=self.macs_per_row, rank_init=rank_init, **operands)
 
 
 def _pad_cols(w, n):

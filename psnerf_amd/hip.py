@@ -749,10 +749,17 @@ def shadow_points(surf, ldir, n_steps, lnear, lfar, u, omu, box):
     return pts, rows, counter
 
 
-def mlp_infer_pe(desc, packed_w, packed_b, points, pe_octaves, pe_scale, out=None, macs_per_row=None, n_rows_dev=None, out_rows=None):
+def _last_path(path):
+    """Fill ``path`` (a PsnMlpPath, or None) with what this thread's last launch of the fused MLP engine ran (psn_mlp_last_path)."""
+    if path is not None:
+        _check(_lib.psn_mlp_last_path(ctypes.byref(path)), 'mlp_last_path')
+
+
+def mlp_infer_pe(desc, packed_w, packed_b, points, pe_octaves, pe_scale, out=None, macs_per_row=None, n_rows_dev=None, out_rows=None, path=None):
     """Network on gamma(pe_scale * points) with the encoding formed inside the kernel (psn_mlp_infer_pe) -> [Q, n_out].
     ``n_rows_dev`` (int64 [1] on the device): only the first n_rows_dev[0] points are valid (psn_mlp_infer_pe_indirect; the
-    grid covers all Q); ``out_rows`` (int64 [Q]): row r is written to out[out_rows[r]] -- ``out`` is then required."""
+    grid covers all Q); ``out_rows`` (int64 [Q]): row r is written to out[out_rows[r]] -- ``out`` is then required.
+    ``path``: a PsnMlpPath that receives what the library launched."""
     Q = points.shape[0]
     assert points.shape == (Q, 3) and points.is_contiguous()
     indirect = n_rows_dev is not None
@@ -771,18 +778,21 @@ def mlp_infer_pe(desc, packed_w, packed_b, points, pe_octaves, pe_scale, out=Non
                                                   _tptr(points, 'points'), Q, n_rows_dev.data_ptr(),
                                                   None if out_rows is None else out_rows.data_ptr(), int(pe_octaves), float(pe_scale),
                                                   out.data_ptr(), _stream()), 'mlp_infer_pe_indirect')
+        _last_path(path)
         return out
     assert out_rows is None
     with _Prof('mlp_infer', Q, None if macs_per_row is None else 2.0 * macs_per_row * Q):
         _check(_lib.psn_mlp_infer_pe(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'), _tptr(points, 'points'),
                                      Q, int(pe_octaves), float(pe_scale), out.data_ptr(), _stream()), 'mlp_infer_pe')
+    _last_path(path)
     return out
 
 
 def march_sweep(desc, packed_w, packed_b, origin, direction, far, u, omu, near, n_steps, tau, pe_octaves, pe_scale,
-                early_exit=True, macs_per_row=None):
+                early_exit=True, macs_per_row=None, path=None):
     """Occupancy of the n_steps sweep points of every ray (psn_march_sweep) -> (occ [N, n_steps], skip flags [N] int32 or None).
-    early_exit: blocks of 64 steps behind a ray's first sign change are not evaluated (their occ entries are uninitialised)."""
+    early_exit: blocks of 64 steps behind a ray's first sign change are not evaluated (their occ entries are uninitialised).
+    path: a PsnMlpPath that receives what the library launched."""
     N = origin.shape[0]
     assert origin.shape == (N, 3) and direction.shape == (N, 3) and far.shape == (N,) and u.numel() == n_steps == omu.numel()
     occ = torch.empty(N, n_steps, device=origin.device, dtype=torch.float32)
@@ -799,6 +809,7 @@ def march_sweep(desc, packed_w, packed_b, origin, direction, far, u, omu, near, 
                                     int(n_steps), float(tau), int(pe_octaves), float(pe_scale),
                                     None if skip is None else skip.data_ptr(), None if count is None else count.data_ptr(),
                                     occ.data_ptr(), _stream()), 'march_sweep')
+    _last_path(path)
     return occ, skip
 
 
@@ -1141,84 +1152,66 @@ class block_order(object):
 
 def mlp_infer(desc, packed_w, packed_b, tab_a, a_div, a_mod, tab_b, b_div, b_mod, n_rows, out=None, init_a=None,
               init_b=None, save=None, save_row0=0, mask=None, aux2=None, save2=None, act_init=None, macs_per_row=None,
-              rank_init=None, save_tiles=None, save2_tiles=None, act_init_rows=None, live=None, save_bits=None):
-    """save: list (one entry per hidden layer, None allowed) of [n_rows - save_row0, 256] tensors that receive the
+              rank_init=None, save_tiles=None, save2_tiles=None, act_init_rows=None, live=None, save_bits=None, path=None):
+    """One launch of the fused engine (psn_mlp_launch; the library decides between the lean and the chain engine).
+    save: list (one entry per hidden layer, None allowed) of [n_rows - save_row0, 256] tensors that receive the
     post-activation outputs of the rows >= save_row0.
     rank_init = (coef [n_rows, k], basis [k, init_stride]), k <= 4: rank-k init of the layers with init_off >= 0.
     act_init [act_init_rows (default n_rows), width]: initial activations; the rows behind them start from zeros.
     live = (count float32 [1] on the device, period): the rows [0, save_row0) are groups of `period` rows of which the first
-    count[0] are real (psn_mlp_infer_padded; plain forward launches only): all-padding workgroups write zeros and leave.
+    count[0] are real (PsnMlpLaunch.live_count; plain forward launches only): all-padding workgroups write zeros and leave.
     save_bits: list like ``save`` of int64 [n_rows - save_row0, 4] tensors (or None) that receive the sign bits of the dumped
-    activations (psn_mlp_infer_bits); a chain layer with ACT_RELU_BITS takes such a tensor as its ``mask`` entry."""
-    tiles_arr = None
+    activations (PsnMlpLaunch.save_bits_ptrs); a chain layer with ACT_RELU_BITS takes such a tensor as its ``mask`` entry.
+    path: a PsnMlpPath that receives what the library launched."""
+    o, keep = PsnMlpLaunch(), []     # (keep: the host arrays of the launch, alive until it returns)
     if save_tiles is not None or save2_tiles is not None:  # per layer: bit mt = the 16-column tile mt of the dump is written
         tiles_arr = (ctypes.c_uint32 * (2 * MAX_LAYERS))(*([0xFFFFFFFF] * (2 * MAX_LAYERS)))
         for base, lst in ((0, save_tiles), (MAX_LAYERS, save2_tiles)):
             for l, m in enumerate(lst or []):
                 if m is not None:
                     tiles_arr[base + l] = int(m)
-    rk_coef = rk_basis = None
-    rk_k = 0
+        keep.append(tiles_arr)
+        o.dump_tiles = ctypes.addressof(tiles_arr)
     if rank_init is not None:
         rk_coef, rk_basis = rank_init
-        rk_k = rk_basis.shape[0]
+        o.rk_k = rk_k = rk_basis.shape[0]
         assert rk_coef.shape == (n_rows, rk_k) and rk_coef.is_contiguous() and rk_basis.is_contiguous() and 1 <= rk_k <= 4
         assert rk_basis.shape[1] == desc.init_stride, 'rank_init: the basis rows are init_stride floats'
-
-    ai_rows = 0
+        o.rk_coef, o.rk_basis = _tptr(rk_coef, 'rk_coef'), _tptr(rk_basis, 'rk_basis')
     if act_init is not None:
-        ai_rows = n_rows if act_init_rows is None else act_init_rows
-        assert act_init.is_contiguous() and act_init.shape[0] >= ai_rows, 'act_init: fewer rows than act_init_rows'
+        o.act_init_rows = n_rows if act_init_rows is None else act_init_rows
+        assert act_init.is_contiguous() and act_init.shape[0] >= o.act_init_rows, 'act_init: fewer rows than act_init_rows'
+        o.act_init = _tptr(act_init, 'act_init')
     if out is None and desc.n_out > 0:
         out = torch.empty(n_rows, desc.n_out, device=packed_w.device, dtype=torch.float32)
     n_hidden = desc.n_layers - 1 if desc.n_out > 0 else desc.n_layers
-    def ptr_array(lst, n, name):
+
+    def ptr_array(lst, n, name, words=None):
+        """HOST array of the device pointers of ``lst``; words: the entries are sign-bit words (None: those that are int64)."""
         if lst is None:
             return None
         assert len(lst) == n, '%s: expected %d entries' % (name, n)
-        return (ctypes.c_void_p * n)(*[None if t is None else (_bits_ptr(t, name) if t.dtype == torch.int64 else _tptr(t, name)) for t in lst])
+        is_words = lambda t: t.dtype == torch.int64 if words is None else words
+        keep.append((ctypes.c_void_p * n)(*[None if t is None else (_bits_ptr(t, name) if is_words(t) else _tptr(t, name)) for t in lst]))
+        return ctypes.addressof(keep[-1])
 
-    mask_arr = ptr_array(mask, desc.n_layers, 'mask')
-    aux2_arr = ptr_array(aux2, desc.n_layers, 'aux2')
-    save2_arr = ptr_array(save2, desc.n_layers, 'save2')
-    save_arr = None
-    if save is not None:
-        assert len(save) == n_hidden
-        save_arr = (ctypes.c_void_p * len(save))(*[None if t is None else _tptr(t, 'save') for t in save])
-    # 'mlp_infer' = the lean engine, 'mlp_chain' = the chain engine (same dispatch rule as psn_mlp_infer)
-    chain = act_init is not None or rank_init is not None or tiles_arr is not None or mask is not None or aux2 is not None or save2 is not None or any(
-        desc.layers[l].act > ACT_SOFTPLUS100 for l in range(desc.n_layers))
-    if save_bits is not None:
-        if chain or save is None:
-            raise RuntimeError('mlp_infer: sign-bit words go with the activation dumps of a plain forward launch')
-        assert len(save_bits) == n_hidden
-        for t, b in zip(save, save_bits):
-            assert b is None or (t is not None and b.shape == (t.shape[0], 4))
-        bits_arr = (ctypes.c_void_p * n_hidden)(*[None if t is None else _bits_ptr(t, 'save_bits') for t in save_bits])
-        cnt, period = live if live is not None else (None, 0)
-        with _Prof('mlp_infer', n_rows, None if macs_per_row is None else 2.0 * macs_per_row * n_rows):
-            _check(_lib.psn_mlp_infer_bits(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'),
-                                           _tptr(tab_a, 'tab_a', allow_none=True), a_div, a_mod, _tptr(tab_b, 'tab_b', allow_none=True), b_div, b_mod,
-                                           _tptr(init_a, 'init_a', allow_none=True), _tptr(init_b, 'init_b', allow_none=True), save_arr, bits_arr, save_row0, n_rows,
-                                           _tptr(out, 'out', allow_none=True), None if cnt is None else cnt.data_ptr(), int(period), _stream()), 'mlp_infer_bits')
-        return out
+    o.mask_ptrs, o.aux2_ptrs, o.save2_ptrs = (ptr_array(lst, desc.n_layers, name) for lst, name in ((mask, 'mask'), (aux2, 'aux2'), (save2, 'save2')))
+    o.save_ptrs, o.save_bits_ptrs = ptr_array(save, n_hidden, 'save', False), ptr_array(save_bits, n_hidden, 'save_bits', True)
+    for t, b in zip(save or [], save_bits or []):
+        assert b is None or (t is not None and b.shape == (t.shape[0], 4))
     if live is not None:
         cnt, period = live
-        if chain:
-            raise RuntimeError('mlp_infer: a device-side live count is for plain forward launches (no chain operands)')
         assert cnt.is_cuda and cnt.dtype == torch.float32 and cnt.numel() == 1 and int(period) >= 1
-        with _Prof('mlp_infer', n_rows, None if macs_per_row is None else 2.0 * macs_per_row * n_rows):
-            _check(_lib.psn_mlp_infer_padded(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'),
-                                             _tptr(tab_a, 'tab_a', allow_none=True), a_div, a_mod, _tptr(tab_b, 'tab_b', allow_none=True), b_div, b_mod,
-                                             _tptr(init_a, 'init_a', allow_none=True), _tptr(init_b, 'init_b', allow_none=True), save_arr, save_row0, n_rows,
-                                             _tptr(out, 'out', allow_none=True), cnt.data_ptr(), int(period), _stream()), 'mlp_infer_padded')
-        return out
-    with _Prof('mlp_chain' if chain else 'mlp_infer', n_rows, None if macs_per_row is None else 2.0 * macs_per_row * n_rows):
-        _check(_lib.psn_mlp_infer(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'),
-                                  _tptr(tab_a, 'tab_a', allow_none=True), a_div, a_mod, _tptr(tab_b, 'tab_b', allow_none=True), b_div, b_mod,
-                                  _tptr(init_a, 'init_a', allow_none=True), _tptr(init_b, 'init_b', allow_none=True), save_arr, save_row0, mask_arr,
-                                  aux2_arr, save2_arr, _tptr(act_init, 'act_init', allow_none=True), int(ai_rows), _tptr(rk_coef, 'rk_coef', allow_none=True),
-                                  _tptr(rk_basis, 'rk_basis', allow_none=True), rk_k, tiles_arr, n_rows, _tptr(out, 'out', allow_none=True), _stream()), 'mlp_infer')
+        o.live_count, o.live_period = cnt.data_ptr(), int(period)
+    o.tab_a, o.a_div, o.a_mod = _tptr(tab_a, 'tab_a', allow_none=True), a_div, a_mod
+    o.tab_b, o.b_div, o.b_mod = _tptr(tab_b, 'tab_b', allow_none=True), b_div, b_mod
+    o.init_a, o.init_b = _tptr(init_a, 'init_a', allow_none=True), _tptr(init_b, 'init_b', allow_none=True)
+    o.save_row0, o.n_rows, o.out = save_row0, n_rows, _tptr(out, 'out', allow_none=True)
+    path = PsnMlpPath() if path is None else path
+    with _Prof('mlp_infer', n_rows, None if macs_per_row is None else 2.0 * macs_per_row * n_rows) as prof:
+        _check(_lib.psn_mlp_launch(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'), ctypes.byref(o),
+                                   ctypes.byref(path), _stream()), 'mlp_infer')
+        prof.name = 'mlp_chain' if path.chain else 'mlp_infer'     # the lean / the chain engine, as the library chose
     return out
 
 

@@ -646,7 +646,7 @@ def mf_shade(light_dir, view, normal, albedo, rough, light_int, vis, f0):
 
 # --------------------------------------------------------------------------- visibility net: shading + supervision rows
 # ReLU-backward chains read the forward launch's SIGN BITS (32 bytes per row and layer, written beside the activation dumps:
-# psn_mlp_infer_bits / PSN_ACT_RELU_BITS) instead of re-reading the 1 KB activation rows as masks -- d z = d h * (h > 0) either
+# PsnMlpLaunch.save_bits_ptrs / PSN_ACT_RELU_BITS) instead of re-reading the 1 KB activation rows as masks -- d z = d h * (h > 0) either
 # way, bit for bit; 16 operand loads per lane and layer fewer in the chain (each VMEM instruction of a stage costs the chain
 # about 1 %).  False: the activation rows themselves (PSN_ACT_RELU_MASK; A/B and tests).
 RELU_SIGN_BITS = True
@@ -676,7 +676,7 @@ class VisibilityPair(torch.autograd.Function):
         (large) backward kernels are queued first, ahead of the many small launches of the other networks.
         live_count (float32 [1] on the device): pe_x is a surface list padded to a fixed capacity of which the first
         live_count[0] rows are real -- the workgroups of the gradient-free shading rows that hold padding only leave early
-        (psn_mlp_infer_padded; their outputs are zeros, which nothing reads: ops.ScatterRows drops the padding rows)."""
+        (PsnMlpLaunch.live_count; their outputs are zeros, which nothing reads: ops.ScatterRows drops the padding rows)."""
         Ws, bs = params[0::2], params[1::2]
         Ns, LV = pe_x.shape[0], pe_l.shape[0]
         V = LV - n_shade

@@ -61,7 +61,7 @@ class GraphedTrainStep(object):
         count differs share ONE graph and the step has no host synchronisation even for the reference's dictionary; the dead rows
         behind the real ones contribute exact zeros (their dense outputs are never written, their gradients are zeroed by
         psn_gather_rows_valid); the gradient-free shading rows among them -- 92 % of the rows of the BEAR step -- are not even
-        evaluated (the visibility launch reads the count on the device, psn_mlp_infer_padded), the others are: (N - Ns) / Ns
+        evaluated (the visibility launch reads the count on the device, PsnMlpLaunch.live_count), the others are: (N - Ns) / Ns
         more rows in the small networks, the supervision rows, shading and losses, and split-K sums in a different order than
         the unpadded step (equal to rounding, not bit for bit).  An EMPTY mask gives no pixel a row (the pixel -> row map reads the
         count too): dense outputs, losses and gradients are those of the eager step on the empty batch.  ``pad_multiple`` = k > 0: for batches that bring their 'surface_idx'

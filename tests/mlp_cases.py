@@ -6,7 +6,7 @@ tests/test_mlp_gpu.py runs every case on the device.
 A *case* is a plain dict.  ``build(case)`` turns it into a network (plain float32 CPU tensors, seeded per case), its
 inputs and operands; ``evaluate(net, dtype)`` is the definition of what the launch computes: every layer in the order of
 the kernel's header comment, in ``dtype`` (float64 = the truth, float32 = the reference arithmetic), returning the output, the
-first and second dump of every hidden layer.  ``dispatch(case)`` restates the conditions of mlp_infer_impl and of the kernel's
+first and second dump of every hidden layer.  ``dispatch(case)`` restates the conditions of mlp_infer_plan and of the kernel's
 prologue in Python: which instantiation runs and in which state every launch switch is.
 
 Weights are randn * 1.2 / sqrt(fan_in), biases randn * 0.05 (the scales of tests/test_kernels_gpu.py).
@@ -464,7 +464,7 @@ WRONG_FORMS = ('swap_ab', 'no_a_div', 'drop_skip', 'double_bias', 'occ_sign')
 
 def sign_words(dump):
     """Sign-bit words of a dumped activation tensor [n, W] (float32 ndarray): word (row, g) bit 4 mt + r = (feature 16 mt + 4 g + r
-    > 0), as int64 [n, 4] (the header of psn_mlp_infer_bits)."""
+    > 0), as int64 [n, 4] (the header of PsnMlpLaunch.save_bits_ptrs)."""
     d = np.asarray(dump)
     n, W = d.shape
     words = np.zeros((n, 4), dtype=np.uint64)
@@ -501,7 +501,7 @@ def dead_rows(c, live):
 
 
 def dispatch(c, net=None, point_major=True, live=None):
-    """The launch path of a case: a restatement of mlp_infer_impl / mlp_infer_pe_impl / psn_march_sweep and of the kernel prologue."""
+    """The launch path of a case: a restatement of mlp_infer_plan / mlp_infer_pe_impl / psn_march_sweep and of the kernel prologue."""
     net = net or build(c)
     hid = net.width // 32
     shapes = layer_shape(net)
@@ -544,7 +544,7 @@ def dispatch(c, net=None, point_major=True, live=None):
                 half_final=0 < n_out <= 16, wide_final=chain_ and hid == 8 and n_out > 32, blocks_straddle=straddle, name=name)
 
 
-# every instantiation the fp32 dispatcher can launch (mlp_infer_impl, mlp_infer_pe_impl, psn_march_sweep)
+# every instantiation the fp32 dispatcher can launch (mlp_infer_plan, mlp_infer_pe_impl, psn_march_sweep)
 INSTANTIATIONS = ('lean/16', 'lean/8', 'lean/4', 'chain/16', 'chain/8', 'chain/4', 'lean/16/trim', 'chain/16/trim',
                   'chain/16/froma', 'chain/16/trim/froma', 'lean/16/src2/trim', 'lean/16/src3/trim')
 

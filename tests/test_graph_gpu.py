@@ -196,7 +196,7 @@ def test_surface_index_is_nonzero_padded_with_the_last_entry(cuda, n):
 
 @pytest.mark.parametrize('ns,live', [(1000, 517), (1024, 0), (1024, 1024), (4096, 3700), (640, 64)])
 def test_padded_visibility_launch_skips_only_padding_workgroups(cuda, ns, live):
-    """psn_mlp_infer_padded through ops.VisibilityPair.launch: with a device-side live count the shading rows (L groups of ns) of
+    """PsnMlpLaunch.live_count through ops.VisibilityPair.launch: with a device-side live count the shading rows (L groups of ns) of
     workgroups that hold padding only are zeros, every other output and every dump of the supervision rows is bit-identical to
     the plain launch."""
     from psnerf_amd import ops

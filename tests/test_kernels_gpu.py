@@ -423,7 +423,7 @@ def test_fused_geo_occupancy(cuda):
 
 
 def test_mlp_chain_activation_programs(cuda):
-    """Every per-layer activation program of the chain engine (psn_mlp_infer with operands and dumps) against a
+    """Every per-layer activation program of the chain engine (psn_mlp_launch with operands and dumps) against a
     float64 restatement: ragged row count, input-feature k-tiles, two operands, two dumps, HEAD side outputs."""
     from psnerf_amd import hip, fused
     g = torch.Generator().manual_seed(0)

@@ -524,13 +524,16 @@ def _run_c1(c, net, pk, ta, tb, mods, cuda, order=None):
     kw = {}
     if c['live'] is not None:
         kw = dict(live=(torch.tensor([float(c['live'])], device=cuda), c['period']), save_row0=c['save_row0'])
-    call = lambda: pk(ta, n, a_div=a_div, a_mod=a_mod, tab_b=tb, b_div=b_div, b_mod=b_mod, out=out, **kw)
+    path = hip.PsnMlpPath()
+    call = lambda: pk(ta, n, a_div=a_div, a_mod=a_mod, tab_b=tb, b_div=b_div, b_mod=b_mod, out=out, path=path, **kw)
     if order is None:
         call()
     else:
         with hip.block_order(order):
             call()
     assert guards_intact(whole, n)
+    # the lean engine, on split-bf16 stages exactly when the pack holds them
+    assert path.blocks > 0 and not path.chain and path.x3 == int(pk.desc.w_format == hip.W_BF16X2)
     return out
 
 
@@ -582,8 +585,10 @@ def test_bf16x2_stages_random_weights_vs_modelled_arithmetic(mods, cuda):
     assert pk.desc.w_format == hip.W_BF16X2
     dumps = [nan_buffer(Q, 256, cuda) for _ in range(len(Ws))]
     whole, out = nan_buffer(Q, 1, cuda)
-    pk(pe, Q, save=[d for _, d in dumps], out=out)
+    path = hip.PsnMlpPath()
+    pk(pe, Q, save=[d for _, d in dumps], out=out, path=path)
     assert guards_intact(whole, Q) and all(guards_intact(w_, Q) for w_, _ in dumps)
+    assert path.chain == 1 and path.x3 == 1 and path.width16 == 16
     t64, t32 = lc.geo_chain_model(Ws, bs, skip, pe.cpu(), torch.float64), lc.geo_chain_model(Ws, bs, skip, pe.cpu(), torch.float32)
     record('bf16x2/chain', 'C2-chain logit', out, t64[0], t32[0])
     record('bf16x2/chain', 'C2-chain features', dumps[-1][1], t64[1], t32[1])

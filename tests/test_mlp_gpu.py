@@ -80,6 +80,18 @@ def check(c, path, name, got, truth, ref):
         _WORST[path] = (rh, rr, '%s %s' % (c['id'], name))
 
 
+def assert_path(c, net, path, **kw):
+    """What the library launched (PsnMlpPath) is the instantiation mlp_cases.dispatch states for the case."""
+    d = mc.dispatch(c, net, **kw)
+    assert path.blocks > 0, '%s: nothing was launched' % c['id']
+    got = dict(chain=bool(path.chain), hid=path.width16 // 2, src=path.src, trim=bool(path.trim), from_a=bool(path.from_a),
+               point_major=path.pm_period != 0)
+    assert got == {k: d[k] for k in got}, '%s: launched %s' % (c['id'], got)
+    name = '%s/%d%s%s%s' % ('chain' if path.chain else 'lean', path.width16, '/src%d' % path.src if path.src else '',
+                            '/trim' if path.trim else '', '/froma' if path.from_a else '')
+    assert name == d['name'], c['id']
+
+
 def pack_net(net, mods, cuda):
     hip, fused = mods
     names = dict(none='NONE', relu='RELU', softplus='SOFTPLUS100')
@@ -174,13 +186,15 @@ def run_lean(c, net, pk, mods, cuda, order=None, live=None, dumps=True, res=None
     kw = {}
     if live is not None:
         kw['live'] = (torch.tensor([float(live)], device=cuda), c['period'])
+    path = hip.PsnMlpPath()
     call = lambda: pk(ta, n, a_div=a_div, a_mod=a_mod, tab_b=tb, b_div=b_div, b_mod=b_mod, out=out, save=save,
-                      save_row0=row0, save_bits=bits, **kw)
+                      save_row0=row0, save_bits=bits, path=path, **kw)
     if order is None:
         call()
     else:
         with hip.block_order(order):
             call()
+    assert_path(c, net, path, point_major=order != 'row', live=live)
     res.update(out=out, save=save, bits=bits)
     for w_, rows, g_ in res['bufs']:
         assert guards_intact(w_, rows, g_), '%s: a guard row was written' % c['id']
@@ -225,7 +239,7 @@ def test_lean_engine_vs_float64(mods, cuda, c):
 
 @pytest.mark.parametrize('c', mc.E_CASES, ids=mc.case_id)
 def test_padded_row_sets(mods, cuda, c):
-    """psn_mlp_infer_padded: the all-padding blocks (stated from live and period) are exact zeros, every other row and every dump
+    """PsnMlpLaunch.live_count: the all-padding blocks (stated from live and period) are exact zeros, every other row and every dump
     equals the plain launch bit for bit, in both block orders; the plain launch meets the float64 bound."""
     net, t64, t32 = mc.reference(c)
     pk = pack_net(net, mods, cuda)
@@ -280,10 +294,12 @@ def run_chain(c, net, pk, mods, cuda, masks=None, res=None):
         kw['save_tiles'] = []
     if net.rk is not None:
         kw['rank_init'] = (dv(net.rk[0]).contiguous(), dv(net.rk[1]).contiguous())
+    path = hip.PsnMlpPath()
     hip.mlp_infer(pk.desc, pk.w, pk.b, dv(net.tab_a), 1, n, None, 1, 1, n, out=out, init_a=dv(net.init_direct), save=save, save_row0=0,
                   mask=mask if any(m is not None for m in mask) else None, aux2=aux2 if any(m is not None for m in aux2) else None,
                   save2=save2 if any(m is not None for m in save2) else None, act_init=dv(net.act_init),
-                  act_init_rows=net.act_init_rows, **kw)
+                  act_init_rows=net.act_init_rows, path=path, **kw)
+    assert_path(c, net, path)
     for w_, rows, g_ in res['bufs']:
         assert guards_intact(w_, rows, g_), '%s: a guard row was written' % c['id']
     res.update(out=out, save=save, save2=save2)
@@ -339,10 +355,12 @@ def test_encoding_prologue_vs_float64(mods, cuda, c):
     pk = pack_net(net, mods, cuda)
     path = mc.dispatch(c, net)['name']
     pts = net.points.to(cuda).contiguous()
+    launched = hip.PsnMlpPath()
     if c['src'] == 3:
         s = net.sweep
         occ, skip = hip.march_sweep(pk.desc, pk.w, pk.b, s['origin'].to(cuda), s['direction'].to(cuda), s['far'].to(cuda), s['u'].to(cuda),
-                                    s['omu'].to(cuda), s['near'], c['steps'], 0.5, c['octaves'], c['pe_scale'], early_exit=False)
+                                    s['omu'].to(cuda), s['near'], c['steps'], 0.5, c['octaves'], c['pe_scale'], early_exit=False, path=launched)
+        assert_path(c, net, launched)
         assert skip is None and occ.shape == (c['rays'], c['steps'])
         check(c, path, 'occ', occ.reshape(-1, 1), t64['out'], t32['out'])
         # the same points through the table-free point launch: bit-identical
@@ -351,7 +369,8 @@ def test_encoding_prologue_vs_float64(mods, cuda, c):
         return
     Q = pts.shape[0]
     whole, out = nan_buffer(Q, net.n_out, cuda, G_OUT)
-    pk.on_points(pts, c['octaves'], c['pe_scale'], out=out)
+    pk.on_points(pts, c['octaves'], c['pe_scale'], out=out, path=launched)
+    assert_path(c, net, launched)
     assert guards_intact(whole, Q, G_OUT)
     if c['count'] is None:
         check(c, path, 'out', out, t64['out'], t32['out'])
@@ -360,17 +379,18 @@ def test_encoding_prologue_vs_float64(mods, cuda, c):
     count = torch.tensor([cnt], dtype=torch.int64, device=cuda)
     if not c['scatter']:
         w2, o2 = nan_buffer(Q, net.n_out, cuda, G_OUT)
-        pk.on_points(pts, c['octaves'], c['pe_scale'], out=o2, n_rows_dev=count)
+        pk.on_points(pts, c['octaves'], c['pe_scale'], out=o2, n_rows_dev=count, path=launched)
         assert guards_intact(w2, Q, G_OUT) and untouched(o2[cnt:]), '%s: a row behind the count was written' % c['id']
         got = o2[:cnt]
     else:
         perm = torch.randperm(mc.SCATTER_ROWS, generator=torch.Generator().manual_seed(cnt))[:Q].to(cuda)
         w2, o2 = nan_buffer(mc.SCATTER_ROWS, net.n_out, cuda, G_OUT)
-        pk.on_points(pts, c['octaves'], c['pe_scale'], out=o2, n_rows_dev=count, out_rows=perm)
-        named = torch.zeros(mc.SCATTER_ROWS, dtype=torch.bool, device=cuda)
+        pk.on_points(pts, c['octaves'], c['pe_scale'], out=o2, n_rows_dev=count, out_rows=perm, path=launched)
+        named =torch.zeros(mc.SCATTER_ROWS, dtype=torch.bool, device=cuda)
         named[perm[:cnt]] = True
         assert guards_intact(w2, mc.SCATTER_ROWS, G_OUT) and untouched(o2[~named]), '%s: an entry no out_rows names was written' % c['id']
         got = o2[perm[:cnt]]
+    assert_path(c, net, launched)
     assert torch.equal(got.view(torch.int32), out[:cnt].view(torch.int32)), '%s: differs from the plain launch' % c['id']
     check(c, path, 'out', got, t64['out'][:cnt], t32['out'][:cnt])
 
@@ -393,8 +413,8 @@ def test_argument_checks_refuse_and_launch_nothing(mods, cuda, c):
 
 
 def test_live_count_on_a_chain_launch_is_refused_by_the_library(mods, cuda):
-    """psn_mlp_infer_padded takes no chain operands, so a chain launch reaches it only through a program that needs none (HEAD):
-    called through the C ABI directly, the `!chain` clause of mlp_infer_impl answers PSN_E_ARG."""
+    """A live count with no chain OPERAND at all still meets a chain launch when a program makes it one (HEAD): called through the
+    C ABI directly, the `!chain` clause of the planner (csrc/mlp_infer.hip, mlp_infer_plan) answers PSN_E_ARG."""
     import ctypes
     hip, _ = mods
     n, row0 = 128, 64
@@ -405,9 +425,12 @@ def test_live_count_on_a_chain_launch_is_refused_by_the_library(mods, cuda):
     dumps = [nan_buffer(n - row0, 256, cuda, G_OUT) for _ in range(2)]
     save = (ctypes.c_void_p * 2)(*[d.data_ptr() for _, d in dumps])
     ta, live = net.tab_a.to(cuda), torch.tensor([3.0], device=cuda)
-    rc = hip._lib.psn_mlp_infer_padded(ctypes.byref(pk.desc), pk.w.data_ptr(), pk.b.data_ptr(), ta.data_ptr(), 1, n, None, 1, 1, None, None,
-                                       save, row0, n, out.data_ptr(), live.data_ptr(), 64, hip._stream())
-    assert rc != 0
+    o, path = hip.PsnMlpLaunch(), hip.PsnMlpPath()
+    o.tab_a, o.a_div, o.a_mod, o.b_div, o.b_mod = ta.data_ptr(), 1, n, 1, 1
+    o.save_ptrs, o.save_row0, o.n_rows, o.out = ctypes.addressof(save), row0, n, out.data_ptr()
+    o.live_count, o.live_period = live.data_ptr(), 64
+    rc = hip._lib.psn_mlp_launch(ctypes.byref(pk.desc), pk.w.data_ptr(), pk.b.data_ptr(), ctypes.byref(o), ctypes.byref(path), hip._stream())
+    assert rc != 0 and path.blocks == 0
     with pytest.raises(RuntimeError, match='mlp_infer_padded: needs the lean variant'):
         hip._check(rc, 'mlp_infer_padded')
     torch.cuda.synchronize()
@@ -415,14 +438,16 @@ def test_live_count_on_a_chain_launch_is_refused_by_the_library(mods, cuda):
 
 
 def test_live_count_on_a_chain_launch_is_refused_by_the_wrapper(mods, cuda):
-    """hip.mlp_infer refuses the same before any C call (the library's own check: the test above)."""
+    """hip.mlp_infer states no rule of its own: a live count beside a chain operand (a mask) reaches the library, whose check (the
+    test above) refuses it with the same words, and nothing is written."""
     hip, _ = mods
     c = mc.chain('ARG-live-on-chain', n=128, prog=('relu_mask', 'none'), n_out=3)
     net = mc.build(c)
     pk = pack_net(net, mods, cuda)
     whole, out = nan_buffer(128, 3, cuda, G_OUT)
-    with pytest.raises(RuntimeError, match='live count is for plain forward launches'):
+    path = hip.PsnMlpPath()
+    with pytest.raises(RuntimeError, match='mlp_infer_padded: needs the lean variant'):
         hip.mlp_infer(pk.desc, pk.w, pk.b, net.tab_a.to(cuda), 1, 128, None, 1, 1, 128, out=out, mask=[net.mask[0].to(cuda), None, None],
-                      save_row0=64, live=(torch.tensor([3.0], device=cuda), 64))
+                      save_row0=64, live=(torch.tensor([3.0], device=cuda), 64), path=path)
     torch.cuda.synchronize()
-    assert untouched(whole)
+    assert untouched(whole) and path.blocks == 0

@@ -707,7 +707,7 @@ def test_indirect_occupancy_launch_reads_its_row_count_on_the_device(cuda):
 @pytest.mark.parametrize('n', [0, 1, 63, 64, 5000, 70001])
 def test_occupancy_with_in_kernel_encoding_is_bit_identical(cuda, n):
     """psn_mlp_infer_pe (positional encoding formed in the kernel prologue, network.py:141-150 + 85-101 in one launch) ==
-    psn_pe_encode + psn_mlp_infer on the [Q,64] table, bit for bit, incl. ragged row counts and far-away points."""
+    psn_pe_encode + psn_mlp_launch on the [Q,64] table, bit for bit, incl. ragged row counts and far-away points."""
     from psnerf_amd import hip
     cfg, net, ren = _renderer(cuda)
     g = torch.Generator().manual_seed(n)
