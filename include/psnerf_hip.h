@@ -709,7 +709,7 @@ int psn_weight_norm_bwd(int n_items, const PsnWnItem* items, void* stream);
  * n_out <= 32 outputs followed by out_act.  The input block of row q is
  * [ A[(q / a_div) % a_mod, 0:64] | B[(q / b_div) % b_mod, 0:64] ] with bf16 tables of 64 columns (128-byte rows).
  *
- * Weight stream (bf16, one contiguous buffer, in execution order), each piece written by psn_mlp_pack_bf16:
+ * Weight stream (bf16, one contiguous buffer, in execution order), each piece written by psn_lowp_pack with one plane:
  *   layer 0:      input block k-steps 0..7 [W_a | W_b] natural order, 1 bias k-step            (72 KB)
  *   layer l >= 1: activation k-steps 0..7 (permuted), 1 bias k-step (72 KB); if has_in[l]: input block k-steps 0..7
  *                 (64 KB); activation k-steps 8..15 (64 KB)
@@ -726,11 +726,16 @@ typedef struct {
     uint8_t has_in[PSN_MLP_MAX_LAYERS + 4];
 } PsnBf16Desc;
 
-/* k-steps [ks0, ks0 + n_ks) of W[rows, cols] (row-major fp32, ldw floats per row, zero-extended) for n_ot output tiles
- * of 32 (8 = hidden layer, 1 = final layer) -> dst[n_ks][n_ot][64 lanes][8] bf16.  permuted != 0: K follows the
- * register layout of the previous layer's activations; 0: natural order (input block, bias columns). */
-int psn_mlp_pack_bf16(const float* W, int64_t ldw, int rows, int cols, int permuted, int n_ot, int ks0, int n_ks,
-                      uint16_t* dst, void* stream);
+/* The packers of this engine (n_planes = 1, n_pieces = 2) and of the split-bf16 engine below (3, 3; anything else is refused).
+ * Piece p of an fp32 value = the round-to-nearest-even bf16 of what pieces 0 .. p - 1 left: three add up to the value exactly.
+ * psn_lowp_pack: k-steps [ks0, ks0 + n_ks) of W[rows, cols] (row-major fp32, ldw floats per row, zero-extended) for n_ot output
+ * tiles of 32 (8 = hidden layer, 1 = final layer) -> dst[n_ks][n_ot][n_planes][64 lanes][8] bf16, plane p = piece p, element j
+ * of lane (m, h) = W[32 ot + m][k].  permuted != 0: K follows the register layout of the previous layer's activations,
+ * k = 32 (ks / 2) + 16 (ks % 2) + 8 (j / 4) + 4 h + (j % 4); 0: natural order (input block, bias columns), k = 16 ks + 8 h + j.
+ * psn_lowp_pack_bias: V [n, 256] fp32 -> dst[n][8 tiles][64 lanes][8] bf16: n bias k-steps, K slots 0 .. n_pieces - 1 = the pieces. */
+int psn_lowp_pack(const float* W, int64_t ldw, int rows, int cols, int permuted, int n_ot, int ks0, int n_ks, int n_planes,
+                  uint16_t* dst, void* stream);
+int psn_lowp_pack_bias(const float* V, int64_t n, int n_pieces, uint16_t* dst, void* stream);
 
 /* out [n_rows, n_out] fp32.  tab_b may be NULL (input block = table A only).  All device buffers 16-byte aligned. */
 int psn_mlp_infer_bf16(const PsnBf16Desc* desc, const uint16_t* packed_w, const float* final_bias, const uint16_t* tab_a,
@@ -741,8 +746,8 @@ int psn_mlp_infer_bf16(const PsnBf16Desc* desc, const uint16_t* packed_w, const 
  * n = surface point; the 512-light evaluation of stage2/eval.py:199-218): the input block of a row is table A row n
  * ([rows_per_group, 64] bf16) and the group's part of every input layer, W_b * B[g] + b, arrives as that group's bias:
  * group_bias [n_groups][n_in][8 KB] = one bias k-step per (group, input layer in network order), written by
- * psn_bf16_pack_group_bias from fp32 rows.  The light's encoding and its weight columns therefore stay in fp32 (one small
- * product per light and input layer on the host side) and cost no k-steps per row.
+ * psn_lowp_pack_bias (two pieces) from fp32 rows.  The light's encoding and its weight columns therefore stay in fp32 (one
+ * small product per light and input layer on the host side) and cost no k-steps per row.
  * Weight stream: as above with 4 input k-steps (table A columns only) instead of 8 and WITHOUT the bias k-step of the
  * layers that read the input block:
  *   layer 0: input k-steps 0..3 (32 KB);  layer l >= 1: activation k-steps 0..7, bias k-step unless has_in[l];
@@ -751,34 +756,28 @@ int psn_mlp_infer_bf16(const PsnBf16Desc* desc, const uint16_t* packed_w, const 
 int psn_mlp_infer_bf16_grouped(const PsnBf16Desc* desc, const uint16_t* packed_w, const float* final_bias,
                                const uint16_t* tab_a, int64_t rows_per_group, const uint16_t* group_bias, int64_t n_groups,
                                float* out, void* stream);
-/* V [n, 256] fp32 -> dst [n][4096] bf16: bias k-steps (K slot 0 = bf16(v), slot 1 = bf16(v - slot 0), the rest 0). */
-int psn_bf16_pack_group_bias(const float* V, int64_t n, uint16_t* dst, void* stream);
 
 /* ------------------------------------------------------------------------
- * Split-bf16 ("bf16x6") inference engine, csrc/mlp_infer_x3.hip -- EXPERIMENT, opt-in, gradient-free rows only.  The
- * network of psn_mlp_infer_bf16_grouped with every fp32 operand carried as three bf16 planes (hi / mid / lo, exact sum)
- * and every product as the six partial products of weight >= 2^-16: fp32-class results from the bf16 matrix pipe.
- *   psn_x3_pack        W [rows, cols] fp32 -> k-steps [ks0, ks0 + n_ks) as [ks][n_ot tiles][3 planes][64 lanes][8] bf16 (K order
- *                      as psn_mlp_pack_bf16: natural for the input block, permuted for activations)
- *   psn_x3_pack_bias   V [n, 256] fp32 -> n bias k-steps [8 tiles][64 lanes][8] bf16 (K slots 0..2 = the three pieces)
+ * Split-bf16 ("bf16x6") inference engine, csrc/mlp_infer_x3.hip -- EXPERIMENT, opt-in, gradient-free rows only.  The network of
+ * psn_mlp_infer_bf16_grouped with every fp32 operand carried as three bf16 planes (hi / mid / lo, exact sum) and every product as the
+ * six partial products of weight >= 2^-16: fp32-class results from the bf16 matrix pipe.  Weights and bias k-steps: psn_lowp_pack and
+ * psn_lowp_pack_bias with three planes / pieces.  Every entry (psn_march_sweep_x3 since version 102) refuses a packed_w or bias_steps
+ * (grouped form: also U, V) off a 16-byte boundary.
  *   psn_mlp_infer_x3_grouped: rows (g, n) -> g * rows_per_group + n; packed_w = the weight stream in execution order (48 KB
  *     stages of 2 k-steps: every hidden layer >= 1 = its 16 activation k-steps; final layer = one stage [16 k-steps][3 planes],
  *     + 56 KB of padding); bias_steps [n_hidden][8 KB] (used for the layers without an input block).  The layers that read
  *     the input block start from U[n] + V[g] (both fp32, [., n_input_layers * 256]): U = W_a x_n per row, V = W_b x_g + b per
  *     group, as the init tables of psn_mlp_launch; layer 0 is that sum alone.  out [n_groups * rows_per_group, n_out] fp32.
  * ---------------------------------------------------------------------- */
-int psn_x3_pack(const float* W, int64_t ldw, int rows, int cols, int permuted, int n_ot, int ks0, int n_ks, uint16_t* dst, void* stream);
-int psn_x3_pack_bias(const float* V, int64_t n, uint16_t* dst, void* stream);
 int psn_mlp_infer_x3_grouped(const PsnBf16Desc* desc, const uint16_t* packed_w, const uint16_t* bias_steps, const float* final_bias,
                              const float* U, int64_t rows_per_group, const float* V, int64_t n_groups, float* out, void* stream);
-/* The stage-1 occupancy network (stage1/model/network.py:85-101: softplus(beta = 100) stack on the positional encoding of the
- * point, cat[h, pe] / sqrt(2) in front of the skip layer, output row 0) on the split-bf16 engine, for GRADIENT-FREE queries
- * (shadow rays rendering.py:378-408, ray march :447-462, shape_extract :297-376): out[r] = sigmoid(-10 logit(points[r])).
- * desc: n_hidden, n_out = 1, out_act; packed_w: layer 0 as 4 natural-order k-steps of its encoding columns (psn_x3_pack,
- * permuted = 0), every further hidden layer 16 permuted k-steps (the skip layer as ONE 256-input matrix, scaled by 1 / sqrt(2)),
- * the final row as one stage; bias_steps [n_hidden][4096] (psn_x3_pack_bias); final_bias [32].  The kernel forms the encoding
- * (pe_octaves, pe_scale: the expressions of psn_pe_encode) and writes it into input features pe_first .. of layer skip_layer
- * (-1: none).  n_rows_dev / out_rows: as psn_mlp_infer_pe_indirect (row count on the device, outputs scattered). */
+/* The stage-1 occupancy network (stage1/model/network.py:85-101: softplus(beta = 100) stack on the positional encoding of the point,
+ * cat[h, pe] / sqrt(2) in front of the skip layer, output row 0) on the split-bf16 engine, for GRADIENT-FREE queries (shadow rays
+ * rendering.py:378-408, ray march :447-462, shape_extract :297-376): out[r] = sigmoid(-10 logit(points[r])). desc: n_hidden, n_out = 1,
+ * out_act; packed_w: layer 0 as 4 natural-order k-steps of its encoding columns, every further hidden layer 16 permuted k-steps (the
+ * skip layer as ONE 256-input matrix, scaled by 1 / sqrt(2)), the final row as one stage; bias_steps [n_hidden][4096]; final_bias [32].
+ * The kernel forms the encoding (pe_octaves, pe_scale: the expressions of psn_pe_encode) and writes it into input features pe_first ..
+ * of layer skip_layer (-1: none).  n_rows_dev / out_rows: as psn_mlp_infer_pe_indirect (row count on the device, outputs scattered). */
 int psn_mlp_infer_x3_occ(const PsnBf16Desc* desc, const uint16_t* packed_w, const uint16_t* bias_steps, const float* final_bias,
                          const float* points, int64_t n_rows, const long long* n_rows_dev, const int64_t* out_rows, int pe_octaves,
                          float pe_scale, int skip_layer, int pe_first, float* out, void* stream);

@@ -12,4 +12,4 @@ void set_error(const char* fmt, ...) {
 }  // namespace psn
 
 extern "C" const char* psn_last_error(void) { return psn::g_err; }
-extern "C" int psn_version(void) { return 101; }
+extern "C" int psn_version(void) { return 102; }

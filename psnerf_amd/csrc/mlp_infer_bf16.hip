@@ -11,7 +11,7 @@
 // holds, for output tile ot and register v = 4q + r, feature 32 ot + 8 q + 4 h + r of row n (MFMA C/D layout).
 // After ReLU the pairs (v, v+1) are rounded to bf16 (v_cvt_pk_bf16_f32, RNE; ReLU = v_pk_max_i16 with 0 on the
 // packed halves) and registers [8 qp, 8 qp + 8) of tile ot become B operand k-step 2 ot + qp of the next layer, whose
-// lane supplies K indices 8 h + j  <->  feature 32 ot + 16 qp + 8 (j / 4) + 4 h + (j % 4): psn_mlp_pack_bf16
+// lane supplies K indices 8 h + j  <->  feature 32 ot + 16 qp + 8 (j / 4) + 4 h + (j % 4): psn_lowp_pack
 // orders the weight columns to match.  The input block [PE(x) | PE(l)] (2 x 64 bf16 per row, gathered from two
 // tables) is consumed as 8 natural-order k-steps; the bias rides along as one more k-step whose B operand is the
 // constant (1, 1, 0, ...) against the columns (bf16(b), bf16(b - bf16(b))): no VALU add, ~16 significant bits.
@@ -25,15 +25,11 @@
 //
 // Roofline: MFMA-bound in bf16 (2.5 PFLOP/s dense).  Measured: 1.35 PFLOP/s algorithmic on the visibility net of
 // bear.conf (0.54 of the peak), matrix pipe 67 % busy at 2.25 GHz.
-#include "common.h"
+#include "lowp.h"
 
 namespace psn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef short shortx2 __attribute__((ext_vector_type(2)));
-typedef int intx4 __attribute__((ext_vector_type(4)));
 
 struct Bf16Args {
     PsnBf16Desc d;
@@ -45,7 +41,7 @@ struct Bf16Args {
     unsigned n_rows;
     float* out;
     // GROUPED: rows (g, n) -> g * rows_per_group + n read table A row n; group g supplies the bias k-steps of the layers
-    // that read the input block (gbias [n_groups][n_in_layers][8 KB], psn_bf16_pack_group_bias)
+    // that read the input block (gbias [n_groups][n_in_layers][8 KB], psn_lowp_pack_bias)
     const unsigned char* gbias;
     unsigned rows_per_group, tiles_per_group, n_in_layers;
 };
@@ -350,87 +346,20 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_bf16_kernel(Bf16Args g) {
     }
 }
 
-// Bias k-steps of the row groups: V [n, 256] fp32 (one row per (group, input layer): W_b * B[group] + b) ->
-// [n][8 output tiles][64 lanes][8] bf16 in the natural K order of a bias k-step: K slot 0 = bf16(v), slot 1 = bf16(v - slot 0).
-__global__ __launch_bounds__(256) void bf16_pack_group_bias_kernel(const float* __restrict__ V, int64_t n, uint16_t* __restrict__ dst) {
-    const int64_t total = n * 4096;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int j = (int)(e & 7);
-        const int lane = (int)((e >> 3) & 63);
-        const int ot = (int)((e >> 9) & 7);
-        const int64_t r = e >> 12;
-        const int k = 8 * (lane >> 5) + j;
-        float v = 0.0f;
-        if (k < 2) {
-            const float b = V[r * 256 + 32 * ot + (lane & 31)];
-            const float hi = (float)(__bf16)b;
-            v = k == 0 ? hi : b - hi;
-        }
-        dst[e] = __builtin_bit_cast(uint16_t, (__bf16)v);
-    }
-}
-
-// W[rows, cols] (row-major, ldw floats per row), zero-extended, k-steps [ks0, ks0 + n_ks) -> [ks][ot][lane][8] bf16:
-//   lane (m = lane & 31, h = lane >> 5), element j  <-  W[32 ot + m][k],
-//   k = 16 ks + 8 h + j (natural order: input block, bias columns) or
-//   k = 32 (ks / 2) + 16 (ks % 2) + 8 (j / 4) + 4 h + (j % 4) (permuted: previous layer's activations).
-__global__ __launch_bounds__(256) void mlp_pack_bf16_kernel(const float* __restrict__ W, int64_t ldw, int rows, int cols,
-                                                            int permuted, int n_ot, int ks0, int n_ks, uint16_t* __restrict__ dst) {
-    const int64_t total = (int64_t)n_ks * n_ot * 512;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int j = (int)(e & 7);
-        const int lane = (int)((e >> 3) & 63);
-        const int64_t blk = e >> 9;
-        const int ot = (int)(blk % n_ot);
-        const int ks = ks0 + (int)(blk / n_ot);
-        const int m = lane & 31, h = lane >> 5;
-        const int r = 32 * ot + m;
-        const int k = permuted ? 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3) : 16 * ks + 8 * h + j;
-        float v = 0.0f;
-        if (r < rows && k < cols) v = W[(int64_t)r * ldw + k];
-        dst[e] = __builtin_bit_cast(uint16_t, (__bf16)v);
-    }
-}
-
 }  // namespace psn
 
-extern "C" int psn_mlp_pack_bf16(const float* W, int64_t ldw, int rows, int cols, int permuted, int n_ot, int ks0, int n_ks,
-                                 uint16_t* dst, void* stream) {
+// What both forms check and fill alike: the descriptor, the alignment of the LDS-DMA and table sources (`tabs`: the form's
+// other tables, addresses ORed) and the operands every launch has
+static int bf16_base_args(psn::Bf16Args& a, const char* what, const PsnBf16Desc& d, const uint16_t* packed_w, const float* final_bias,
+                          const uint16_t* tab_a, uintptr_t tabs, float* out) {
     using namespace psn;
-    PSN_CHECK_ARG(W && dst, "mlp_pack_bf16: null pointer");
-    PSN_CHECK_ARG((n_ot == 8 || n_ot == 1) && ks0 >= 0 && n_ks >= 1 && ks0 + n_ks <= 16, "mlp_pack_bf16: n_ot=%d ks0=%d n_ks=%d", n_ot, ks0, n_ks);
-    PSN_CHECK_ARG(rows >= 1 && rows <= 32 * n_ot && cols >= 1 && cols <= 256 && ldw >= cols, "mlp_pack_bf16: %d x %d (ldw %lld) does not fit",
-                  rows, cols, (long long)ldw);
-    const int64_t total = (int64_t)n_ks * n_ot * 512;
-    const int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(mlp_pack_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, W, ldw, rows, cols, permuted, n_ot, ks0, n_ks, dst);
-    PSN_CHECK_LAUNCH("mlp_pack_bf16");
-    return PSN_OK;
-}
-
-static int bf16_launch(bool grouped, psn::Bf16Args& a, int64_t blocks, void* stream, const char* what) {
-    using namespace psn;
-    PSN_CHECK_ARG(blocks < (1ll << 31), "%s: too many rows", what);
-    const size_t lds_bytes = 2 * kStageBytes;
-    // 144 KB of dynamic LDS need the opt-in attribute; set per call (per-device state, cheap, no static flag to race on)
-    const void* fn = grouped ? reinterpret_cast<const void*>(&mlp_infer_bf16_kernel<true>) : reinterpret_cast<const void*>(&mlp_infer_bf16_kernel<false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        set_error("%s: cannot reserve %zu bytes of LDS: %s", what, lds_bytes, hipGetErrorString(e));
-        return PSN_E_LAUNCH;
-    }
-    if (grouped) hipLaunchKernelGGL(mlp_infer_bf16_kernel<true>, dim3((unsigned)blocks), dim3(kBfWaves * 64), lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(mlp_infer_bf16_kernel<false>, dim3((unsigned)blocks), dim3(kBfWaves * 64), lds_bytes, (hipStream_t)stream, a);
-    PSN_CHECK_LAUNCH(what);
-    return PSN_OK;
-}
-
-static int bf16_check_desc(const PsnBf16Desc& d, const char* what) {
-    using namespace psn;
-    PSN_CHECK_ARG(d.n_hidden >= 1 && d.n_hidden <= PSN_MLP_MAX_LAYERS, "%s: n_hidden=%d", what, d.n_hidden);
-    PSN_CHECK_ARG(d.n_out >= 1 && d.n_out <= 32, "%s: n_out=%d", what, d.n_out);
-    PSN_CHECK_ARG(d.out_act >= PSN_OUT_NONE && d.out_act <= PSN_OUT_OCC, "%s: out_act=%d", what, d.out_act);
-    PSN_CHECK_ARG(d.has_in[0] != 0, "%s: layer 0 must read the input block", what);
+    if (int rc = lowp_check_desc(d, what, 1, true)) return rc;
+    PSN_CHECK_ARG((((uintptr_t)packed_w | (uintptr_t)tab_a | tabs) & 15) == 0, "%s: buffers must be 16-byte aligned", what);
+    a.d = d;
+    a.w = reinterpret_cast<const unsigned char*>(packed_w);
+    a.final_bias = final_bias;
+    a.ta = reinterpret_cast<const unsigned char*>(tab_a);
+    a.out = out;
     return PSN_OK;
 }
 
@@ -439,25 +368,19 @@ extern "C" int psn_mlp_infer_bf16(const PsnBf16Desc* desc, const uint16_t* packe
                                   int64_t b_mod, int64_t n_rows, float* out, void* stream) {
     using namespace psn;
     PSN_CHECK_ARG(desc && packed_w && final_bias && tab_a && out, "mlp_infer_bf16: null pointer");
-    const PsnBf16Desc& d = *desc;
-    if (int rc = bf16_check_desc(d, "mlp_infer_bf16")) return rc;
-    PSN_CHECK_ARG(a_div >= 1 && a_mod >= 1 && (tab_b == nullptr || (b_div >= 1 && b_mod >= 1)), "mlp_infer_bf16: bad index map");
-    PSN_CHECK_ARG((((uintptr_t)packed_w | (uintptr_t)tab_a | (uintptr_t)tab_b) & 15) == 0, "mlp_infer_bf16: buffers must be 16-byte aligned");
-    if (n_rows <= 0) return PSN_OK;
     Bf16Args a = {};
-    a.d = d;
-    a.w = reinterpret_cast<const unsigned char*>(packed_w);
-    a.final_bias = final_bias;
-    a.ta = reinterpret_cast<const unsigned char*>(tab_a);
-    a.tb = reinterpret_cast<const unsigned char*>(tab_b);
+    if (int rc = bf16_base_args(a, "mlp_infer_bf16", *desc, packed_w, final_bias, tab_a, (uintptr_t)tab_b, out)) return rc;
+    PSN_CHECK_ARG(a_div >= 1 && a_mod >= 1 && (tab_b == nullptr || (b_div >= 1 && b_mod >= 1)), "mlp_infer_bf16: bad index map");
+    if (n_rows <= 0) return PSN_OK;
     PSN_CHECK_ARG(n_rows < (1ll << 31) && a_div < (1ll << 31) && a_mod <= (1ll << 24) && b_div < (1ll << 31) && b_mod <= (1ll << 24),
                   "mlp_infer_bf16: 32-bit index arithmetic: n_rows, divisors < 2^31, table rows <= 2^24");
+    a.tb = reinterpret_cast<const unsigned char*>(tab_b);
     a.a_div = (unsigned)a_div; a.a_mod = (unsigned)a_mod;
     a.b_div = (unsigned)(b_div > 0 ? b_div : 1); a.b_mod = (unsigned)(b_mod > 0 ? b_mod : 1);
     a.n_rows = (unsigned)n_rows;
-    a.out = out;
     const int rows_per_block = kBfWaves * 64;
-    return bf16_launch(false, a, (n_rows + rows_per_block - 1) / rows_per_block, stream, "mlp_infer_bf16");
+    return lowp_launch(&mlp_infer_bf16_kernel<false>, a, (n_rows + rows_per_block - 1) / rows_per_block, rows_per_block, 2 * kStageBytes, stream,
+                       "mlp_infer_bf16");
 }
 
 extern "C" int psn_mlp_infer_bf16_grouped(const PsnBf16Desc* desc, const uint16_t* packed_w, const float* final_bias,
@@ -465,34 +388,16 @@ extern "C" int psn_mlp_infer_bf16_grouped(const PsnBf16Desc* desc, const uint16_
                                           int64_t n_groups, float* out, void* stream) {
     using namespace psn;
     PSN_CHECK_ARG(desc && packed_w && final_bias && tab_a && group_bias && out, "mlp_infer_bf16_grouped: null pointer");
-    const PsnBf16Desc& d = *desc;
-    if (int rc = bf16_check_desc(d, "mlp_infer_bf16_grouped")) return rc;
-    PSN_CHECK_ARG((((uintptr_t)packed_w | (uintptr_t)tab_a | (uintptr_t)group_bias) & 15) == 0, "mlp_infer_bf16_grouped: buffers must be 16-byte aligned");
+    Bf16Args a = {};
+    if (int rc = bf16_base_args(a, "mlp_infer_bf16_grouped", *desc, packed_w, final_bias, tab_a, (uintptr_t)group_bias, out)) return rc;
     PSN_CHECK_ARG(rows_per_group >= 0 && n_groups >= 0 && rows_per_group <= (1ll << 24) && rows_per_group * n_groups < (1ll << 31),
                   "mlp_infer_bf16_grouped: 32-bit index arithmetic: rows per group <= 2^24, rows < 2^31");
     if (rows_per_group == 0 || n_groups == 0) return PSN_OK;
-    Bf16Args a = {};
-    a.d = d;
-    a.w = reinterpret_cast<const unsigned char*>(packed_w);
-    a.final_bias = final_bias;
-    a.ta = reinterpret_cast<const unsigned char*>(tab_a);
     a.gbias = reinterpret_cast<const unsigned char*>(group_bias);
     a.rows_per_group = (unsigned)rows_per_group;
     a.tiles_per_group = (unsigned)((rows_per_group + kBfWaves * 64 - 1) / (kBfWaves * 64));
     a.n_rows = (unsigned)(rows_per_group * n_groups);
-    int n_in = 0;
-    for (int l = 0; l < d.n_hidden; ++l) n_in += d.has_in[l] != 0;
-    a.n_in_layers = (unsigned)n_in;
-    a.out = out;
-    return bf16_launch(true, a, (int64_t)a.tiles_per_group * n_groups, stream, "mlp_infer_bf16_grouped");
-}
-
-extern "C" int psn_bf16_pack_group_bias(const float* V, int64_t n, uint16_t* dst, void* stream) {
-    using namespace psn;
-    PSN_CHECK_ARG(V && dst && n >= 1 && n < (1ll << 30), "bf16_pack_group_bias: V / dst / n=%lld", (long long)n);
-    const int64_t total = n * 4096;
-    const int blocks = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-    hipLaunchKernelGGL(bf16_pack_group_bias_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, V, n, dst);
-    PSN_CHECK_LAUNCH("bf16_pack_group_bias");
-    return PSN_OK;
+    a.n_in_layers = lowp_n_in(*desc);
+    return lowp_launch(&mlp_infer_bf16_kernel<true>, a, (int64_t)a.tiles_per_group * n_groups, kBfWaves * 64, 2 * kStageBytes, stream,
+                       "mlp_infer_bf16_grouped");
 }

@@ -21,14 +21,9 @@
 // + b = U[n] + V[g] with U = W_a pe(x) (one fp32 row per point) and V = W_b pe(l) + b (one per group) computed by two small
 // fp32 GEMMs on the host side; the layers that read the input block START their accumulators from U[n] + V[g] (fp32 adds)
 // and spend no MFMA on it: layer 0 is that sum alone.
-#include "common.h"
+#include "lowp.h"
 
 namespace psn {
-
-typedef __bf16 xbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 xbf16x2 __attribute__((ext_vector_type(2)));
-typedef float xfloatx2 __attribute__((ext_vector_type(2)));
-typedef int xintx4 __attribute__((ext_vector_type(4)));
 
 struct X3Args {
     PsnBf16Desc d;
@@ -95,9 +90,9 @@ __device__ __forceinline__ void x3_dma_piece(const unsigned char* __restrict__ g
 __device__ __forceinline__ float x3_bf16_to_f32_lo(int packed) { return __builtin_bit_cast(float, packed << 16); }
 __device__ __forceinline__ float x3_bf16_to_f32_hi(int packed) { return __builtin_bit_cast(float, packed & (int)0xFFFF0000); }
 __device__ __forceinline__ int x3_cvt2(float a, float b) {
-    xfloatx2 f;
+    floatx2 f;
     f[0] = a; f[1] = b;
-    return __builtin_bit_cast(int, __builtin_convertvector(f, xbf16x2));  // v_cvt_pk_bf16_f32, round to nearest even
+    return __builtin_bit_cast(int, __builtin_convertvector(f, bf16x2));  // v_cvt_pk_bf16_f32, round to nearest even
 }
 // two fp32 values -> their hi / mid / lo bf16 pairs (each piece exact in fp32: the residuals have <= 16 significant bits)
 __device__ __forceinline__ void x3_split2(float a, float b, int& hi, int& mid, int& lo) {
@@ -119,7 +114,7 @@ __device__ __forceinline__ void x3_split2(float a, float b, int& hi, int& mid, i
 // ~400 registers (456 with the whole epilogue between two layers), one wave per SIMD.
 template <bool OCC>
 __device__ __forceinline__ void x3_epi_job(const floatx16& a, const int j, const int ot, const int lh, const bool inject, const float* pe_row,
-                                           const int pe_first, xintx4 (&st)[3][2]) {
+                                           const int pe_first, intx4 (&st)[3][2]) {
     const int qp = j >> 2, i = j & 3;
     float c0, c1;
     if constexpr (OCC) {
@@ -151,7 +146,7 @@ struct X3EpiPhases {
     f32x2 z, nat, hi, r, u, w, lw, l, sp;
     int h_, m_;
     __device__ __forceinline__ void run(const int k, const floatx16& a, const int j, const int ot, const int lh, const bool inject,
-                                        const float* pe_row, const int pe_first, xintx4 (&st)[3][2]) {
+                                        const float* pe_row, const int pe_first, intx4 (&st)[3][2]) {
         const int qp = j >> 2, i = j & 3;
         if constexpr (OCC) {
             const float L2E = 1.44269502162933349609375f, LN2_HI = 0.693147182464599609375f, LN2_LO = -1.904654323148236e-9f;
@@ -215,11 +210,11 @@ struct X3EpiPhases {
 // in a layer's last stage, whose first k-step moves src -> dst).  HAS_JOB: group grp carries accumulator pair grp of tile
 // `job_ot` of the previous layer (job_acc) through its six phases, one behind each pair of MFMAs.
 template <bool OCC, bool MOVE, bool HAS_JOB, typename BOp, typename RequestPiece>
-__device__ __forceinline__ void x3_stage_mma_p(floatx16 (&dst)[8], floatx16 (&src)[8], const xbf16x8* __restrict__ wl, int lane, int n_pieces, BOp bop,
+__device__ __forceinline__ void x3_stage_mma_p(floatx16 (&dst)[8], floatx16 (&src)[8], const bf16x8* __restrict__ wl, int lane, int n_pieces, BOp bop,
                                                RequestPiece request_piece, const floatx16& job_acc, const int job_ot, const int lh, const bool inject,
-                                               const float* pe_row, const int pe_first, xintx4 (&job_st)[3][2]) {
-    xbf16x8 a[2][3][2];
-    auto load_frags = [&](int grp, xbf16x8 (&f)[3][2]) __attribute__((always_inline)) {
+                                               const float* pe_row, const int pe_first, intx4 (&job_st)[3][2]) {
+    bf16x8 a[2][3][2];
+    auto load_frags = [&](int grp, bf16x8 (&f)[3][2]) __attribute__((always_inline)) {
         const int ks = grp >> 2, p = grp & 3;
 #pragma unroll
         for (int o = 0; o < 2; ++o)
@@ -238,8 +233,8 @@ __device__ __forceinline__ void x3_stage_mma_p(floatx16 (&dst)[8], floatx16 (&sr
             // one wave per SIMD their latency is then exposed at the head of every group
             __builtin_amdgcn_sched_barrier(0);
         }
-        const xbf16x8 (&fr)[3][2] = a[grp & 1];
-        const xbf16x8 bh = bop(0, ks), bm = bop(1, ks), bl = bop(2, ks);
+        const bf16x8 (&fr)[3][2] = a[grp & 1];
+        const bf16x8 bh = bop(0, ks), bm = bop(1, ks), bl = bop(2, ks);
         floatx16& c0 = dst[2 * p];
         floatx16& c1 = dst[2 * p + 1];
         X3EpiPhases<OCC> ph;
@@ -348,14 +343,14 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
         // (read back by the same wave only -- layer 0 and the epilogue in front of the skip layer --, behind the barrier of
         //  the first stage)
     }
-    xbf16x8 ones_b;  // K slots 0..2 (lane half 0) carry the constant 1: the three bias pieces add up exactly
+    bf16x8 ones_b;  // K slots 0..2 (lane half 0) carry the constant 1: the three bias pieces add up exactly
     {
-        xintx4 o = {lh == 0 ? 0x3F803F80 : 0, lh == 0 ? 0x00003F80 : 0, 0, 0};
-        ones_b = __builtin_bit_cast(xbf16x8, o);
+        intx4 o = {lh == 0 ? 0x3F803F80 : 0, lh == 0 ? 0x00003F80 : 0, 0, 0};
+        ones_b = __builtin_bit_cast(bf16x8, o);
     }
 
     floatx16 cur[8], tmp[8];  // cur: the finished pre-activations of the previous layer (loop-carried); tmp: the layer being accumulated
-    xintx4 st[2][3][2];       // B-operand planes of two output tiles: [ring slot][plane][k-step of the tile]
+    intx4 st[2][3][2];       // B-operand planes of two output tiles: [ring slot][plane][k-step of the tile]
 
     // lane (n, h), tile ot, register v = 4 q + r  <->  feature 32 ot + 8 q + 4 h + r: four consecutive floats per (ot, q).
     // acc = U[n] + V[g] (fp32).  (Requesting the U row ahead of the preceding epilogue needs 128 more registers than the
@@ -378,7 +373,7 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
     auto init_bias = [&](floatx16 (&acc)[8]) __attribute__((always_inline)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        const xbf16x8* bl = reinterpret_cast<const xbf16x8*>(xsmem + (gstage & 1) * kX3BufBytes + kX3StageBytes);
+        const bf16x8* bl = reinterpret_cast<const bf16x8*>(xsmem + (gstage & 1) * kX3BufBytes + kX3StageBytes);
         floatx16 zero;
 #pragma unroll
         for (int i = 0; i < 16; ++i) zero[i] = 0.0f;
@@ -390,7 +385,7 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
     {                                                                                                        \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                     \
         __syncthreads();                                                                                     \
-        const xbf16x8* wl = reinterpret_cast<const xbf16x8*>(xsmem + (gstage & 1) * kX3BufBytes);            \
+        const bf16x8* wl = reinterpret_cast<const bf16x8*>(xsmem + (gstage & 1) * kX3BufBytes);            \
         unsigned char* nxt = xsmem + ((gstage + 1) & 1) * kX3BufBytes;                                       \
         const unsigned char* bsrc_ = (BSRC);                                                                 \
         x3_stage_mma_p<OCC, MOVE, HAS_JOB>(DST, SRC, wl, lane, (NEXT_HAS_BIAS) ? 14 : 12, BOP,               \
@@ -404,24 +399,24 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
     if constexpr (OCC) {
         // layer 0: bias + W_0 pe(x) on the matrix pipe, natural K order: k-step ks, slot j of lane (n, h) = column 16 ks + 8 h + j
         init_bias(cur);  // (its barrier also orders the encoding writes above against the reads below)
-        xbf16x8 bin[3][4];
+        bf16x8 bin[3][4];
 #pragma unroll
         for (int ks = 0; ks < 3; ++ks) {
             const float4 v0 = *reinterpret_cast<const float4*>(pe_row + 16 * ks + 8 * lh), v1 = *reinterpret_cast<const float4*>(pe_row + 16 * ks + 8 * lh + 4);
-            xintx4 oh, om, ol;
+            intx4 oh, om, ol;
             int h_, m_, l_;
             x3_split2(v0.x, v0.y, h_, m_, l_); oh[0] = h_; om[0] = m_; ol[0] = l_;
             x3_split2(v0.z, v0.w, h_, m_, l_); oh[1] = h_; om[1] = m_; ol[1] = l_;
             x3_split2(v1.x, v1.y, h_, m_, l_); oh[2] = h_; om[2] = m_; ol[2] = l_;
             x3_split2(v1.z, v1.w, h_, m_, l_); oh[3] = h_; om[3] = m_; ol[3] = l_;
-            bin[0][ks] = __builtin_bit_cast(xbf16x8, oh); bin[1][ks] = __builtin_bit_cast(xbf16x8, om); bin[2][ks] = __builtin_bit_cast(xbf16x8, ol);
+            bin[0][ks] = __builtin_bit_cast(bf16x8, oh); bin[1][ks] = __builtin_bit_cast(bf16x8, om); bin[2][ks] = __builtin_bit_cast(bf16x8, ol);
         }
         {
-            xintx4 z = {0, 0, 0, 0};
-            bin[0][3] = bin[1][3] = bin[2][3] = __builtin_bit_cast(xbf16x8, z);
+            intx4 z = {0, 0, 0, 0};
+            bin[0][3] = bin[1][3] = bin[2][3] = __builtin_bit_cast(bf16x8, z);
         }
-        X3P_STAGE(false, false, cur, cur, ([&](int pl, int ks) -> xbf16x8 { return bin[pl][ks]; }), false, g.bias, cur[0], 0, st[0])
-        X3P_STAGE(false, false, cur, cur, ([&](int pl, int ks) -> xbf16x8 { return bin[pl][2 + ks]; }), n_hidden > 1, g.bias + kX3BiasBytes, cur[0], 0, st[0])
+        X3P_STAGE(false, false, cur, cur, ([&](int pl, int ks) -> bf16x8 { return bin[pl][ks]; }), false, g.bias, cur[0], 0, st[0])
+        X3P_STAGE(false, false, cur, cur, ([&](int pl, int ks) -> bf16x8 { return bin[pl][2 + ks]; }), n_hidden > 1, g.bias + kX3BiasBytes, cur[0], 0, st[0])
     } else {
         // layer 0: U[n] + V[g] alone
         init_uv(cur, 0);
@@ -440,30 +435,30 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
         const unsigned char* next_bsrc = g.bias + (size_t)(li + 1 < n_hidden ? li + 1 : 0) * kX3BiasBytes;
         // stage S: MFMAs on tile S's planes (ring slot S & 1), the epilogue of tile S + 1 (into the other slot) in their gaps
 #define X3P_ACT(S)                                                                                                           \
-        X3P_STAGE(false, true, tmp, tmp, ([&](int pl, int ks) -> xbf16x8 { return __builtin_bit_cast(xbf16x8, st[(S) & 1][pl][ks]); }),   \
+        X3P_STAGE(false, true, tmp, tmp, ([&](int pl, int ks) -> bf16x8 { return __builtin_bit_cast(bf16x8, st[(S) & 1][pl][ks]); }),   \
                   false, next_bsrc, cur[(S) + 1], (S) + 1, st[((S) + 1) & 1])
         X3P_ACT(0) X3P_ACT(1) X3P_ACT(2) X3P_ACT(3) X3P_ACT(4) X3P_ACT(5) X3P_ACT(6)
 #undef X3P_ACT
         // last stage: every tile of the previous layer has been consumed -- the results move back into `cur`
-        X3P_STAGE(true, false, cur, tmp, ([&](int pl, int ks) -> xbf16x8 { return __builtin_bit_cast(xbf16x8, st[1][pl][ks]); }),
+        X3P_STAGE(true, false, cur, tmp, ([&](int pl, int ks) -> bf16x8 { return __builtin_bit_cast(bf16x8, st[1][pl][ks]); }),
                   next_bias, next_bsrc, cur[0], 0, st[0])
     }
 #undef X3P_STAGE
     // final layer: the whole epilogue of the last hidden layer (tmp is dead: its registers hold the 16 k-steps of planes),
     // then one output tile (n_out <= 32), 16 k-steps x 3 planes in ONE 48 KB stage; four accumulator chains
-    xbf16x8 bact[3][16];
+    bf16x8 bact[3][16];
 #pragma unroll
     for (int ot = 0; ot < 8; ++ot) {
-        xintx4 s8[3][2];
+        intx4 s8[3][2];
 #pragma unroll
         for (int j = 0; j < 8; ++j) x3_epi_job<OCC>(cur[ot], j, ot, lh, false, pe_row, g.pe_first, s8);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) { bact[pl][2 * ot] = __builtin_bit_cast(xbf16x8, s8[pl][0]); bact[pl][2 * ot + 1] = __builtin_bit_cast(xbf16x8, s8[pl][1]); }
+        for (int pl = 0; pl < 3; ++pl) { bact[pl][2 * ot] = __builtin_bit_cast(bf16x8, s8[pl][0]); bact[pl][2 * ot + 1] = __builtin_bit_cast(bf16x8, s8[pl][1]); }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     {
-        const xbf16x8* wl = reinterpret_cast<const xbf16x8*>(xsmem + (gstage & 1) * kX3BufBytes);
+        const bf16x8* wl = reinterpret_cast<const bf16x8*>(xsmem + (gstage & 1) * kX3BufBytes);
         floatx16 f[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -471,7 +466,7 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
             for (int i = 0; i < 16; ++i) f[c][i] = 0.0f;
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) {
-            const xbf16x8 ah = wl[(ks * 3 + 0) * 64 + lane], am = wl[(ks * 3 + 1) * 64 + lane], al = wl[(ks * 3 + 2) * 64 + lane];
+            const bf16x8 ah = wl[(ks * 3 + 0) * 64 + lane], am = wl[(ks * 3 + 1) * 64 + lane], al = wl[(ks * 3 + 2) * 64 + lane];
             floatx16& c = f[ks & 3];
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bact[0][ks], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bact[2][ks], c, 0, 0, 0);
@@ -514,123 +509,54 @@ __global__ __launch_bounds__(256, 1) void mlp_infer_x3p_kernel(X3Args g) {
     }
 }
 
-// ---- packers --------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void x3_split1(float v, uint16_t (&p)[3]) {
-    float r = v;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const __bf16 b = (__bf16)r;
-        p[i] = __builtin_bit_cast(uint16_t, b);
-        r -= (float)b;
-    }
-}
-// W[rows, cols] (row-major, ldw floats per row), zero-extended, k-steps [ks0, ks0 + n_ks) -> [ks][ot][plane][lane][8] bf16;
-// K order as psn_mlp_pack_bf16 (natural: k = 16 ks + 8 h + j; permuted: k = 32 (ks / 2) + 16 (ks % 2) + 8 (j / 4) + 4 h + (j % 4))
-__global__ __launch_bounds__(256) void x3_pack_kernel(const float* __restrict__ W, int64_t ldw, int rows, int cols, int permuted, int n_ot,
-                                                      int ks0, int n_ks, uint16_t* __restrict__ dst) {
-    const int64_t total = (int64_t)n_ks * n_ot * 512;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int j = (int)(e & 7);
-        const int lane = (int)((e >> 3) & 63);
-        const int64_t blk = e >> 9;
-        const int ot = (int)(blk % n_ot);
-        const int ksl = (int)(blk / n_ot);
-        const int ks = ks0 + ksl;
-        const int m = lane & 31, h = lane >> 5;
-        const int r = 32 * ot + m;
-        const int k = permuted ? 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3) : 16 * ks + 8 * h + j;
-        float v = 0.0f;
-        if (r < rows && k < cols) v = W[(int64_t)r * ldw + k];
-        uint16_t p[3];
-        x3_split1(v, p);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) dst[(((int64_t)ksl * n_ot + ot) * 3 + pl) * 512 + lane * 8 + j] = p[pl];
-    }
-}
-// V [n, 256] fp32 -> bias k-steps [n][8 tiles][64 lanes][8] bf16: K slots 0, 1, 2 (lane half 0) = hi, mid, lo of the value
-__global__ __launch_bounds__(256) void x3_pack_bias_kernel(const float* __restrict__ V, int64_t n, uint16_t* __restrict__ dst) {
-    const int64_t total = n * 4096;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int j = (int)(e & 7);
-        const int lane = (int)((e >> 3) & 63);
-        const int ot = (int)((e >> 9) & 7);
-        const int64_t r = e >> 12;
-        const int k = 8 * (lane >> 5) + j;
-        uint16_t o = 0;
-        if (k < 3) {
-            uint16_t p[3];
-            x3_split1(V[r * 256 + 32 * ot + (lane & 31)], p);
-            o = p[k];
-        }
-        dst[e] = o;
-    }
-}
 }  // namespace psn
 
-// Launch of mlp_infer_x3p_kernel<OCC>: 112 KB of dynamic LDS (+ 24 KB of encoding for OCC) need the opt-in attribute, set per
-// call as in bf16_launch (mlp_infer_bf16.hip)
+// What the three entries check and fill alike: the descriptor, the 16-byte alignment of the LDS-DMA sources (and of `tables`: a
+// form's float4-read tables, addresses ORed) and the operands every launch has
+static int x3_base_args(psn::X3Args& a, const char* what, const PsnBf16Desc& d, bool layer0_in, const uint16_t* packed_w, const uint16_t* bias_steps,
+                        const float* final_bias, uintptr_t tables, float* out) {
+    using namespace psn;
+    if (int rc = lowp_check_desc(d, what, 2, layer0_in)) return rc;
+    PSN_CHECK_ARG((((uintptr_t)packed_w | (uintptr_t)bias_steps | tables) & 15) == 0, "%s: buffers must be 16-byte aligned", what);
+    a.d = d;
+    a.w = reinterpret_cast<const unsigned char*>(packed_w);
+    a.bias = reinterpret_cast<const unsigned char*>(bias_steps);
+    a.final_bias = final_bias;
+    a.out = out;
+    return PSN_OK;
+}
+
+// The in-kernel encoding and the skip layer of the occupancy network (occupancy form and sweep)
+static int x3_pe_args(psn::X3Args& a, const char* what, int pe_octaves, float pe_scale, int skip_layer, int pe_first) {
+    using namespace psn;
+    PSN_CHECK_ARG(pe_octaves >= 0 && 3 + 6 * pe_octaves <= kX3PeStride, "%s: %d octaves do not fit %d encoding columns", what, pe_octaves, kX3PeStride);
+    PSN_CHECK_ARG(skip_layer < a.d.n_hidden && (skip_layer < 1 || (pe_first >= 192 && pe_first + 3 + 6 * pe_octaves <= 256)),
+                  "%s: skip_layer=%d pe_first=%d (the encoding columns must be input features 192..255 of a layer >= 1)", what, skip_layer, pe_first);
+    a.pe_octaves = pe_octaves; a.pe_scale = pe_scale; a.skip_layer = skip_layer < 1 ? -1 : skip_layer; a.pe_first = pe_first;
+    return PSN_OK;
+}
+
+// 112 KB of dynamic LDS, + 24 KB of encoding for OCC
 template <bool OCC>
 static int x3_launch(const psn::X3Args& a, int64_t blocks, void* stream, const char* what) {
     using namespace psn;
-    const size_t lds_bytes = 2 * kX3BufBytes + (OCC ? kX3PeBytes : 0);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_infer_x3p_kernel<OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        set_error("%s: cannot reserve %zu bytes of LDS: %s", what, lds_bytes, hipGetErrorString(e));
-        return PSN_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(mlp_infer_x3p_kernel<OCC>, dim3((unsigned)blocks), dim3(kX3Waves * 64), lds_bytes, (hipStream_t)stream, a);
-    PSN_CHECK_LAUNCH(what);
-    return PSN_OK;
-}
-
-extern "C" int psn_x3_pack(const float* W, int64_t ldw, int rows, int cols, int permuted, int n_ot, int ks0, int n_ks, uint16_t* dst,
-                           void* stream) {
-    using namespace psn;
-    PSN_CHECK_ARG(W && dst, "x3_pack: null pointer");
-    PSN_CHECK_ARG((n_ot == 8 || n_ot == 1) && ks0 >= 0 && n_ks >= 1 && ks0 + n_ks <= 16, "x3_pack: n_ot=%d ks0=%d n_ks=%d", n_ot, ks0, n_ks);
-    PSN_CHECK_ARG(rows >= 1 && rows <= 32 * n_ot && cols >= 1 && cols <= 256 && ldw >= cols, "x3_pack: %d x %d (ldw %lld) does not fit", rows, cols, (long long)ldw);
-    const int64_t total = (int64_t)n_ks * n_ot * 512;
-    hipLaunchKernelGGL(x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, ldw, rows, cols, permuted, n_ot, ks0, n_ks, dst);
-    PSN_CHECK_LAUNCH("x3_pack");
-    return PSN_OK;
-}
-
-extern "C" int psn_x3_pack_bias(const float* V, int64_t n, uint16_t* dst, void* stream) {
-    using namespace psn;
-    PSN_CHECK_ARG(V && dst && n >= 1 && n < (1ll << 30), "x3_pack_bias: V / dst / n=%lld", (long long)n);
-    const int64_t total = n * 4096;
-    const int blocks = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-    hipLaunchKernelGGL(x3_pack_bias_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, V, n, dst);
-    PSN_CHECK_LAUNCH("x3_pack_bias");
-    return PSN_OK;
+    return lowp_launch(&mlp_infer_x3p_kernel<OCC>, a, blocks, kX3Waves * 64, 2 * kX3BufBytes + (OCC ? kX3PeBytes : 0), stream, what);
 }
 
 extern "C" int psn_mlp_infer_x3_grouped(const PsnBf16Desc* desc, const uint16_t* packed_w, const uint16_t* bias_steps, const float* final_bias,
                                         const float* U, int64_t rows_per_group, const float* V, int64_t n_groups, float* out, void* stream) {
     using namespace psn;
     PSN_CHECK_ARG(desc && packed_w && bias_steps && final_bias && U && V && out, "mlp_infer_x3_grouped: null pointer");
-    const PsnBf16Desc& d = *desc;
-    PSN_CHECK_ARG(d.n_hidden >= 2 && d.n_hidden <= PSN_MLP_MAX_LAYERS && d.n_out >= 1 && d.n_out <= 32, "mlp_infer_x3_grouped: n_hidden=%d n_out=%d", d.n_hidden, d.n_out);
-    PSN_CHECK_ARG(d.out_act >= PSN_OUT_NONE && d.out_act <= PSN_OUT_OCC && d.has_in[0] != 0, "mlp_infer_x3_grouped: out_act=%d, layer 0 must read the input block", d.out_act);
-    PSN_CHECK_ARG((((uintptr_t)packed_w | (uintptr_t)bias_steps | (uintptr_t)U | (uintptr_t)V) & 15) == 0, "mlp_infer_x3_grouped: buffers must be 16-byte aligned");
+    X3Args a = {};
+    if (int rc = x3_base_args(a, "mlp_infer_x3_grouped", *desc, true, packed_w, bias_steps, final_bias, (uintptr_t)U | (uintptr_t)V, out)) return rc;
     PSN_CHECK_ARG(rows_per_group >= 0 && n_groups >= 0 && rows_per_group <= (1ll << 24) && rows_per_group * n_groups < (1ll << 31),
                   "mlp_infer_x3_grouped: 32-bit index arithmetic: rows per group <= 2^24, rows < 2^31");
     if (rows_per_group == 0 || n_groups == 0) return PSN_OK;
-    X3Args a = {};
-    a.d = d;
-    a.w = reinterpret_cast<const unsigned char*>(packed_w);
-    a.bias = reinterpret_cast<const unsigned char*>(bias_steps);
-    a.final_bias = final_bias;
     a.U = U; a.V = V;
     a.rows_per_group = (unsigned)rows_per_group;
     a.tiles_per_group = (unsigned)((rows_per_group + kX3Waves * 32 - 1) / (kX3Waves * 32));
-    int n_in = 0;
-    for (int l = 0; l < d.n_hidden; ++l) n_in += d.has_in[l] != 0;
-    a.n_in_layers = (unsigned)n_in;
-    a.out = out;
-    const int64_t blocks = (int64_t)a.tiles_per_group * n_groups;
-    PSN_CHECK_ARG(blocks < (1ll << 31), "mlp_infer_x3_grouped: too many rows");
-    return x3_launch<false>(a, blocks, stream, "mlp_infer_x3_grouped");
+    a.n_in_layers = lowp_n_in(*desc);
+    return x3_launch<false>(a, (int64_t)a.tiles_per_group * n_groups, stream, "mlp_infer_x3_grouped");
 }
 
 // Stage-1 occupancy network on the split-bf16 engine: sigmoid(-10 logit) of n_rows query points, see mlp_infer_x3p_kernel<true>.
@@ -639,23 +565,12 @@ extern "C" int psn_mlp_infer_x3_occ(const PsnBf16Desc* desc, const uint16_t* pac
                                     int pe_octaves, float pe_scale, int skip_layer, int pe_first, float* out, void* stream) {
     using namespace psn;
     PSN_CHECK_ARG(desc && packed_w && bias_steps && final_bias && points && out, "mlp_infer_x3_occ: null pointer");
-    const PsnBf16Desc& d = *desc;
-    PSN_CHECK_ARG(d.n_hidden >= 2 && d.n_hidden <= PSN_MLP_MAX_LAYERS && d.n_out >= 1 && d.n_out <= 32, "mlp_infer_x3_occ: n_hidden=%d n_out=%d", d.n_hidden, d.n_out);
-    PSN_CHECK_ARG(d.out_act >= PSN_OUT_NONE && d.out_act <= PSN_OUT_OCC, "mlp_infer_x3_occ: out_act=%d", d.out_act);
-    PSN_CHECK_ARG(pe_octaves >= 0 && 3 + 6 * pe_octaves <= kX3PeStride, "mlp_infer_x3_occ: %d octaves do not fit %d encoding columns", pe_octaves, kX3PeStride);
-    PSN_CHECK_ARG(skip_layer < d.n_hidden && (skip_layer < 1 || (pe_first >= 192 && pe_first + 3 + 6 * pe_octaves <= 256)),
-                  "mlp_infer_x3_occ: skip_layer=%d pe_first=%d (the encoding columns must be input features 192..255 of a layer >= 1)", skip_layer, pe_first);
-    PSN_CHECK_ARG((((uintptr_t)packed_w | (uintptr_t)bias_steps) & 15) == 0, "mlp_infer_x3_occ: buffers must be 16-byte aligned");
+    X3Args a = {};
+    if (int rc = x3_base_args(a, "mlp_infer_x3_occ", *desc, false, packed_w, bias_steps, final_bias, 0, out)) return rc;
+    if (int rc = x3_pe_args(a, "mlp_infer_x3_occ", pe_octaves, pe_scale, skip_layer, pe_first)) return rc;
     PSN_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 31), "mlp_infer_x3_occ: 32-bit row arithmetic: rows < 2^31");
     if (n_rows == 0) return PSN_OK;
-    X3Args a = {};
-    a.d = d;
-    a.w = reinterpret_cast<const unsigned char*>(packed_w);
-    a.bias = reinterpret_cast<const unsigned char*>(bias_steps);
-    a.final_bias = final_bias;
     a.points = points; a.n_rows = n_rows; a.n_rows_dev = n_rows_dev; a.out_rows = out_rows;
-    a.pe_octaves = pe_octaves; a.pe_scale = pe_scale; a.skip_layer = skip_layer < 1 ? -1 : skip_layer; a.pe_first = pe_first;
-    a.out = out;
     return x3_launch<true>(a, (n_rows + kX3Waves * 32 - 1) / (kX3Waves * 32), stream, "mlp_infer_x3_occ");
 }
 
@@ -670,21 +585,14 @@ extern "C" int psn_march_sweep_x3(const PsnBf16Desc* desc, const uint16_t* packe
                                   int* skip, float* occ, unsigned long long* n_blocks, void* stream) {
     using namespace psn;
     PSN_CHECK_ARG(desc && packed_w && bias_steps && final_bias && origin && dir && far && u && omu && occ, "march_sweep_x3: null pointer");
-    const PsnBf16Desc& d = *desc;
-    PSN_CHECK_ARG(d.n_hidden >= 2 && d.n_hidden <= PSN_MLP_MAX_LAYERS && d.n_out == 1 && d.out_act == PSN_OUT_OCC, "march_sweep_x3: the occupancy network (one output, OCC)");
-    PSN_CHECK_ARG(pe_octaves >= 0 && 3 + 6 * pe_octaves <= kX3PeStride, "march_sweep_x3: %d octaves do not fit %d encoding columns", pe_octaves, kX3PeStride);
-    PSN_CHECK_ARG(skip_layer < d.n_hidden && (skip_layer < 1 || (pe_first >= 192 && pe_first + 3 + 6 * pe_octaves <= 256)), "march_sweep_x3: skip_layer=%d pe_first=%d", skip_layer, pe_first);
+    X3Args a = {};
+    if (int rc = x3_base_args(a, "march_sweep_x3", *desc, false, packed_w, bias_steps, final_bias, 0, occ)) return rc;
+    PSN_CHECK_ARG(desc->n_out == 1 && desc->out_act == PSN_OUT_OCC, "march_sweep_x3: the occupancy network (one output, OCC)");
+    if (int rc = x3_pe_args(a, "march_sweep_x3", pe_octaves, pe_scale, skip_layer, pe_first)) return rc;
     PSN_CHECK_ARG(n_steps >= 128 && n_steps % (kX3Waves * 32) == 0 && n_rays >= 0 && n_rays * (int64_t)n_steps < (1ll << 31),
                   "march_sweep_x3: n_steps=%d must be a multiple of 128, rays x steps < 2^31", n_steps);
     if (n_rays == 0) return PSN_OK;
-    X3Args a = {};
-    a.d = d;
-    a.w = reinterpret_cast<const unsigned char*>(packed_w);
-    a.bias = reinterpret_cast<const unsigned char*>(bias_steps);
-    a.final_bias = final_bias;
     a.n_rows = n_rays * (int64_t)n_steps;
-    a.pe_octaves = pe_octaves; a.pe_scale = pe_scale; a.skip_layer = skip_layer < 1 ? -1 : skip_layer; a.pe_first = pe_first;
-    a.out = occ;
     a.ray_o = origin; a.ray_d = dir; a.far = far; a.u = u; a.omu = omu; a.near = near; a.tau = tau; a.n_steps = n_steps;
     a.skip = skip; a.n_blocks = n_blocks;
     return x3_launch<true>(a, n_rays * (n_steps / (kX3Waves * 32)), stream, "march_sweep_x3");

@@ -313,6 +313,78 @@ def pack_relu_mlp(weights, biases, din_a, din_b, skip_at, out_act=hip.OUT_NONE, 
     return pack_layers(layers, ka, kb, weights[-1].shape[0], out_act, weights[0].device, width=width, reuse=reuse, x3=x3)
 
 
+# --------------------------------------------------------------------------- reduced-precision engines (bf16, split bf16)
+# A packer first PLANS its weight stream as a list of pieces in execution order -- (W, permuted, n_ot, ks0, n_ks) = k-steps of a
+# matrix view as hip.lowp_pack takes them, or an int n = n zero k-steps of a hidden layer --, then _lowp_stream sizes, allocates and
+# fills the buffer from that list: no size is stated apart from the writes that fill it.
+def _lowp_net(weights, biases, out_act, skip_at=None, n_out=None):
+    """What every packer starts from -> (desc, float32 weights, float32 biases, the final layer's piece, final bias padded to 32).
+    The input block is read by layer 0 and by the layer after ``skip_at``; n_out: the leading output rows that are evaluated."""
+    n = len(weights)
+    Ws, bs = [w.detach().float().contiguous() for w in weights], [b.detach().float() for b in biases]
+    n_out = Ws[-1].shape[0] if n_out is None else n_out
+    desc = hip.PsnBf16Desc()
+    desc.n_hidden, desc.n_out, desc.out_act = n - 1, n_out, out_act
+    for li in range(n - 1):
+        desc.has_in[li] = int(li == 0 or li - 1 == skip_at)
+    fb = torch.zeros(32, device=Ws[0].device)
+    fb[:n_out] = bs[-1][:n_out]
+    return desc, Ws, bs, (Ws[-1][:n_out], True, 1, 0, 16), fb
+
+
+def _lowp_stream(pieces, planes, device):
+    """The pieces in order as one bfloat16 buffer, + the 56 KB that the last stage request of either engine over-reads."""
+    sizes = [(8 * p if isinstance(p, int) else p[2] * p[4]) * planes * 512 for p in pieces]
+    buf = torch.zeros(sum(sizes) + 56 * 512, device=device, dtype=torch.bfloat16)
+    off = 0
+    for p, size in zip(pieces, sizes):
+        if not isinstance(p, int):
+            hip.lowp_pack(*p, buf[off:off + size], planes=planes)
+        off += size
+    return buf
+
+
+def _bias_cols(b):
+    """[256] -> the [256, 2] matrix (bf16(b), b - bf16(b)) of a bias k-step of the bf16 engine."""
+    hi = b.to(torch.bfloat16).float()
+    return torch.stack([hi, b - hi], dim=1).contiguous()
+
+
+def _in_columns(W, li, din_a, din_b):
+    """The table-A and table-B columns of an input layer's weight (layer 0: the whole matrix; later: behind the 256 activations)."""
+    c0 = 0 if li == 0 else 256
+    return W[:, c0:c0 + din_a], W[:, c0 + din_a:c0 + din_a + din_b]
+
+
+def _group_tables(desc, Ws, bs, din_a, din_b):
+    """Grouped forms: the input layers' table-A and table-B columns, zero-padded to 64, and their biases, stacked in network
+    order -> ([n_in * 256, 64], [n_in * 256, 64], [n_in * 256]) fp32."""
+    layers = [li for li in range(desc.n_hidden) if desc.has_in[li]]
+    init_wa = torch.zeros(len(layers) * 256, 64, device=Ws[0].device)
+    init_wb = torch.zeros_like(init_wa)
+    for i, li in enumerate(layers):
+        init_wa[i * 256:(i + 1) * 256, :din_a], init_wb[i * 256:(i + 1) * 256, :din_b] = _in_columns(Ws[li], li, din_a, din_b)
+    return init_wa, init_wb, torch.cat([bs[li] for li in layers]).contiguous()
+
+
+def _pack_bf16_stream(desc, Ws, bs, final, din_a, din_b, grouped):
+    """Weight stream of the bf16 engine (include/psnerf_hip.h, psn_mlp_infer_bf16 / _grouped).  Input block of an input layer:
+    4 k-steps of table A and -- two-table form -- 4 of table B; the grouped form has no bias k-step for such a layer."""
+    pieces = []
+    for li in range(desc.n_hidden):
+        block, bias = [], [(_bias_cols(bs[li]), False, 8, 0, 1)]
+        if desc.has_in[li]:
+            W_a, W_b = _in_columns(Ws[li], li, din_a, din_b)
+            block = [(W_a, False, 8, 0, 4)] + ([] if grouped else [(W_b, False, 8, 0, 4) if din_b > 0 else 4])
+            bias = [] if grouped else bias
+        if li == 0:
+            pieces += block + bias
+        else:
+            W_act = Ws[li][:, :256]
+            pieces += [(W_act, True, 8, 0, 8)] + bias + block + [(W_act, True, 8, 8, 8)]
+    return _lowp_stream(pieces + [final], 1, Ws[0].device)
+
+
 class PackedBf16(object):
     """A 256-wide ReLU network packed for the bf16 inference engine (csrc/mlp_infer_bf16.hip)."""
 
@@ -330,54 +402,10 @@ def pack_relu_mlp_bf16(weights, biases, din_a, din_b, skip_at, out_act=hip.OUT_N
     """stage2 Network (stage2/model/renderer.py:34-49) of width 256 for the bf16 engine: the input row is
     [table A (din_a <= 64 real columns) | table B (din_b <= 64)], concatenated again AFTER layer ``skip_at``.
     Weight stream layout: include/psnerf_hip.h (psn_mlp_infer_bf16)."""
-    n = len(weights)
-    dev = weights[0].device
-    assert n - 1 <= hip.MAX_LAYERS and din_a <= 64 and din_b <= 64
+    assert len(weights) - 1 <= hip.MAX_LAYERS and din_a <= 64 and din_b <= 64
     assert all(w.shape[0] == 256 for w in weights[:-1]) and weights[-1].shape[0] <= 32
-    desc = hip.PsnBf16Desc()
-    desc.n_hidden, desc.n_out, desc.out_act = n - 1, weights[-1].shape[0], out_act
-    KS = 8 * 512  # bf16 elements per k-step of a hidden layer
-    sizes = []
-    for li in range(n - 1):
-        has_in = li == 0 or li - 1 == skip_at
-        desc.has_in[li] = int(has_in)
-        sizes.append(9 * KS if li == 0 else (17 + (8 if has_in else 0)) * KS)
-    # the kernel always requests a full 72 KB stage: the final layer's 16 KB block is followed by 56 KB of padding
-    buf = torch.zeros(sum(sizes) + 72 * 512, device=dev, dtype=torch.bfloat16)
-
-    def bias_cols(b):
-        b = b.detach().float()
-        hi = b.to(torch.bfloat16).float()
-        return torch.stack([hi, b - hi], dim=1).contiguous()
-
-    def pack_in(W_in, dst):  # [256, din_a + din_b] -> 4 k-steps of table A, 4 of table B
-        hip.mlp_pack_bf16(W_in[:, :din_a], False, 8, 0, 4, dst[:4 * KS])
-        if din_b > 0:
-            hip.mlp_pack_bf16(W_in[:, din_a:din_a + din_b], False, 8, 0, 4, dst[4 * KS:8 * KS])
-        else:
-            dst[4 * KS:8 * KS].zero_()
-
-    off = 0
-    for li in range(n - 1):
-        W = weights[li].detach().float()
-        dst = buf[off:off + sizes[li]]
-        if li == 0:
-            pack_in(W, dst)
-            hip.mlp_pack_bf16(bias_cols(biases[li]), False, 8, 0, 1, dst[8 * KS:9 * KS])
-        else:
-            W_act = W[:, :256]
-            hip.mlp_pack_bf16(W_act, True, 8, 0, 8, dst[:8 * KS])
-            hip.mlp_pack_bf16(bias_cols(biases[li]), False, 8, 0, 1, dst[8 * KS:9 * KS])
-            hi = 9 * KS
-            if desc.has_in[li]:
-                pack_in(W[:, 256:], dst[9 * KS:17 * KS])
-                hi = 17 * KS
-            hip.mlp_pack_bf16(W_act, True, 8, 8, 8, dst[hi:hi + 8 * KS])
-        off += sizes[li]
-    hip.mlp_pack_bf16(weights[-1].detach().float(), True, 1, 0, 16, buf[off:off + 16 * 512])
-    fb = torch.zeros(32, device=dev)
-    fb[:weights[-1].shape[0]] = biases[-1].detach().float()
-    return PackedBf16(desc, buf, fb)
+    desc, Ws, bs, final, fb = _lowp_net(weights, biases, out_act, skip_at)
+    return PackedBf16(desc, _pack_bf16_stream(desc, Ws, bs, final, din_a, din_b, False), fb)
 
 
 class PackedBf16Grouped(object):
@@ -394,7 +422,7 @@ class PackedBf16Grouped(object):
     def group_bias(self, tab_b):
         """tab_b [n_groups, 64] fp32 group features -> bias k-steps [n_groups * n_in, 4096] bfloat16."""
         V = hip.gemm(tab_b, self.wb_t, bias=self.b_in, epi=hip.EPI_BIAS)  # [n_groups, n_in * 256]
-        return hip.bf16_pack_group_bias(V.view(-1, 256))
+        return hip.lowp_pack_bias(V.view(-1, 256), 2)
 
     def __call__(self, tab_a, tab_b, out=None):
         """tab_a [Ns, 64] bfloat16, tab_b [n_groups, 64] float32 -> [n_groups * Ns, n_out] (group-major rows)."""
@@ -404,53 +432,11 @@ class PackedBf16Grouped(object):
 def pack_relu_mlp_bf16_grouped(weights, biases, din_a, din_b, skip_at, out_act=hip.OUT_NONE):
     """As pack_relu_mlp_bf16 for the grouped form: the weight stream holds the table-A columns of the input layers only
     (4 k-steps) and no bias k-step for them (include/psnerf_hip.h, psn_mlp_infer_bf16_grouped)."""
-    n = len(weights)
-    dev = weights[0].device
-    assert n - 1 <= hip.MAX_LAYERS and din_a <= 64 and 0 < din_b <= 64
+    assert len(weights) - 1 <= hip.MAX_LAYERS and din_a <= 64 and 0 < din_b <= 64
     assert all(w.shape[0] == 256 for w in weights[:-1]) and weights[-1].shape[0] <= 32
-    desc = hip.PsnBf16Desc()
-    desc.n_hidden, desc.n_out, desc.out_act = n - 1, weights[-1].shape[0], out_act
-    KS = 8 * 512
-    sizes = []
-    for li in range(n - 1):
-        has_in = li == 0 or li - 1 == skip_at
-        desc.has_in[li] = int(has_in)
-        sizes.append(4 * KS if li == 0 else (16 + (4 if has_in else 1)) * KS)
-    buf = torch.zeros(sum(sizes) + 72 * 512, device=dev, dtype=torch.bfloat16)
-
-    def bias_cols(b):
-        b = b.detach().float()
-        hi = b.to(torch.bfloat16).float()
-        return torch.stack([hi, b - hi], dim=1).contiguous()
-
-    wb, b_in = [], []
-    off = 0
-    for li in range(n - 1):
-        W = weights[li].detach().float()
-        dst = buf[off:off + sizes[li]]
-        if li == 0:
-            hip.mlp_pack_bf16(W[:, :din_a], False, 8, 0, 4, dst[:4 * KS])
-            wb.append(W[:, din_a:din_a + din_b]); b_in.append(biases[li].detach().float())
-        else:
-            W_act = W[:, :256]
-            hip.mlp_pack_bf16(W_act, True, 8, 0, 8, dst[:8 * KS])
-            hi = 8 * KS
-            if desc.has_in[li]:
-                hip.mlp_pack_bf16(W[:, 256:256 + din_a], False, 8, 0, 4, dst[hi:hi + 4 * KS])
-                wb.append(W[:, 256 + din_a:256 + din_a + din_b]); b_in.append(biases[li].detach().float())
-                hi += 4 * KS
-            else:
-                hip.mlp_pack_bf16(bias_cols(biases[li]), False, 8, 0, 1, dst[hi:hi + KS])
-                hi += KS
-            hip.mlp_pack_bf16(W_act, True, 8, 8, 8, dst[hi:hi + 8 * KS])
-        off += sizes[li]
-    hip.mlp_pack_bf16(weights[-1].detach().float(), True, 1, 0, 16, buf[off:off + 16 * 512])
-    fb = torch.zeros(32, device=dev)
-    fb[:weights[-1].shape[0]] = biases[-1].detach().float()
-    wb_t = torch.zeros(64, len(wb) * 256, device=dev)
-    for i, w in enumerate(wb):
-        wb_t[:din_b, i * 256:(i + 1) * 256] = w.t()
-    return PackedBf16Grouped(desc, buf, fb, wb_t.contiguous(), torch.cat(b_in).contiguous())
+    desc, Ws, bs, final, fb = _lowp_net(weights, biases, out_act, skip_at)
+    _, init_wb, b_in = _group_tables(desc, Ws, bs, din_a, din_b)
+    return PackedBf16Grouped(desc, _pack_bf16_stream(desc, Ws, bs, final, din_a, din_b, True), fb, init_wb.t().contiguous(), b_in)
 
 
 def pack_geo_occupancy(weights, biases, skips, d_pe, x3=False, out_act=hip.OUT_OCC, negate=False):
@@ -632,6 +618,18 @@ class PackedX3Occ(object):
                                     macs_per_row=self.macs_per_row)
 
 
+def _pack_x3(desc, Ws, bs, final, first, bias_layers):
+    """Weight stream and bias k-steps of the split-bf16 engine -> (w, bias_steps [n_hidden, 4096], MACs per row of the network):
+    ``first`` (layer 0's pieces), every further hidden layer as 16 permuted k-steps, the final layer as one stage; the hidden
+    layers in ``bias_layers`` get their bias k-step (rows zero-extended to 256), the others a zero one."""
+    B = torch.zeros(desc.n_hidden, 256, device=Ws[0].device)
+    for li in bias_layers:
+        B[li, :bs[li].numel()] = bs[li]
+    w = _lowp_stream(first + [(W[:, :256], True, 8, 0, 16) for W in Ws[1:-1]] + [final], 3, Ws[0].device)
+    macs = sum(W.shape[0] * W.shape[1] for W in Ws[:-1]) + desc.n_out * Ws[-1].shape[1]
+    return w, hip.lowp_pack_bias(B, 3), macs
+
+
 def pack_geo_occupancy_x3(weights, biases, skips, d_pe):
     """stage1 occupancy-only network (stage1/model/network.py:85-95,124-125; same arguments as pack_geo_occupancy) for the
     split-bf16 engine.  Weight stream in execution order: layer 0 = 4 natural-order k-steps of the encoding columns (two 48 KB
@@ -639,77 +637,25 @@ def pack_geo_occupancy_x3(weights, biases, skips, d_pe):
     has a bias k-step.  The skip layer (input cat[h, pe] / sqrt(2)) is an ordinary 256-input layer: its encoding columns are
     input features pe_first .. pe_first + d_pe - 1, which the kernel fills in (1 / sqrt(2) folded into the weights here)."""
     n = len(weights)
-    dev = weights[0].device
     assert len(skips) <= 1 and d_pe <= 48 and 3 <= n <= hip.MAX_LAYERS + 1
     assert all(w.shape[0] <= 256 for w in weights[:-1]) and weights[0].shape[1] == d_pe
-    desc = hip.PsnBf16Desc()
-    desc.n_hidden, desc.n_out, desc.out_act = n - 1, 1, hip.OUT_OCC
-    KS = hip.X3_KS
-    final_elems = 16 * 3 * 512
-    buf = torch.zeros(4 * KS + (n - 2) * 16 * KS + final_elems + 56 * 512, device=dev, dtype=torch.bfloat16)  # (+ 56 KB: the last request over-reads)
-    bias_steps = torch.zeros(n - 1, 4096, device=dev, dtype=torch.bfloat16)
-    inv = 1.0 / math.sqrt(2.0)
-    off, macs, skip_layer, pe_first = 0, 0, -1, 0
-    for li in range(n - 1):
-        W, b = weights[li].detach().float(), biases[li].detach().float()
-        macs += W.shape[0] * W.shape[1]
-        desc.has_in[li] = int(li == 0)
-        if li == 0:
-            hip.x3_pack(W.contiguous(), False, 8, 0, 4, buf[off:off + 4 * KS])
-            off += 4 * KS
-        else:
-            if li in skips:
-                assert W.shape[1] == 256, 'the skip layer reads cat[h, pe]: 256 input features'
-                W = W * inv
-                skip_layer, pe_first = li, W.shape[1] - d_pe
-            hip.x3_pack(W.contiguous(), True, 8, 0, 16, buf[off:off + 16 * KS])
-            off += 16 * KS
-        bp = torch.zeros(1, 256, device=dev)
-        bp[0, :b.numel()] = b
-        hip.x3_pack_bias(bp, bias_steps[li:li + 1])
-    macs += weights[-1].shape[1]
-    hip.x3_pack(weights[-1].detach().float()[:1].contiguous(), True, 1, 0, 16, buf[off:off + final_elems])
-    fb = torch.zeros(32, device=dev)
-    fb[0] = biases[-1].detach().float()[0]
-    return PackedX3Occ(desc, buf, bias_steps, fb, skip_layer, pe_first, macs)
+    desc, Ws, bs, final, fb = _lowp_net(weights, biases, hip.OUT_OCC, n_out=1)
+    skip_layer, pe_first = -1, 0
+    for li in skips:
+        if 0 < li < n - 1:
+            assert Ws[li].shape[1] == 256, 'the skip layer reads cat[h, pe]: 256 input features'
+            Ws[li] = Ws[li] * (1.0 / math.sqrt(2.0))
+            skip_layer, pe_first = li, 256 - d_pe
+    w, bias_steps, macs = _pack_x3(desc, Ws, bs, final, [(Ws[0], False, 8, 0, 4)], range(n - 1))
+    return PackedX3Occ(desc, w, bias_steps, fb, skip_layer, pe_first, macs)
 
 
 def pack_relu_mlp_x3_grouped(weights, biases, din_a, din_b, skip_at, out_act=hip.OUT_NONE):
     """stage2 Network (stage2/model/renderer.py:34-49) of width 256 for the split-bf16 engine, grouped form.  Weight stream in
     execution order (include/psnerf_hip.h, psn_mlp_infer_x3_grouped)."""
     n = len(weights)
-    dev = weights[0].device
     assert 3 <= n <= hip.MAX_LAYERS + 1 and din_a <= 64 and 0 < din_b <= 64
     assert all(w.shape[0] == 256 for w in weights[:-1]) and weights[-1].shape[0] <= 32
-    desc = hip.PsnBf16Desc()
-    desc.n_hidden, desc.n_out, desc.out_act = n - 1, weights[-1].shape[0], out_act
-    KS = hip.X3_KS
-    final_elems = 16 * 3 * 512
-    buf = torch.zeros((n - 2) * 16 * KS + final_elems + 56 * 512, device=dev, dtype=torch.bfloat16)  # (+ 56 KB: the last request over-reads)
-    bias_steps = torch.zeros(n - 1, 4096, device=dev, dtype=torch.bfloat16)
-    wa, wb, b_in = [], [], []
-    off = 0
-    macs = 0
-    for li in range(n - 1):
-        W = weights[li].detach().float()
-        macs += W.shape[0] * W.shape[1]
-        has_in = li == 0 or li - 1 == skip_at
-        desc.has_in[li] = int(has_in)
-        c0 = 0 if li == 0 else 256
-        if li > 0:
-            hip.x3_pack(W[:, :256], True, 8, 0, 16, buf[off:off + 16 * KS])
-            off += 16 * KS
-        if has_in:
-            wa.append(W[:, c0:c0 + din_a]); wb.append(W[:, c0 + din_a:c0 + din_a + din_b]); b_in.append(biases[li].detach().float())
-        else:
-            hip.x3_pack_bias(biases[li].detach().float().view(1, 256).contiguous(), bias_steps[li:li + 1])
-    macs += weights[-1].shape[0] * weights[-1].shape[1]
-    hip.x3_pack(weights[-1].detach().float(), True, 1, 0, 16, buf[off:off + final_elems])
-    fb = torch.zeros(32, device=dev)
-    fb[:weights[-1].shape[0]] = biases[-1].detach().float()
-    init_wa = torch.zeros(len(wa) * 256, 64, device=dev)
-    init_wb = torch.zeros(len(wb) * 256, 64, device=dev)
-    for i, (a_, b_) in enumerate(zip(wa, wb)):
-        init_wa[i * 256:(i + 1) * 256, :din_a] = a_
-        init_wb[i * 256:(i + 1) * 256, :din_b] = b_
-    return PackedX3Grouped(desc, buf, bias_steps, fb, init_wa, init_wb, torch.cat(b_in).contiguous(), macs)
+    desc, Ws, bs, final, fb = _lowp_net(weights, biases, out_act, skip_at)
+    w, bias_steps, macs = _pack_x3(desc, Ws, bs, final, [], [li for li in range(n - 1) if not desc.has_in[li]])
+    return PackedX3Grouped(desc, w, bias_steps, fb, *_group_tables(desc, Ws, bs, din_a, din_b), macs)

@@ -1252,13 +1252,36 @@ def weight_norm_bwd(vs, gs, scales, dws, out=None):
 
 
 # --------------------------------------------------------------------------- bf16 inference engine (evaluation only)
-def mlp_pack_bf16(W, permuted, n_ot, ks0, n_ks, dst):
-    """k-steps [ks0, ks0 + n_ks) of the fp32 matrix W (row-major view) -> dst (flat bfloat16 view, n_ks*n_ot*512
-    elements) in fragment order of the bf16 engine."""
+def lowp_pack(W, permuted, n_ot, ks0, n_ks, dst, planes=1):
+    """k-steps [ks0, ks0 + n_ks) of the fp32 matrix W (row-major view) -> dst (flat bfloat16 view, n_ks * n_ot * planes * 512
+    elements) in fragment order (psn_lowp_pack): planes = 1 for the bf16 engine, 3 (hi / mid / lo of every weight) for the split one."""
     assert W.dim() == 2 and W.stride(1) == 1 and W.is_cuda and W.dtype == torch.float32
-    assert dst.dtype == torch.bfloat16 and dst.is_contiguous() and dst.numel() == n_ks * n_ot * 512
-    _check(_lib.psn_mlp_pack_bf16(W.data_ptr(), W.stride(0), W.shape[0], W.shape[1], int(permuted), n_ot, ks0, n_ks,
-                                  dst.data_ptr(), _stream()), 'mlp_pack_bf16')
+    assert dst.dtype == torch.bfloat16 and dst.is_contiguous() and dst.numel() == n_ks * n_ot * planes * 512
+    _check(_lib.psn_lowp_pack(W.data_ptr(), W.stride(0), W.shape[0], W.shape[1], int(permuted), n_ot, ks0, n_ks, planes,
+                              dst.data_ptr(), _stream()), 'lowp_pack')
+
+
+def lowp_pack_bias(V, pieces, dst=None):
+    """V [n, 256] fp32 -> [n, 4096] bfloat16 bias k-steps (psn_lowp_pack_bias): K slots 0 .. pieces - 1 = the value's leading bf16
+    pieces; 2 for the bf16 engine (one row per (group, input layer)), 3 for the split one."""
+    assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and V.dim() == 2 and V.shape[1] == 256
+    if dst is None:
+        dst = torch.empty(V.shape[0], 4096, device=V.device, dtype=torch.bfloat16)
+    assert dst.dtype == torch.bfloat16 and dst.is_contiguous() and dst.numel() == V.shape[0] * 4096
+    _check(_lib.psn_lowp_pack_bias(V.data_ptr(), V.shape[0], pieces, dst.data_ptr(), _stream()), 'lowp_pack_bias')
+    return dst
+
+
+def _bf16_stream(t, name):
+    """Device pointer of a packed weight or bias stream."""
+    if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()):
+        raise RuntimeError('%s: must be a contiguous bfloat16 HIP tensor' % name)
+    return t.data_ptr()
+
+
+def _n_in(desc):
+    """Hidden layers of a PsnBf16Desc that read the input block."""
+    return sum(1 for l in range(desc.n_hidden) if desc.has_in[l])
 
 
 def _bf16_table(t, name):
@@ -1282,24 +1305,14 @@ def mlp_infer_bf16(desc, packed_w, final_bias, tab_a, a_div, a_mod, tab_b, b_div
     return out
 
 
-def bf16_pack_group_bias(V, dst=None):
-    """V [n, 256] fp32 (one row per (group, input layer)) -> [n, 4096] bfloat16 bias k-steps of the bf16 engine."""
-    assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and V.dim() == 2 and V.shape[1] == 256
-    if dst is None:
-        dst = torch.empty(V.shape[0], 4096, device=V.device, dtype=torch.bfloat16)
-    assert dst.dtype == torch.bfloat16 and dst.is_contiguous() and dst.numel() == V.shape[0] * 4096
-    _check(_lib.psn_bf16_pack_group_bias(V.data_ptr(), V.shape[0], dst.data_ptr(), _stream()), 'bf16_pack_group_bias')
-    return dst
-
-
 def mlp_infer_bf16_grouped(desc, packed_w, final_bias, tab_a, group_bias, n_groups, out=None):
-    """Rows (g, n) -> g * tab_a.shape[0] + n; group_bias [n_groups * n_in_layers, 4096] bfloat16 (bf16_pack_group_bias)."""
+    """Rows (g, n) -> g * tab_a.shape[0] + n; group_bias [n_groups * n_in_layers, 4096] bfloat16 (lowp_pack_bias, 2 pieces)."""
     rows = tab_a.shape[0]
     if out is None:
         out = torch.empty(n_groups * rows, desc.n_out, device=packed_w.device, dtype=torch.float32)
     assert packed_w.dtype == torch.bfloat16 and packed_w.is_cuda and packed_w.is_contiguous()
     assert final_bias.numel() == 32
-    n_in = sum(1 for l in range(desc.n_hidden) if desc.has_in[l])
+    n_in = _n_in(desc)
     if not (group_bias.is_cuda and group_bias.dtype == torch.bfloat16 and group_bias.is_contiguous()
             and group_bias.numel() == n_groups * n_in * 4096):
         raise RuntimeError('group_bias: must be a contiguous [n_groups * %d, 4096] bfloat16 HIP tensor' % n_in)
@@ -1317,42 +1330,21 @@ def mlp_infer_bf16_grouped(desc, packed_w, final_bias, tab_a, group_bias, n_grou
 X3_KS = 8 * 3 * 512  # bf16 elements of one hidden-layer k-step: 8 output tiles x 3 planes x 1 KB
 
 
-def x3_pack(W, permuted, n_ot, ks0, n_ks, dst):
-    """k-steps [ks0, ks0 + n_ks) of the fp32 matrix W -> dst (flat bfloat16 view, n_ks * n_ot * 3 * 512 elements): the three
-    bf16 planes of every weight in fragment order of the split engine (psn_x3_pack)."""
-    assert W.dim() == 2 and W.stride(1) == 1 and W.is_cuda and W.dtype == torch.float32
-    assert dst.dtype == torch.bfloat16 and dst.is_contiguous() and dst.numel() == n_ks * n_ot * 3 * 512
-    _check(_lib.psn_x3_pack(W.data_ptr(), W.stride(0), W.shape[0], W.shape[1], int(permuted), n_ot, ks0, n_ks, dst.data_ptr(), _stream()),
-           'x3_pack')
-
-
-def x3_pack_bias(V, dst=None):
-    """V [n, 256] fp32 -> [n, 4096] bfloat16 bias k-steps (K slots 0..2 = hi / mid / lo)."""
-    assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and V.dim() == 2 and V.shape[1] == 256
-    if dst is None:
-        dst = torch.empty(V.shape[0], 4096, device=V.device, dtype=torch.bfloat16)
-    assert dst.dtype == torch.bfloat16 and dst.is_contiguous() and dst.numel() == V.shape[0] * 4096
-    _check(_lib.psn_x3_pack_bias(V.data_ptr(), V.shape[0], dst.data_ptr(), _stream()), 'x3_pack_bias')
-    return dst
-
-
 def mlp_infer_x3_grouped(desc, packed_w, bias_steps, final_bias, U, V, out=None, macs_per_row=None):
     """Rows (g, n) -> g * U.shape[0] + n on the split-bf16 engine (psn_mlp_infer_x3_grouped); U [Ns, n_in * 256], V [G, n_in * 256]
     fp32 init tables of the layers that read the input block."""
     rows, n_groups = U.shape[0], V.shape[0]
     if out is None:
         out = torch.empty(n_groups * rows, desc.n_out, device=packed_w.device, dtype=torch.float32)
-    n_in = sum(1 for l in range(desc.n_hidden) if desc.has_in[l])
-    for t, nm in ((packed_w, 'packed_w'), (bias_steps, 'bias_steps')):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()):
-            raise RuntimeError('%s: must be a contiguous bfloat16 HIP tensor' % nm)
+    n_in = _n_in(desc)
+    streams = (_bf16_stream(packed_w, 'packed_w'), _bf16_stream(bias_steps, 'bias_steps'))
     assert U.shape[1] == V.shape[1] == n_in * 256 and bias_steps.numel() == desc.n_hidden * 4096
     assert final_bias.numel() == 32 and out.numel() == n_groups * rows * desc.n_out
     ptrs = (_tptr(final_bias, 'final_bias'), _tptr(U, 'U'), _tptr(V, 'V'), _tptr(out, 'out'))
     if n_groups * rows == 0:
         return out
     with _Prof('mlp_infer_x3', n_groups * rows, None if macs_per_row is None else 2.0 * macs_per_row * n_groups * rows):
-        _check(_lib.psn_mlp_infer_x3_grouped(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), ptrs[0],
+        _check(_lib.psn_mlp_infer_x3_grouped(ctypes.byref(desc), streams[0], streams[1], ptrs[0],
                                              ptrs[1], rows, ptrs[2], n_groups, ptrs[3], _stream()), 'mlp_infer_x3_grouped')
     return out
 
@@ -1366,9 +1358,7 @@ def mlp_infer_x3_occ(desc, packed_w, bias_steps, final_bias, points, pe_octaves,
     if out is None:
         assert out_rows is None
         out = torch.empty(Q, desc.n_out, device=points.device, dtype=torch.float32)
-    for t, nm in ((packed_w, 'packed_w'), (bias_steps, 'bias_steps')):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()):
-            raise RuntimeError('%s: must be a contiguous bfloat16 HIP tensor' % nm)
+    streams = (_bf16_stream(packed_w, 'packed_w'), _bf16_stream(bias_steps, 'bias_steps'))
     assert bias_steps.numel() == desc.n_hidden * 4096 and final_bias.numel() == 32 and desc.n_out == 1
     if n_rows_dev is not None:
         assert n_rows_dev.is_cuda and n_rows_dev.dtype == torch.int64 and n_rows_dev.numel() == 1
@@ -1378,7 +1368,7 @@ def mlp_infer_x3_occ(desc, packed_w, bias_steps, final_bias, points, pe_octaves,
     if Q == 0:
         return out
     with _Prof('mlp_infer_x3_occ', Q, None if macs_per_row is None else 2.0 * macs_per_row * Q):
-        _check(_lib.psn_mlp_infer_x3_occ(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), ptrs[0],
+        _check(_lib.psn_mlp_infer_x3_occ(ctypes.byref(desc), streams[0], streams[1], ptrs[0],
                                          ptrs[1], Q, None if n_rows_dev is None else n_rows_dev.data_ptr(),
                                          None if out_rows is None else out_rows.data_ptr(), int(pe_octaves), float(pe_scale),
                                          int(skip_layer), int(pe_first), ptrs[2], _stream()), 'mlp_infer_x3_occ')
@@ -1466,16 +1456,14 @@ def march_sweep_x3(desc, packed_w, bias_steps, final_bias, origin, direction, fa
     evaluated when early_exit (their entries are uninitialised).  n_steps a multiple of 128."""
     N = origin.shape[0]
     assert origin.shape == (N, 3) and direction.shape == (N, 3) and far.shape == (N,) and u.numel() == n_steps == omu.numel()
-    for t, nm in ((packed_w, 'packed_w'), (bias_steps, 'bias_steps')):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()):
-            raise RuntimeError('%s: must be a contiguous bfloat16 HIP tensor' % nm)
+    streams = (_bf16_stream(packed_w, 'packed_w'), _bf16_stream(bias_steps, 'bias_steps'))
     occ = torch.empty(N, n_steps, device=origin.device, dtype=torch.float32)
     skip = torch.zeros(N, device=origin.device, dtype=torch.int32) if early_exit else None
     if N == 0:
         return occ, skip
     count = torch.zeros(1, device=origin.device, dtype=torch.int64) if PROFILE_EVENTS is not None else None
     with _Prof('march_sweep_x3', N * n_steps, None if (macs_per_row is None or count is None) else (count, 2.0 * macs_per_row * 128)):
-        _check(_lib.psn_march_sweep_x3(ctypes.byref(desc), packed_w.data_ptr(), bias_steps.data_ptr(), _tptr(final_bias, 'final_bias'),
+        _check(_lib.psn_march_sweep_x3(ctypes.byref(desc), streams[0], streams[1], _tptr(final_bias, 'final_bias'),
                                        _tptr(origin, 'origin'), _tptr(direction, 'direction'), _tptr(far, 'far'), _tptr(u, 'u'), _tptr(omu, 'omu'),
                                        float(near), N, int(n_steps), float(tau), int(pe_octaves), float(pe_scale), int(skip_layer), int(pe_first),
                                        None if skip is None else skip.data_ptr(), occ.data_ptr(), None if count is None else count.data_ptr(),

@@ -112,7 +112,7 @@ def order_free(terms, what=''):
 
 # --------------------------------------------------------------------------- layout models of the packers (family B3)
 def k_index(permuted, ks, h, j):
-    """K index of element j of lane half h in k-step ks (header comment of psn_mlp_pack_bf16 / psn_x3_pack)."""
+    """K index of element j of lane half h in k-step ks (header comment of psn_lowp_pack)."""
     if permuted:
         return 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3)
     return 16 * ks + 8 * h + j
@@ -141,19 +141,19 @@ def _bits16(t):
 
 
 def pack_bf16_reference(W, permuted, n_ot, ks0, n_ks):
-    """psn_mlp_pack_bf16: every element the RNE bf16 of its source -> int16 bit patterns, flat."""
+    """psn_lowp_pack, one plane: every element the RNE bf16 of its source -> int16 bit patterns, flat."""
     return _bits16(torch.from_numpy(pack_source(W, permuted, n_ot, ks0, n_ks))).reshape(-1)
 
 
 def pack_x3_reference(W, permuted, n_ot, ks0, n_ks):
-    """psn_x3_pack: [ks][ot][plane][lane][8], plane p = piece p of split3 -> int16 bit patterns, flat."""
+    """psn_lowp_pack, three planes: [ks][ot][plane][lane][8], plane p = piece p of split3 -> int16 bit patterns, flat."""
     src = torch.from_numpy(pack_source(W, permuted, n_ot, ks0, n_ks))
     return _bits16(torch.stack(split3(src), dim=2)).reshape(-1)
 
 
 def bias_step_reference(V, n_pieces):
     """Bias k-steps [n][8 tiles][64 lanes][8]: K slot 8 h + j = piece (8 h + j) of V[r, 32 ot + (lane & 31)] for the first
-    ``n_pieces`` slots (2: psn_bf16_pack_group_bias, hi and bf16(v - hi); 3: psn_x3_pack_bias), every other slot 0."""
+    ``n_pieces`` slots (psn_lowp_pack_bias; 2: hi and bf16(v - hi); 3: hi, mid, lo), every other slot 0."""
     V = torch.as_tensor(V, dtype=torch.float32)
     n = V.shape[0]
     out = torch.zeros(n, 8, 64, 8)
@@ -321,7 +321,7 @@ def build_probe_net(c):
     """Four hidden layers; the probes sit in layer c['lp'], features carry over by identity rows, the final layer reads one
     feature per output with weight 1 (one bf16 ulp of a probe = one bf16 ulp of its output).  Two-table form: the probe value is
     the layer's bias (stream bias k-step); grouped form: the probe layer reads the input block, so the value arrives as
-    W_b x_g + b through psn_bf16_pack_group_bias (bf16(b) in the bias, the rest in W_b[:, 0] against x_g[0] = 1)."""
+    W_b x_g + b through psn_lowp_pack_bias (bf16(b) in the bias, the rest in W_b[:, 0] against x_g[0] = 1)."""
     g = _gen(c)
     net = Net()
     net.c = c

@@ -186,8 +186,15 @@ def test_argument_validation_needs_no_gpu():
     assert rc == -1 and b'n_items' in lib.psn_last_error()
     rc = lib.psn_secant_step(None, 0.5, None, None, None, None, None, None, None, None, 4, None)
     assert rc == -1 and b'null' in lib.psn_last_error()
-    rc = lib.psn_mlp_pack_bf16(None, 4, 4, 4, 0, 8, 0, 1, None, None)
+    rc = lib.psn_lowp_pack(None, 4, 4, 4, 0, 8, 0, 1, 1, None, None)
     assert rc == -1 and b'null' in lib.psn_last_error()
+    # the packers write 1 or 3 planes of a weight and 2 or 3 pieces of a bias: anything else is refused before any HIP call
+    for planes in (0, 2, 4):
+        rc = lib.psn_lowp_pack(ctypes.c_void_p(64), 4, 4, 4, 0, 8, 0, 1, planes, ctypes.c_void_p(64), None)
+        assert rc == -1 and ('n_planes=%d' % planes).encode() in lib.psn_last_error()
+    for pieces in (1, 4):
+        rc = lib.psn_lowp_pack_bias(ctypes.c_void_p(64), 1, pieces, ctypes.c_void_p(64), None)
+        assert rc == -1 and ('n_pieces=%d' % pieces).encode() in lib.psn_last_error()
     # in-kernel positional encoding: shape rules are checked before any pointer is touched
     m = hip.PsnMlpDesc()
     rc = lib.psn_mlp_infer_pe(ctypes.byref(m), None, None, None, 10, 6, 1.0, None, None)

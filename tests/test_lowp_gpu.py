@@ -143,7 +143,7 @@ def test_bf16_engine_is_exact(mods, cuda, c):
 
 def test_bf16_group_bias_rows_arrive_exactly(mods, cuda):
     """The V rows of a grouped probe case, W_b x_g + b formed by the fp32 GEMM, equal the reference's bit for bit: the probe values
-    reach psn_bf16_pack_group_bias as the reference states them."""
+    reach psn_lowp_pack_bias as the reference states them."""
     hip, _ = mods
     c = [x for x in lc.A2_CASES if x['form'] == 'grouped'][1]
     net, ref = lc.reference_bf16(c)
@@ -201,7 +201,7 @@ def test_bf16_packer_equals_layout_model(mods, cuda, item):
     v, W = _views(item, cuda)
     n = item['n_ks'] * item['n_ot'] * 512
     whole, dst = _bf16_guarded(n, cuda)
-    hip.mlp_pack_bf16(v, item['permuted'], item['n_ot'], item['ks0'], item['n_ks'], dst)
+    hip.lowp_pack(v, item['permuted'], item['n_ot'], item['ks0'], item['n_ks'], dst, planes=1)
     assert same_bits16(dst, lc.pack_bf16_reference(W, item['permuted'], item['n_ot'], item['ks0'], item['n_ks'])) and _guard16(whole, n)
 
 
@@ -211,7 +211,7 @@ def test_x3_packer_planes_sum_to_the_source(mods, cuda, item):
     v, W = _views(item, cuda)
     n = item['n_ks'] * item['n_ot'] * 3 * 512
     whole, dst = _bf16_guarded(n, cuda)
-    hip.x3_pack(v, item['permuted'], item['n_ot'], item['ks0'], item['n_ks'], dst)
+    hip.lowp_pack(v, item['permuted'], item['n_ot'], item['ks0'], item['n_ks'], dst, planes=3)
     assert _guard16(whole, n)
     p = dst.float().cpu().view(item['n_ks'], item['n_ot'], 3, 64, 8)
     src = torch.from_numpy(lc.pack_source(W, item['permuted'], item['n_ot'], item['ks0'], item['n_ks']))
@@ -223,10 +223,10 @@ def test_x3_packer_planes_sum_to_the_source(mods, cuda, item):
 def test_bias_step_packers_equal_layout_model(mods, cuda, n):
     hip, _ = mods
     V = lc.bias_matrix(n)
-    for fn, pieces in ((hip.bf16_pack_group_bias, 2), (hip.x3_pack_bias, 3)):
+    for pieces in (2, 3):
         whole, dst = _bf16_guarded(n * 4096, cuda)
-        fn(V.to(cuda), dst.view(n, 4096))
-        assert same_bits16(dst, lc.bias_step_reference(V, pieces)) and _guard16(whole, n * 4096), fn.__name__
+        hip.lowp_pack_bias(V.to(cuda), pieces, dst.view(n, 4096))
+        assert same_bits16(dst, lc.bias_step_reference(V, pieces)) and _guard16(whole, n * 4096), pieces
 
 
 # --------------------------------------------------------------------------- argument checks
@@ -476,8 +476,8 @@ def test_x3_engine_refuses_bad_arguments_and_launches_nothing(mods, cuda):
         return hip._lib.psn_mlp_infer_x3_occ(ctypes.byref(desc), pk3.w.data_ptr(), pk3.bias_steps.data_ptr(), pk3.final_bias.data_ptr(), pts.data_ptr(), 33,
                                              None, None, octaves, lc.OCC_SCALE, skip_layer, pe_first, out.data_ptr(), st)
 
-    def sweep_(n_steps=128, octaves=lc.OCC_OCTAVES, skip_layer=pk3.skip_layer, pe_first=pk3.pe_first):
-        return hip._lib.psn_march_sweep_x3(ctypes.byref(pk3.desc), pk3.w.data_ptr(), pk3.bias_steps.data_ptr(), pk3.final_bias.data_ptr(),
+    def sweep_(n_steps=128, octaves=lc.OCC_OCTAVES, skip_layer=pk3.skip_layer, pe_first=pk3.pe_first, w=pk3.w.data_ptr()):
+        return hip._lib.psn_march_sweep_x3(ctypes.byref(pk3.desc), w, pk3.bias_steps.data_ptr(), pk3.final_bias.data_ptr(),
                                            ray[0].data_ptr(), ray[1].data_ptr(), ray[2].data_ptr(), ray[3].data_ptr(), ray[4].data_ptr(), 0.25, 3, n_steps,
                                            0.5, octaves, lc.OCC_SCALE, skip_layer, pe_first, None, out.data_ptr(), None, st)
     _refused(hip, grouped_(desc=_desc_copy(hip, pkx.desc, n_hidden=1)), 'mlp_infer_x3_grouped', 'mlp_infer_x3_grouped: n_hidden=1')
@@ -492,6 +492,8 @@ def test_x3_engine_refuses_bad_arguments_and_launches_nothing(mods, cuda):
     _refused(hip, sweep_(pe_first=191), 'march_sweep_x3', 'pe_first=191')
     _refused(hip, sweep_(n_steps=200), 'march_sweep_x3', 'n_steps=200 must be a multiple of 128')
     _refused(hip, sweep_(n_steps=64), 'march_sweep_x3', 'n_steps=64 must be a multiple of 128')
+    assert pk3.w.data_ptr() % 16 == 0     # ... and 2 bytes off that boundary: refused like its siblings' streams, before any launch
+    _refused(hip, sweep_(w=pk3.w.data_ptr() + 2), 'march_sweep_x3', 'buffers must be 16-byte aligned')
     torch.cuda.synchronize()
     assert untouched(whole)
     assert grouped_() == 0 and occ_() == 0 and sweep_() == 0     # the same calls with good arguments run
