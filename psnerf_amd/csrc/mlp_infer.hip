@@ -1633,7 +1633,10 @@ extern "C" int psn_root_find(const PsnMlpDesc* desc, const float* packed_w, cons
     PSN_CHECK_ARG(desc && packed_w && packed_b && origin && dir && bracket && d_out, "root_find: null pointer");
     if (const int rc = check_pe_net(*desc, "root_find", pe_octaves, false, true, true)) return rc;
     PSN_CHECK_ARG(n_iter >= 0 && n_iter <= 64, "root_find: n_iter=%d", n_iter);
-    if (n_rays <= 0) return PSN_OK;
+    if (n_rays <= 0) {  // nothing launched: psn_mlp_last_path answers with zeros, not with an earlier launch
+        t_last_path = {};
+        return PSN_OK;
+    }
     InferArgs a = base_args(*desc, packed_w, packed_b, n_rays, d_out);
     a.ray_o = origin; a.ray_d = dir; a.bracket = bracket; a.tau = tau; a.pe_scale = pe_scale; a.n_iter = n_iter; a.pe_octaves = pe_octaves;
     // the feature-parallel form (16 rays per workgroup) is written for exactly the shape check_pe_net admits (even stage counts per

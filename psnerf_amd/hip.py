@@ -813,15 +813,23 @@ def march_sweep(desc, packed_w, packed_b, origin, direction, far, u, omu, near, 
     return occ, skip
 
 
-def root_find(desc, packed_w, packed_b, origin, direction, bracket, tau, n_iter, pe_octaves, pe_scale):
-    """n_iter secant iterations on every ray in one launch (psn_root_find) -> d_pred [N]."""
+def root_find(desc, packed_w, packed_b, origin, direction, bracket, tau, n_iter, pe_octaves, pe_scale, out=None, path=None):
+    """n_iter secant iterations on every ray in one launch (psn_root_find) -> d_pred [N].
+    ``out``: the caller's [N] destination; ``path``: a PsnMlpPath that receives what the library launched."""
     N = origin.shape[0]
     assert bracket.shape == (4, N)
-    out = torch.empty(N, device=origin.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(N, device=origin.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.numel() == N
+    if N == 0:  # (empty tensors have no device pointer to hand over) nothing is launched: a zeroed path
+        if path is not None:
+            ctypes.memset(ctypes.byref(path), 0, ctypes.sizeof(path))
+        return out
     with _Prof('root_find', N, None):
         _check(_lib.psn_root_find(ctypes.byref(desc), _tptr(packed_w, 'packed_w'), _tptr(packed_b, 'packed_b'), _tptr(origin, 'origin'),
                                   _tptr(direction, 'direction'), _tptr(bracket, 'bracket'), N, float(tau), int(n_iter), int(pe_octaves),
-                                  float(pe_scale), out.data_ptr(), _stream()), 'root_find')
+                                  float(pe_scale), _tptr(out, 'd_pred'), _stream()), 'root_find')
+    _last_path(path)
     return out
 
 

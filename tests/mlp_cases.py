@@ -10,6 +10,11 @@ first and second dump of every hidden layer.  ``dispatch(case)`` restates the co
 prologue in Python: which instantiation runs and in which state every launch switch is.
 
 Weights are randn * 1.2 / sqrt(fan_in), biases randn * 0.05 (the scales of tests/test_kernels_gpu.py).
+
+Family H is the secant root finder (psn_root_find, both forms): ``root_inputs(case)`` builds rays and brackets on the CPU from the
+float64 definition, ``root_find_definition`` is the float32 definition of the iterates, ``trace_check`` the float64 check that
+follows the kernel's own iterates (teacher-forced: a free-running float64 secant is no truth, a branch on f_mid < 0 may
+legitimately flip once f_mid is rounding noise).
 """
 import math
 import zlib
@@ -22,6 +27,7 @@ MAX_LAYERS = 12            # PSN_MLP_MAX_LAYERS
 BLOCK = 64                 # rows per workgroup (4 waves x 16)
 RTOL = 1e-5                # helpers.assert_vs_truth(rtol=RTOL, atol='max') per tensor
 GUARD = 3                  # guard rows in front of and behind every output / dump buffer
+SRC_ROOT = 4               # kSrcRootFp: the feature-parallel root finder's key in the kernel table
 
 # activation programs by name -> PSN_ACT_* (include/psnerf_hip.h; test_mlp_cpu.py compares with the parsed header)
 ACT = dict(none=0, relu=1, softplus=2, relu_mask=3, mul_aux=4, mul2=5, softplus_bwd=6, head=7, relu_bits=8,
@@ -210,7 +216,9 @@ def build_pe(c):
     prev = 0
     for l in range(depth):
         reads_in = l == 0 or l == skip
-        out_dim = 217 if (kact == 7 and l == skip - 1) else 256
+        # 217 outputs -> the next layer reads 7 activation k-tiles: in front of the skip layer (skip_kact = 7: 7 + the encoding), or in
+        # front of layer ``trim`` (which need not read the encoding: 7 stages and no input block)
+        out_dim = 217 if ((kact == 7 and skip is not None and l == skip - 1) or (c.get('trim') is not None and l == c['trim'] - 1)) else 256
         fan = prev + (d_pe if reads_in else 0)
         L = dict(act=c['act'], Wact=_w(g, out_dim, prev, fan) if prev else None, Wa=None, Wb=None, bias=_b(g, out_dim), mode=None)
         if reads_in:
@@ -219,6 +227,10 @@ def build_pe(c):
         net.layers.append(L)
         prev = out_dim
     net.layers.append(dict(act='none', Wact=_w(g, c['n_out'], prev, prev), Wa=None, Wb=None, bias=_b(g, c['n_out']), mode=None))
+    if c['src'] == SRC_ROOT:
+        net.octaves = c['octaves']
+        net.maps = (1, max(c['n'], 1), 1, 1)
+        return net          # (the query points are the root finder's own: evaluate(net, dtype, points=...))
     if c['src'] == 3:
         N, M = c['rays'], c['steps']
         o = torch.randn(N, 3, generator=g) * 0.3
@@ -361,11 +373,15 @@ def _sig_from_a(a):
     return 1.0 - torch.exp(-100.0 * torch.clamp(a, min=0.0))
 
 
-def evaluate(net, dtype, wrong=None):
+def evaluate(net, dtype, wrong=None, points=None):
     """-> dict(out=[n, n_out] or None, d1=[per hidden layer: first dump], d2=[second dump or None]).
-    ``wrong``: one of WRONG_FORMS, a deliberately wrong formulation (test_mlp_cpu.py shows that the bound catches each)."""
+    ``wrong``: one of WRONG_FORMS, a deliberately wrong formulation (test_mlp_cpu.py shows that the bound catches each).
+    ``points`` (encoding networks): float32 [n, 3] query points in place of the case's own."""
     c = net.c
     n = c['rays'] * c['steps'] if c.get('src') == 3 else (c.get('capacity') or c['n'])
+    xs32 = getattr(net, 'xs32', None)
+    if points is not None:
+        n, xs32 = points.shape[0], points * torch.tensor(c['pe_scale'], dtype=torch.float32)
     T = lambda t: None if t is None else t.to(dtype)
     rows = torch.arange(n)
     a_div, a_mod, b_div, b_mod = net.maps
@@ -375,7 +391,7 @@ def evaluate(net, dtype, wrong=None):
     ib = (rows // b_div) % b_mod
     xa = xb = None
     if c['kind'] == 'pe':
-        xa = pe_columns(net.xs32, net.octaves, dtype)
+        xa = pe_columns(xs32, net.octaves, dtype)
     elif net.tab_a is not None:
         xa = T(net.tab_a)[ia]
         xb = T(net.tab_b)[ib] if net.tab_b is not None else None
@@ -500,8 +516,9 @@ def dead_rows(c, live):
     return dead
 
 
-def dispatch(c, net=None, point_major=True, live=None):
-    """The launch path of a case: a restatement of mlp_infer_plan / mlp_infer_pe_impl / psn_march_sweep and of the kernel prologue."""
+def dispatch(c, net=None, point_major=True, live=None, row_parallel=False):
+    """The launch path of a case: a restatement of mlp_infer_plan / mlp_infer_pe_impl / psn_march_sweep / psn_root_find and of the
+    kernel prologue.  ``row_parallel``: the root finder under PSN_ROOT_FIND_ROW_PARALLEL=1."""
     net = net or build(c)
     hid = net.width // 32
     shapes = layer_shape(net)
@@ -509,6 +526,11 @@ def dispatch(c, net=None, point_major=True, live=None):
     n_out = net.n_out
     if c['kind'] == 'pe':
         # (mlp_infer_pe_impl and psn_march_sweep launch ONE instantiation each, unconditionally: nothing to restate but its name)
+        if c['src'] == SRC_ROOT:
+            # psn_root_find: the feature-parallel kernel, 16 rays per workgroup, or (test hook) the row-parallel engine SRC = 1
+            src, per = (1, BLOCK) if row_parallel else (SRC_ROOT, 16)
+            return dict(chain=False, hid=8, src=src, trim=True, from_a=False, pair=False, point_major=False, tb='none', half_final=True,
+                        wide_final=False, blocks_straddle=False, blocks=(c['n'] + per - 1) // per, name='lean/16/src%d/trim' % src)
         return dict(chain=False, hid=8, src=c['src'], trim=True, from_a=False, pair=False, point_major=False, tb='none',
                     half_final=n_out <= 16, wide_final=False, blocks_straddle=False,
                     name='lean/16/src%d/trim' % c['src'])
@@ -544,9 +566,11 @@ def dispatch(c, net=None, point_major=True, live=None):
                 half_final=0 < n_out <= 16, wide_final=chain_ and hid == 8 and n_out > 32, blocks_straddle=straddle, name=name)
 
 
-# every instantiation the fp32 dispatcher can launch (mlp_infer_plan, mlp_infer_pe_impl, psn_march_sweep)
+# every fp32 entry of the engine's kernel table (kInferKernels), i.e. every instantiation the fp32 dispatcher can launch: mlp_infer_plan,
+# mlp_infer_pe_impl, psn_march_sweep and psn_root_find (src4 = the feature-parallel root finder, kSrcRootFp; src1 = the row-parallel one)
 INSTANTIATIONS = ('lean/16', 'lean/8', 'lean/4', 'chain/16', 'chain/8', 'chain/4', 'lean/16/trim', 'chain/16/trim',
-                  'chain/16/froma', 'chain/16/trim/froma', 'lean/16/src2/trim', 'lean/16/src3/trim')
+                  'chain/16/froma', 'chain/16/trim/froma', 'lean/16/src2/trim', 'lean/16/src3/trim', 'lean/16/src4/trim',
+                  'lean/16/src1/trim')
 
 
 # --------------------------------------------------------------------------- case tables
@@ -640,8 +664,8 @@ for w_ in WIDTHS:
 F_CASES.append(chain('F-base-programs-w128', n=63, width=128, prog=('softplus', 'mul_aux', 'mul2', 'head', 'softplus_bwd'), n_out=3, in_scale=0.01))
 
 # encoding prologue
-PE_DEFAULTS = dict(kind='pe', src=2, n=65, width=256, depth=4, skip=2, skip_kact=8, act='softplus', octaves=6, pe_scale=1.0, n_out=1,
-                   out_act='occ', tiles=(2, 0), capacity=None, count=None, scatter=False, seed=0)
+PE_DEFAULTS = dict(kind='pe', src=2, n=65, width=256, depth=4, skip=2, skip_kact=8, trim=None, act='softplus', octaves=6, pe_scale=1.0,
+                   n_out=1, out_act='occ', tiles=(2, 0), capacity=None, count=None, scatter=False, seed=0)
 
 
 def pe(id_, **kw):
@@ -667,8 +691,207 @@ for rays_ in (1, 3):
     for st_ in (64, 192):
         G_CASES.append(pe('G-sweep-rays%d-steps%d' % (rays_, st_), src=3, rays=rays_, steps=st_, n=rays_ * st_, skip_kact=7 if rays_ == 3 else 8))
 
+# --------------------------------------------------------------------------- H: the secant root finder (psn_root_find)
+# One small random occupancy network per case.  Rays: 1 .. 129 (16 rays per workgroup in the feature-parallel form, 64 in the
+# row-parallel one).  Hidden layers 1, 2, 3, 4, 5, 11: the odd-depth barrier of root_find_fp_kernel, the even depths without it and
+# PSN_MLP_MAX_LAYERS.  Stage counts of a layer behind layer 0: 8 activation k-tiles + the encoding (10), 7 + the encoding (9), 7 and
+# no input block (``trim``; the odd-count branch followed directly by the prefetch of the next layer), 8 and no input block.
+H_N_ITER = (0, 1, 2, 3, 8, 64)    # the iteration counts of the bit-for-bit comparison of the two forms
+H_STEPWISE = 8                    # D[0] .. D[8] are compared with the step-by-step composition
+H_TRACE = 3                       # D[0] .. D[3] are checked against float64, teacher-forced
+H_FAR, H_STEPS = 1.5, 33          # the CPU sweep that finds the brackets: depths linspace(0, H_FAR, H_STEPS)
+
+
+def root(id_, **kw):
+    return pe(id_, src=SRC_ROOT, **kw)
+
+
+H_CASES = [
+    root('H-rays1-depth1', n=1, depth=1, skip=None, octaves=0, pe_scale=1.0, tau=0.5),
+    root('H-rays15-depth2-skip8', n=15, depth=2, skip=1, skip_kact=8, act='relu', octaves=6, pe_scale=0.5, tau=0.3),
+    root('H-rays16-depth3-skip7-linear', n=16, depth=3, skip=2, skip_kact=7, act='none', octaves=10, pe_scale=2.0 / 3.0, tau=0.5),
+    root('H-rays17-depth4-trim', n=17, depth=4, skip=None, trim=2, octaves=6, pe_scale=1.0, tau=0.3),
+    root('H-rays63-depth5-skip8', n=63, depth=5, skip=3, skip_kact=8, act='relu', octaves=10, pe_scale=0.5, tau=0.5),
+    # (the softplus stack shrinks the signal by 0.72 per layer, so eleven of them leave a logit that the last bias decides; the skip
+    #  sits late and the seed is one whose logit changes sign on a third of the unit box -- a choice of inputs, made on the CPU)
+    root('H-rays64-depth11-skip7', n=64, depth=11, skip=9, skip_kact=7, octaves=6, pe_scale=2.0 / 3.0, tau=0.5, seed=6),
+    root('H-rays65-depth4-skip8', n=65, depth=4, skip=2, skip_kact=8, octaves=6, pe_scale=1.0, tau=0.5),
+    root('H-rays129-depth3-skip7', n=129, depth=3, skip=1, skip_kact=7, act='relu', octaves=10, pe_scale=1.0, tau=0.3),
+    root('H-rays33-depth1-oct0', n=33, depth=1, skip=None, octaves=0, pe_scale=2.0 / 3.0, tau=0.5),
+    root('H-rays65-depth3-trim', n=65, depth=3, skip=None, trim=1, octaves=10, pe_scale=0.5, tau=0.3),
+    # (with ReLU and no octaves this network is piecewise linear along a ray: the secant lands on the root in two iterations, f_2 is
+    #  rounding noise and the allowance of iterate 3 exceeds the tenth of the bracket -- an unchecked pair, which no case may have)
+    root('H-rays17-depth2-trim', n=17, depth=2, skip=None, trim=1, act='relu', octaves=10, pe_scale=1.0, tau=0.5),
+]
+
+# the argument checks of psn_root_find (PSN_E_ARG, nothing launched, the output untouched): what is changed on a valid call, and the
+# words of the check that must answer
+H_ARG_CASES = [
+    dict(id='H-ARG-n_iter-1', n_iter=-1, refusal='root_find: n_iter=-1'),
+    dict(id='H-ARG-n_iter65', n_iter=65, refusal='root_find: n_iter=65'),
+    dict(id='H-ARG-out_act', desc=dict(out_act=OUT['sigmoid']), refusal='expects an occupancy network'),
+    dict(id='H-ARG-n_out3', desc=dict(n_out=3), refusal='expects an occupancy network'),
+    dict(id='H-ARG-bf16x2', desc=dict(w_format='bf16x2'), refusal='fp32 weight stages only'),
+    dict(id='H-ARG-softplus-final', final_act='softplus', refusal='activation'),
+    dict(id='H-ARG-in_kt_a1', desc=dict(in_kt_a=1), refusal='the input block is one 64-column positional encoding'),
+]
+
+
+def ray_kinds(n):
+    """Per ray: 'x' a genuine crossing bracket, 'benign' the (0, 1, -1, 1) psn_first_crossing writes for a miss, 'dd' d_low == d_high,
+    'ff' f_low == f_high (a division by zero: inf, then NaN).  A single ray is a crossing."""
+    kinds = []
+    for i in range(n):
+        kinds.append('x' if n == 1 else 'benign' if i % 16 in (5, 11) else 'dd' if i % 32 == 9 else 'ff' if i % 32 == 25 else 'x')
+    return kinds
+
+
+def secant32(dl, dh, fl, fh):
+    """rendering.py:526 in float32, every operation rounded separately: -f_low (d_high - d_low) / (f_high - f_low) + d_low."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return ((-fl) * (dh - dl) / (fh - fl) + dl).astype(np.float32)
+
+
+def point32(o, v, d):
+    """rendering.py:531 in float32: p = ray0 + d_pred * direction, the product rounded before the sum."""
+    return (o + (d[:, None] * v).astype(np.float32)).astype(np.float32)
+
+
+_ROOT = {}
+
+
+def root_inputs(c):
+    """(net, dict(origin [n,3], direction [n,3], bracket [4,n], kinds, tau)) as float32 numpy arrays, built once per process.  The
+    brackets of the crossing rays come from the float64 definition: random rays are swept on H_STEPS depths, and a ray whose first
+    sample is free yields the pair around its first free -> occupied sign change of occ - tau."""
+    if c['id'] in _ROOT:
+        return _ROOT[c['id']]
+    net = build(c)
+    g = _gen(c, salt=1)
+    n, tau = c['n'], float(np.float32(c['tau']))
+    kinds = ray_kinds(n)
+    need = kinds.count('x')
+    depths = torch.linspace(0.0, H_FAR, H_STEPS)
+    found = []      # (origin, direction, d_low, d_high, f_low, f_high)
+    for _ in range(40):
+        o = (torch.rand(64, 3, generator=g) * 2 - 1) * 0.6
+        v = torch.nn.functional.normalize(torch.randn(64, 3, generator=g), dim=-1)
+        p = (o[:, None, :] + v[:, None, :] * depths[None, :, None]).reshape(-1, 3)
+        val = evaluate(net, torch.float64, points=p)['out'].reshape(64, H_STEPS) - tau
+        change = (val[:, :-1] < 0) & (val[:, 1:] > 0)
+        other = (val[:, :-1] * val[:, 1:]) <= 0
+        for r in range(64):
+            ch = other[r].nonzero().reshape(-1)
+            if val[r, 0] < 0 and ch.numel() and bool(change[r, ch[0]]):
+                i = int(ch[0])
+                found.append((o[r], v[r], depths[i], depths[i + 1], val[r, i].float(), val[r, i + 1].float()))
+        if len(found) >= need:
+            break
+    assert len(found) >= need, '%s: %d of %d crossings found' % (c['id'], len(found), need)
+    origin = (torch.rand(n, 3, generator=g) * 2 - 1) * 0.6
+    direction = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    bracket = torch.tensor([0.0, 1.0, -1.0, 1.0]).repeat(n, 1)
+    it = iter(found)
+    for i, k in enumerate(kinds):
+        if k == 'x':
+            o, v, dl, dh, fl, fh = next(it)
+            origin[i], direction[i] = o, v
+            bracket[i] = torch.stack([dl, dh, fl, fh])
+        elif k == 'dd':
+            bracket[i] = torch.tensor([0.4, 0.4, -0.3, 0.2])
+        elif k == 'ff':
+            bracket[i] = torch.tensor([0.2, 0.7, 0.25, 0.25]) if i % 64 == 25 else torch.tensor([0.2, 0.7, -0.25, -0.25])
+    inp = dict(origin=origin.numpy().copy(), direction=direction.numpy().copy(), bracket=bracket.t().contiguous().numpy().copy(),
+               kinds=kinds, tau=c['tau'], crossing=np.array([k == 'x' for k in kinds]))
+    _ROOT[c['id']] = (net, inp)
+    return _ROOT[c['id']]
+
+
+ROOT_WRONG_FORMS = ('wrong_end', 'tau_plus', 'occ_sign', 'swap_rows', 'one_fewer')
+
+
+def root_find_definition(net, inp, n_iter, dtype=torch.float32, wrong=None):
+    """The definition of psn_root_find: [D[0], .., D[n_iter]] float32 [n], D[k] = the depth after k iterations (rendering.py:525-555:
+    the secant estimate of the bracket, then per iteration the occupancy at ray0 + d_pred * direction, the bracket end on its side
+    moved, the next estimate).  The network is evaluated in ``dtype``, the secant arithmetic in float32.  ``wrong``: one of
+    ROOT_WRONG_FORMS."""
+    o, v = inp['origin'], inp['direction']
+    dl, dh, fl, fh = (inp['bracket'][r].copy() for r in range(4))
+    if wrong == 'swap_rows':
+        fl, fh = fh, fl
+    tau = np.float32(inp['tau'])
+    dp = secant32(dl, dh, fl, fh)
+    D = [dp]
+    for _ in range(n_iter):
+        p = torch.from_numpy(point32(o, v, dp))
+        with np.errstate(all='ignore'):
+            occ = evaluate(net, dtype, wrong='occ_sign' if wrong == 'occ_sign' else None, points=p)['out'].reshape(-1).float().numpy()
+        fm = (occ + tau if wrong == 'tau_plus' else occ - tau).astype(np.float32)
+        low = fm < 0
+        if wrong == 'wrong_end':
+            low = ~low
+        dl, fl = np.where(low, dp, dl), np.where(low, fm, fl)
+        dh, fh = np.where(low, dh, dp), np.where(low, fh, fm)
+        dp = secant32(dl, dh, fl, fh)
+        D.append(dp)
+    if wrong == 'one_fewer':
+        D = [D[0]] + D[:-1]
+    return D
+
+
+def trace_check(net, inp, D):
+    """The float64 check of the iterates D[0] .. D[H_TRACE] of the crossing rays, teacher-forced: the state (d_l, d_h, f_l, f_h) is
+    float64 with error bounds (beta_l, beta_h) on the two f values, 0 at the start (the kernel reads the bracket exactly).  D[0] must
+    have the bits of the float32 formula.  For k = 0, 1, 2: p_k = fl32(o + fl32(D[k] v)) is the kernel's own point, f_k = occ64(p_k) -
+    tau, b_k = RTOL |occ64| + RTOL max |occ64| over the case's points of this iterate (the bound family G holds psn_mlp_infer_pe to).
+    Moving the low end is admissible if f_k < b_k, the high end if f_k > -b_k; each admissible candidate gives d' = -f_l (d_h - d_l)
+    / (f_h - f_l) + d_l with the first-order allowance a' = (|(d_h - d_l) f_h| beta_l + |(d_h - d_l) f_l| beta_h) / (f_h - f_l)^2
+    + 4 ulp32(d').  D[k + 1] must lie within a' of an admissible candidate; the state continues with the candidate of the smallest
+    |D[k + 1] - d'| / a'.  A pair (ray, k) whose a' exceeds a tenth of the ray's initial bracket width is unchecked.
+    -> dict(first_equal, worst = the largest ratio, failures, unchecked, where = (ray, k) of the worst, widest = the largest a' in units
+    of the tenth of the bracket width at which a pair counts as unchecked)."""
+    sel = inp['crossing']
+    o, v = inp['origin'][sel], inp['direction'][sel]
+    br = inp['bracket'][:, sel]
+    tau = float(np.float32(inp['tau']))
+    first = secant32(br[0], br[1], br[2], br[3])
+    res = dict(first_equal=bool(np.array_equal(first.view(np.int32), np.asarray(D[0], dtype=np.float32)[sel].view(np.int32))),
+               worst=0.0, failures=0, unchecked=0, where=None, widest=0.0)
+    dl, dh, fl, fh = (br[r].astype(np.float64) for r in range(4))
+    bl, bh = np.zeros_like(dl), np.zeros_like(dl)
+    width = dh - dl
+    for k in range(H_TRACE):
+        dk = np.asarray(D[k], dtype=np.float32)[sel]
+        nxt = np.asarray(D[k + 1], dtype=np.float32)[sel].astype(np.float64)
+        occ = evaluate(net, torch.float64, points=torch.from_numpy(point32(o, v, dk)))['out'].reshape(-1).numpy()
+        fk = occ - tau
+        bk = RTOL * np.abs(occ) + RTOL * float(np.abs(occ).max())
+        cands = []
+        dk64 = dk.astype(np.float64)
+        for low, ok in ((True, fk < bk), (False, fk > -bk)):
+            cdl, cfl, cbl = (dk64, fk, bk) if low else (dl, fl, bl)
+            cdh, cfh, cbh = (dh, fh, bh) if low else (dk64, fk, bk)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                dn = -cfl * (cdh - cdl) / (cfh - cfl) + cdl
+                al = (np.abs((cdh - cdl) * cfh) * cbl + np.abs((cdh - cdl) * cfl) * cbh) / (cfh - cfl) ** 2
+                al = al + 4.0 * np.spacing(np.abs(dn).astype(np.float32)).astype(np.float64)
+                ratio = np.abs(nxt - dn) / al
+            ratio = np.where(ok & np.isfinite(ratio), ratio, np.inf)
+            cands.append((ratio, al, (cdl, cdh, cfl, cfh, cbl, cbh)))
+        pick_low = cands[0][0] <= cands[1][0]
+        ratio = np.where(pick_low, cands[0][0], cands[1][0])
+        al = np.where(pick_low, cands[0][1], cands[1][1])
+        dl, dh, fl, fh, bl, bh = (np.where(pick_low, a, b) for a, b in zip(cands[0][2], cands[1][2]))
+        res['failures'] += int((ratio > 1.0).sum())
+        res['unchecked'] += int((al > 0.1 * width).sum())
+        res['widest'] = max(res['widest'], float((al / (0.1 * width)).max()) if al.size else 0.0)
+        if ratio.size and float(ratio.max()) > res['worst']:
+            res['worst'], res['where'] = float(ratio.max()), (int(np.flatnonzero(sel)[int(ratio.argmax())]), k)
+    return res
+
+
 LEAN_CASES = B_CASES + C_CASES + D_CASES
-ALL_NET_CASES = B_CASES + C_CASES + D_CASES + E_CASES + F_CASES + G_CASES
+ALL_NET_CASES =B_CASES + C_CASES + D_CASES + E_CASES + F_CASES + G_CASES
 SCATTER_ROWS = 300
 
 # the argument checks (PSN_E_ARG, nothing launched)

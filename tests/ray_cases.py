@@ -9,6 +9,10 @@ the case's SCALE (1 below 512 samples).
 
 first_crossing / sample_points: the torch formulations of rendering.py:457-504 and :110-176 in the reference's op order, to be
 met bit for bit.
+
+The per-ray kernels around the root finder (psn_secant_step, psn_stage1_rays, psn_surface_points, psn_stage1_targets,
+psn_shadow_points; last section): numpy definitions in the reference's op order, float32 to be met bit for bit, float64 as the
+truth of the real-number outputs.
 """
 import functools
 
@@ -507,3 +511,243 @@ def non_monotone_rays(case, c0, c1):
     """Number of rays (all taken as hit rays) whose concatenated outer + inner depths are not non-decreasing before the sort."""
     d = hit_depths(case['dist'], case['far'], SP_NEAR, SP_DELTA, c1, c0, lin(c1)[0], lin(c0)[0], presort=True)
     return int((d[:, 1:] < d[:, :-1]).any(-1).sum())
+
+
+# ======================================================================================= the per-ray kernels around the root finder
+# psn_secant_step, psn_shadow_points (csrc/sample.hip), psn_stage1_rays, psn_surface_points, psn_stage1_targets (csrc/small.hip):
+# numpy transcriptions of the reference lines those files cite, every operation rounded in ``dtype`` (float32: to be met bit for
+# bit; float64 on the float32 inputs cast up: the truth of the real-number outputs, helpers.assert_vs_truth with RTOL).
+PR_N = (1, 255, 256, 257)    # one thread per ray, 256 per workgroup; n = 0 launches nothing
+
+
+def _f32(*xs):
+    return [np.ascontiguousarray(x, dtype=np.float32) for x in xs]
+
+
+# ---- psn_secant_step (rendering.py:525-555)
+def secant_case(n, tau):
+    """Brackets d_low < d_high, f_low < 0 < f_high, rays, and the occupancies of three update steps.  From 8 rays on: ray 2 meets
+    occ == tau exactly in every step (f_mid = 0 is not < 0: the HIGH end moves), ray 3 has d_low == d_high, ray 4 f_low == f_high (a
+    division by zero: inf, then inf or NaN), ray 5 the benign (0, 1, -1, 1) of a miss."""
+    g = torch.Generator().manual_seed(7000 + n)
+    r = lambda *s: torch.rand(*s, generator=g)
+    d_low = 0.5 + 0.5 * r(n)
+    st = dict(d_low=d_low, d_high=d_low + 0.05 + 0.25 * r(n), f_low=-0.01 - 0.49 * r(n), f_high=0.01 + 0.49 * r(n))
+    occ = r(3, n)
+    if n >= 8:
+        occ[:, 2] = float(np.float32(tau))
+        st['d_high'][3] = st['d_low'][3]
+        st['f_high'][4] = st['f_low'][4]
+        for k, v in zip(('d_low', 'd_high', 'f_low', 'f_high'), (0.0, 1.0, -1.0, 1.0)):
+            st[k][5] = v
+    origin = torch.randn(n, 3, generator=g)
+    direction = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    out = {k: v.numpy().copy() for k, v in st.items()}
+    out.update(occ=occ.numpy().copy(), origin=origin.numpy().copy(), direction=direction.numpy().copy(), tau=tau, n=n)
+    return out
+
+
+def secant_step_definition(st, occ, tau, d_pred, origin, direction, dtype=np.float32):
+    """One step on the state st = dict(d_low, d_high, f_low, f_high) -> (new state, d_pred, p_mid); occ None: the initial step."""
+    T = lambda x: np.asarray(x, dtype=dtype)
+    dl, dh, fl, fh = (T(st[k]) for k in ('d_low', 'd_high', 'f_low', 'f_high'))
+    if occ is not None:
+        fm = T(occ) - T(np.float32(tau))
+        low = fm < 0
+        dp = T(d_pred)
+        dl, fl, dh, fh = np.where(low, dp, dl), np.where(low, fm, fl), np.where(low, dh, dp), np.where(low, fh, fm)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        new = (-fl) * (dh - dl) / (fh - fl) + dl
+        p = T(origin) + new[:, None] * T(direction)
+    return dict(d_low=dl, d_high=dh, f_low=fl, f_high=fh), new, p
+
+
+# ---- psn_stage1_rays (common.py:205-226, rendering.py:576-596)
+RAY_SCENES = ('outside', 'inside', 'behind')
+RAY_UNDER_MIN = 1e-4   # rays with |under| below it are left out of the random set (far = sqrt(under) - b is ill-conditioned there)
+
+
+def rays_case(n, scene):
+    """(pix [n,2], K [4,4], W [4,4], radius): fx != fy; 'outside' = the camera 1.5 units out looking at a sphere of radius 0.45 that
+    about half the pixels miss (under <= 0: far = 0), 'inside' = the camera inside the sphere (every ray leaves it), 'behind' = the
+    sphere behind the camera (under > 0 but sqrt(under) - b < 0: clamped to 0)."""
+    g = torch.Generator().manual_seed(7100 + 10 * n + RAY_SCENES.index(scene))
+    h, w = 48, 64
+    K = torch.eye(4)
+    K[0, 0], K[1, 1], K[0, 2], K[1, 2] = 70.0, 66.0, 31.5, 23.25
+    R = torch.linalg.qr(torch.randn(3, 3, generator=g))[0]
+    W = torch.eye(4)
+    W[:3, :3] = R
+    off = torch.tensor([0.03, -0.02, 0.05])
+    W[:3, 3] = {'outside': -R[:, 2] * 1.5 + off, 'inside': R[:, 0] * 0.2 + off, 'behind': R[:, 2] * 1.5 + off}[scene]
+    radius = {'outside': 0.45, 'inside': 0.8, 'behind': 0.45}[scene]
+    pix = torch.stack([torch.rand(4 * n + 64, generator=g) * w, torch.rand(4 * n + 64, generator=g) * h], -1)
+    pix[::3] = torch.floor(pix[::3])
+    K_, W_ = K.numpy().copy(), W.numpy().copy()
+    under = stage1_rays_definition(pix.numpy(), K_, W_, radius, np.float64)[3]
+    keep = np.abs(under) >= RAY_UNDER_MIN
+    pix = pix.numpy()[keep][:n].copy()
+    assert pix.shape[0] == n
+    return pix, K_, W_, radius
+
+
+def stage1_rays_definition(pix, K, W, radius, dtype=np.float32, wrong=None):
+    """-> (cam [n,3], rays [n,3], far [n], under [n]); K [3|4, 3|4]; radius^2 is the float32 the library is handed.
+    wrong='fy': the y axis over fy (the reference divides BOTH axes by fx, common.py:220)."""
+    T = lambda x: np.asarray(x, dtype=dtype)
+    pix, K, W = T(pix), T(K), T(W)
+    r2 = T(np.float32(float(radius ** 2)))
+    fx, cx, cy = K[0, 0], K[0, 2], K[1, 2]
+    qx, qy = (pix[:, 0] - cx) / fx, (pix[:, 1] - cy) / (K[1, 1] if wrong == 'fy' else fx)
+    d = np.stack([qx * W[r, 0] + qy * W[r, 1] + W[r, 2] for r in range(3)], -1)
+    c = np.broadcast_to(W[:3, 3], d.shape)
+    nrm = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+    d = d / nrm[:, None]
+    b = d[:, 0] * c[:, 0] + d[:, 1] * c[:, 1] + d[:, 2] * c[:, 2]
+    cn = np.sqrt(c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1] + c[:, 2] * c[:, 2])
+    under = b * b - (cn * cn - r2)
+    with np.errstate(invalid='ignore'):
+        far = np.where(under > 0, np.maximum(np.sqrt(np.where(under > 0, under, 0)) - b, 0), 0).astype(dtype)
+    return np.ascontiguousarray(c), d, far, under
+
+
+# explicit inputs for the sign of ``under`` (identity rotation, the pixel at the principal point: the ray is (0, 0, 1)):
+# (camera, radius^2 as float32, far).  b = 0 and |cam|^2 = 1: under = radius^2 - 1 exactly.
+RAY_UNDER_EXPLICIT = (
+    ((1.0, 0.0, 0.0), 1.0, 0.0),                                                  # under == 0: not > 0, the ray misses
+    ((1.0, 0.0, 0.0), float(np.nextafter(np.float32(1), np.float32(2))), None),   # under = one ulp: far = its root
+    ((1.0, 0.0, 0.0), float(np.nextafter(np.float32(1), np.float32(0))), 0.0),    # under = -half an ulp
+    ((0.0, 0.0, -2.0), 1.0, 3.0),                                                  # b = -2, under = 1: far = 1 + 2
+    ((0.0, 0.0, 2.0), 1.0, 0.0),                                                   # b = +2, under = 1: 1 - 2 < 0, clamped
+)
+
+
+# ---- psn_surface_points (rendering.py:516-522, 84-108)
+def surface_case(n):
+    """flags {0,1,2,3} x d_pred {finite, 0, +inf, NaN} in the first 16 rays (n = 1: flags 3 on a finite depth), random behind them."""
+    g = torch.Generator().manual_seed(7200 + n)
+    d = (torch.rand(n, generator=g) * 3).numpy()
+    fl = torch.randint(0, 4, (n,), generator=g, dtype=torch.int32).numpy()
+    table = [(f, v) for f in range(4) for v in (0.75, 0.0, np.inf, np.nan)]
+    if n == 1:
+        fl[0] = 3
+    for i, (f, v) in enumerate(table[:n if n >= 16 else 0]):
+        fl[i], d[i] = f, v
+    cam = torch.randn(n, 3, generator=g).numpy()
+    rays = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1).numpy()
+    return _f32(d)[0], fl.astype(np.int32), cam, rays
+
+
+def surface_points_definition(d_pred, flags, cam, rays):
+    """-> (d_i, dists, obj_mask, points) in float32."""
+    d = np.where(flags & 1, d_pred, np.float32(np.inf)).astype(np.float32)     # rendering.py:519-521
+    d = np.where(flags & 2, d, np.float32(0)).astype(np.float32)               # :522
+    zero = d == 0
+    ok = np.isfinite(d)
+    dists = np.where(zero, 0, np.where(ok, d, 1)).astype(np.float32)
+    return d, dists, ok & ~zero, (cam + rays * dists[:, None]).astype(np.float32)
+
+
+# ---- psn_stage1_targets (common.py:172-202, training.py:166-191)
+TG_SIZES = ((1, 1), (1, 7), (6, 8), (48, 64))
+TG_ANGLE = 70.0
+
+
+def nearest_index(pix, h, w, wrong=None):
+    """grid_sample(nearest, align_corners=True, zeros padding) at x = 2 px / w - 1 -> (iy, ix, inside) in float32 op order.
+    wrong='floor': floor(x + 0.5) in place of the half-to-even rint."""
+    one, two = np.float32(1), np.float32(2)
+    px, py = _f32(pix[:, 0], pix[:, 1])
+    x, y = two * px * (one / np.float32(w)) - one, two * py * (one / np.float32(h)) - one
+    fx, fy = ((x + one) / two) * np.float32(w - 1), ((y + one) / two) * np.float32(h - 1)
+    rnd = (lambda v: np.floor(v + np.float32(0.5))) if wrong == 'floor' else np.rint
+    rx, ry = rnd(fx), rnd(fy)
+    inside = (rx >= 0) & (rx <= w - 1) & (ry >= 0) & (ry <= h - 1)
+    return np.where(inside, ry, 0).astype(np.int64), np.where(inside, rx, 0).astype(np.int64), inside, fx, fy
+
+
+def targets_case(h, w, n):
+    """Images and pixel positions: every integer pixel (cycled), x = -1 (outside from 3 columns on: zeros), x = w and y = h (with
+    align_corners=True they are x = 1: exactly the LAST pixel, inside; pixel position px reads column rint(px (w - 1) / w)), x = w + 1, y = h + 1 and (w + 5, -3) (outside), fractional
+    positions, the exact ties (w / 2, .) and (., h / 2) of even sizes (fx = (w - 1) / 2: half to even), and two pixels whose normal has n2 ==
+    cos(TG_ANGLE) exactly (kept) and one ulp below (dropped)."""
+    g = torch.Generator().manual_seed(7300 + 100 * h + w + n)
+    img = torch.rand(3, h, w, generator=g).numpy()
+    mask, valid, nmask = ((torch.rand(h, w, generator=g) > t).float().numpy() for t in (0.4, 0.1, 0.3))
+    normal = torch.nn.functional.normalize(torch.randn(3, h, w, generator=g), dim=0).numpy()
+    cos_t = np.float32(np.cos(np.deg2rad(TG_ANGLE)))
+    # pixel (0, 0), read at (0, 0), and -- unless it is the same one -- pixel (h - 1, w - 1), read at (w, h)
+    nmask[0, 0] = nmask[h - 1, w - 1] = 1.0
+    if (h, w) != (1, 1):
+        normal[2, h - 1, w - 1] = np.nextafter(cos_t, np.float32(0))
+    normal[2, 0, 0] = cos_t
+    world = np.eye(4, dtype=np.float32)
+    world[:3, :3] = torch.linalg.qr(torch.randn(3, 3, generator=g))[0].numpy()
+    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
+    grid = np.stack([xs.reshape(-1), ys.reshape(-1)], -1).astype(np.float32)
+    special = np.array([[0, 0], [w, h], [-1, 0], [w, 0], [0, h], [w + 5, -3], [w / 2, 0], [0, h / 2], [w / 2, h / 2],
+                        [0.4, 0.6], [w - 1.4, h - 1.5], [w * 0.37, h * 0.61], [w + 1, 0], [0, h + 1]], dtype=np.float32)
+    frac = (torch.rand(n, 2, generator=g) * torch.tensor([w + 1.0, h + 1.0]) - 0.5).numpy()
+    pix = np.concatenate([special, grid, frac])[:n] if n > 1 else special[8:9]
+    if pix.shape[0] < n:
+        pix = np.concatenate([pix, grid[np.arange(n - pix.shape[0]) % grid.shape[0]]])
+    return dict(img=img, mask=mask, valid=valid, nmask=nmask, normal=_f32(normal)[0], world=world, pix=_f32(pix)[0], cos_t=float(cos_t), h=h, w=w)
+
+
+def targets_definition(c, mask=True, valid=True, nmask=True, want_normal=False, use_angle=False, wrong=None):
+    """-> (rgb [n,3], mask_gt [n] float, mask_valid [n] bool, norm_mask [n] bool or None, normal_gt [n,3] or None)."""
+    iy, ix, inside, _, _ = nearest_index(c['pix'], c['h'], c['w'], wrong)
+    take = lambda im: np.where(inside, im[..., iy, ix], np.float32(0)).astype(np.float32)
+    n = c['pix'].shape[0]
+    rgb = take(c['img']).T.copy()
+    mask_gt = (take(c['mask']) != 0).astype(np.float32) if mask else np.ones(n, dtype=np.float32)
+    mask_valid = (take(c['valid']) != 0) if valid else np.ones(n, dtype=bool)
+    nm = (take(c['nmask']) != 0) if nmask else None
+    ngt = None
+    if want_normal:
+        nv = take(c['normal'])                                  # [3, n]
+        if use_angle and nm is not None:
+            nm = nm & ~(nv[2] < np.float32(c['cos_t']))          # training.py:189-190: on the unrotated normal
+        Wm = c['world']
+        sgn = _f32([1, -1, -1])[0]
+        ngt = np.stack([nv[0] * (Wm[r, 0] * sgn[0]) + nv[1] * (Wm[r, 1] * sgn[1]) + nv[2] * (Wm[r, 2] * sgn[2]) for r in range(3)], -1)
+        ngt = ngt.astype(np.float32)
+    return rgb, mask_gt, mask_valid, nm, ngt
+
+
+# ---- psn_shadow_points (rendering.py:378-408)
+# (n_surf, n_lights, n_steps, lnear, box, kind): totals 1, 105, 666 and 600 (no multiple of 64 or 256), 1027 (five workgroups)
+SH_CASES = ((1, 1, 1, 0.0, 0.55, 'random'), (7, 3, 5, 0.05, 0.55, 'random'), (37, 2, 9, 0.05, 0.55, 'random'), (50, 3, 4, 0.0, 0.55, 'edge'),
+            (79, 1, 13, 0.05, 0.55, 'random'), (37, 2, 9, 0.05, 10.0, 'all'), (37, 2, 9, 0.05, 0.001, 'none'),
+            (0, 3, 5, 0.05, 0.55, 'random'), (7, 0, 5, 0.05, 0.55, 'random'))
+SH_LFAR = 1.2
+
+
+def shadow_case(ns, nl, S, lnear, box, kind):
+    g = torch.Generator().manual_seed(7400 + 1000 * ns + 10 * nl + S)
+    surf = (torch.rand(ns, 3, generator=g) * 1.2 - 0.6).numpy()
+    if kind == 'none':
+        surf = surf + np.float32(2.0)
+    if kind == 'edge':
+        # step 0 of a ray with lnear = 0 is the surface point itself (d = 0 * 1 + lfar * 0): a coordinate exactly +-box is inside, one
+        # ulp beyond it outside
+        b = np.float32(box)
+        up, dn = np.nextafter(b, np.float32(2)), np.nextafter(-b, np.float32(-2))
+        for i, (axis, v) in enumerate(((0, b), (1, -b), (2, b), (0, up), (1, dn), (2, up), (0, -b), (2, dn))):
+            surf[i] = 0.1
+            surf[i, axis] = v
+    ldir = torch.nn.functional.normalize(torch.randn(nl, 3, generator=g), dim=-1).numpy()
+    u = torch.linspace(0.0, 1.0, steps=S).numpy()
+    return _f32(surf, ldir, u, np.float32(1) - u)
+
+
+def shadow_points_definition(surf, ldir, u, omu, lnear, lfar, box, strict=False):
+    """-> (rows int64 [k] ascending, pts [k,3]): the dense rows (l ns + s) S + m whose point lies in the closed cube, and the points.
+    strict: the wrong form with < in place of <=."""
+    ns, nl, S = surf.shape[0], ldir.shape[0], u.shape[0]
+    d = (np.float32(lnear) * omu + np.float32(lfar) * u).astype(np.float32)
+    p = (surf[None, :, None, :] + (ldir[:, None, None, :] * d[None, None, :, None]).astype(np.float32)).astype(np.float32).reshape(-1, 3)
+    b = np.float32(box)
+    inside = ((p < b) & (p > -b)).all(-1) if strict else ((p <= b) & (p >= -b)).all(-1)
+    rows = np.flatnonzero(inside).astype(np.int64)
+    return rows, p[rows]

@@ -1,7 +1,11 @@
 """What tests/test_mlp_gpu.py rests on, checked without a GPU: the plain-torch definitions of tests/mlp_cases.py equal the oracle
 networks, the case tables reach every instantiation and both states of every launch switch of the fp32 dispatcher, the float32
 evaluation of every case stays within half the bound of the float64 one (so that helpers.assert_vs_truth allows the kernel no
-element beyond the bound), and five wrong formulations of the definition fail that very check."""
+element beyond the bound), and five wrong formulations of the definition fail that very check.  The same for the
+root finder (family H): both of its instantiations are reached by every case with the grid of the form, the kernel table of the
+source holds no fp32 row outside mlp_cases.INSTANTIATIONS, the brackets are genuine (d_l < d_h, f_l < 0 < f_h, confirmed in float64),
+the float32 definition's own iterates pass trace_check within half the allowance with no unchecked pair (worst ratio 0.15 here,
+0.20 on the device's host), and five wrong root finders fail it.  259 tests, 8 s."""
 import copy
 
 import numpy as np
@@ -78,6 +82,10 @@ def _all_dispatches():
         for order in c.get('orders', (None,)):
             for live in (c.get('live') or (None,)):
                 res.append((c, order, live, mc.dispatch(c, net, point_major=order != 'row', live=live)))
+    for c in mc.H_CASES:      # the root finder: both forms of every case
+        net = mc.root_inputs(c)[0]
+        for row_parallel in (False, True):
+            res.append((c, None, None, mc.dispatch(c, net, row_parallel=row_parallel)))
     return res
 
 
@@ -85,17 +93,40 @@ DISPATCHES = _all_dispatches()
 
 
 def test_case_ids_are_unique_and_small():
-    ids = [c['id'] for c in mc.ALL_NET_CASES + mc.ARG_CASES + mc.PACK_ITEMS]
+    ids = [c['id'] for c in mc.ALL_NET_CASES + mc.ARG_CASES + mc.PACK_ITEMS + mc.H_CASES + mc.H_ARG_CASES]
     assert len(ids) == len(set(ids))
-    for c in mc.ALL_NET_CASES:
+    for c in mc.ALL_NET_CASES + mc.H_CASES:
         assert (c.get('capacity') or c['n']) <= 1300, c['id']
 
 
 def test_every_instantiation_of_the_fp32_dispatcher_is_covered():
-    """lean and chain x NMT 4 / 8 / 16, TRIM lean and chain, FROMA with and without TRIM, SRC 2 and SRC 3."""
+    """lean and chain x NMT 4 / 8 / 16, TRIM lean and chain, FROMA with and without TRIM, SRC 2 and SRC 3, and the root finder in
+    both forms (SRC 4 = feature-parallel, SRC 1 = row-parallel): the fp32 rows of the engine's kernel table."""
     seen = {d['name'] for _, _, _, d in DISPATCHES}
     assert seen == set(mc.INSTANTIATIONS), (sorted(seen), sorted(set(mc.INSTANTIATIONS) - seen))
-    assert len(mc.INSTANTIATIONS) == 12
+    assert len(mc.INSTANTIATIONS) == 14
+    for c in mc.H_CASES:     # every H case reaches both, with the grid of its form
+        fp, rp = mc.dispatch(c, row_parallel=False), mc.dispatch(c, row_parallel=True)
+        assert (fp['name'], fp['blocks']) == ('lean/16/src4/trim', (c['n'] + 15) // 16), c['id']
+        assert (rp['name'], rp['blocks']) == ('lean/16/src1/trim', (c['n'] + 63) // 64), c['id']
+
+
+def test_kernel_table_of_the_source_has_no_fp32_row_outside_the_list():
+    """PSN_MLP_KERNELS of csrc/mlp_infer.hip, read as text: every row with x3 = false, and the feature-parallel root finder behind
+    it, is an entry of mc.INSTANTIATIONS, and the other way round."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'psnerf_amd', 'csrc', 'mlp_infer.hip')).read()
+    table = src[src.index('#define PSN_MLP_KERNELS(K)'):src.index('struct InferKernel')]
+    rows = re.findall(r'K\((true|false), (\d+), (\d), (true|false), (true|false), (true|false)\)', table)
+    assert len(rows) == 21 and 'kInferKernels[] = {PSN_MLP_KERNELS(PSN_KERNEL_ROW){0, 16, kSrcRootFp, 1, 0, 0, psn::root_find_fp_kernel}}' in src
+    assert 'constexpr int kSrcRootFp = %d;' % mc.SRC_ROOT in src
+    names = {'lean/16/src%d/trim' % mc.SRC_ROOT}
+    for chain, nmt, s, trim, from_a, x3 in rows:
+        if x3 == 'false':
+            names.add('%s/%s%s%s%s' % ('chain' if chain == 'true' else 'lean', nmt, '/src' + s if s != '0' else '',
+                                       '/trim' if trim == 'true' else '', '/froma' if from_a == 'true' else ''))
+    assert names == set(mc.INSTANTIATIONS), sorted(names ^ set(mc.INSTANTIATIONS))
 
 
 def test_every_launch_switch_occurs_in_both_states():
@@ -189,3 +220,81 @@ def test_sign_words_and_dead_rows():
     assert mc.dead_rows(c, 0).sum() == 3 * 192 and mc.dead_rows(c, 1).sum() == 3 * 128 and mc.dead_rows(c, 64).sum() == 3 * 128
     assert mc.dead_rows(c, 65).sum() == 3 * 64 and mc.dead_rows(c, 129).sum() == 0 and mc.dead_rows(c, 197).sum() == 0
     assert not mc.dead_rows(c, 0)[3 * 192:].any()
+
+
+# --------------------------------------------------------------------------- H: the root finder
+def test_root_cases_cover_what_the_kernels_branch_on():
+    """Rays around both workgroup sizes; depths 1 .. 5 and 11 (odd: the extra barrier of the feature-parallel form, even: none, 11 +
+    the final layer = PSN_MLP_MAX_LAYERS); a layer of 10 stages (8 + the encoding), of 9 (7 + the encoding) and of 7 without an
+    input block; all three activations, octaves, scales and both thresholds; degenerate and benign brackets."""
+    H = mc.H_CASES
+    assert {c['n'] for c in H} >= {1, 15, 16, 17, 63, 64, 65, 129} and max(c['n'] for c in H) <= 129
+    assert {c['depth'] for c in H} == {1, 2, 3, 4, 5, 11} and max(c['depth'] for c in H) + 1 == mc.MAX_LAYERS
+    assert {c['act'] for c in H} == {'softplus', 'relu', 'none'} and {c['octaves'] for c in H} == {0, 6, 10}
+    assert {round(c['pe_scale'], 6) for c in H} == {1.0, 0.5, round(2.0 / 3.0, 6)} and {c['tau'] for c in H} == {0.5, 0.3}
+    assert set(mc.H_N_ITER) == {0, 1, 2, 3, 8, 64} and mc.H_STEPWISE == 8 and mc.H_TRACE == 3
+    stages, trim_parity = set(), set()
+    for c in H:
+        net, inp = mc.root_inputs(c)
+        shapes = mc.layer_shape(net)
+        assert shapes[0] == (2, 0, False) and shapes[-1] == (0, 8, False) and len(shapes) == c['depth'] + 1
+        stages |= {(kin, kact) for kin, kact, _ in shapes[1:-1]}
+        if (0, 7, False) in shapes[1:-1]:
+            trim_parity.add(c['depth'] % 2)
+        kinds = inp['kinds']
+        assert c['n'] == 1 or kinds.count('benign') >= 1, c['id']
+        assert c['n'] < 8 or kinds.count('benign') >= 2, c['id']
+    assert stages == {(2, 8), (2, 7), (0, 7), (0, 8)} and trim_parity == {0, 1}
+    assert sum(mc.root_inputs(c)[1]['kinds'].count('dd') for c in H) >= 5 and sum(mc.root_inputs(c)[1]['kinds'].count('ff') for c in H) >= 5
+    assert [a['id'] for a in mc.H_ARG_CASES] == ['H-ARG-n_iter-1', 'H-ARG-n_iter65', 'H-ARG-out_act', 'H-ARG-n_out3', 'H-ARG-bf16x2',
+                                                 'H-ARG-softplus-final', 'H-ARG-in_kt_a1']
+
+
+@pytest.mark.parametrize('c', mc.H_CASES, ids=mc.case_id)
+def test_root_brackets_are_genuine(c):
+    """Crossing rays: d_l < d_h and f_l < 0 < f_h, and the float64 definition at the two bracket ends has those very signs; the other
+    rays carry the benign (0, 1, -1, 1) or one of the two degenerate brackets."""
+    net, inp = mc.root_inputs(c)
+    x = inp['crossing']
+    dl, dh, fl, fh = inp['bracket']
+    assert int(x.sum()) == inp['kinds'].count('x') >= 1
+    assert (dl[x] < dh[x]).all() and (fl[x] < 0).all() and (fh[x] > 0).all()
+    tau = float(np.float32(c['tau']))
+    for d, sign in ((dl, -1), (dh, 1)):
+        p = torch.from_numpy(inp['origin'][x].astype(np.float64) + d[x, None].astype(np.float64) * inp['direction'][x])
+        val = mc.evaluate(net, torch.float64, points=p.float())['out'].reshape(-1).numpy() - tau
+        assert (np.sign(val) == sign).all()
+    for i, k in enumerate(inp['kinds']):
+        b = inp['bracket'][:, i]
+        if k == 'benign':
+            assert b.tolist() == [0.0, 1.0, -1.0, 1.0]
+        elif k == 'dd':
+            assert b[0] == b[1] and b[2] < 0 < b[3]
+        elif k == 'ff':
+            assert b[2] == b[3] and b[0] < b[1]
+    D = mc.root_find_definition(net, inp, 2)
+    ff = np.array([k == 'ff' for k in inp['kinds']])
+    dd = np.array([k == 'dd' for k in inp['kinds']])
+    assert np.isinf(D[0][ff]).all() and not np.isfinite(D[2][ff]).any() and (D[2][dd] == dl[dd]).all() and np.isfinite(D[2][~ff]).all()
+
+
+@pytest.mark.parametrize('c', mc.H_CASES, ids=mc.case_id)
+def test_root_float32_definition_within_half_the_allowance(c):
+    """The input condition of the GPU suite's float64 check: the float32 CPU definition's own iterates pass trace_check with a worst
+    ratio of at most 0.5 and no unchecked (ray, iterate) pair."""
+    net, inp = mc.root_inputs(c)
+    r = mc.trace_check(net, inp, mc.root_find_definition(net, inp, mc.H_TRACE))
+    print('%s worst ratio %.3f at %s' % (c['id'], r['worst'], r['where']))
+    assert r['first_equal'] and r['failures'] == 0 and r['unchecked'] == 0 and r['worst'] <= 0.5, (c['id'], r)
+
+
+@pytest.mark.parametrize('wrong', mc.ROOT_WRONG_FORMS)
+@pytest.mark.parametrize('case_id', ['H-rays65-depth4-skip8', 'H-rays129-depth3-skip7', 'H-rays33-depth1-oct0'])
+def test_wrong_root_finders_fail_the_trace_check(wrong, case_id):
+    """The wrong bracket end moved, tau added, sigmoid(+10 x), the bracket's f rows swapped, one iteration too few."""
+    c = [c for c in mc.H_CASES if c['id'] == case_id][0]
+    net, inp = mc.root_inputs(c)
+    r = mc.trace_check(net, inp, mc.root_find_definition(net, inp, mc.H_TRACE, wrong=wrong))
+    assert not r['first_equal'] or r['failures'] > 0, (case_id, wrong, r)
+    if wrong != 'swap_rows':
+        assert r['first_equal'] and r['failures'] >= 5      # (the first estimate does not depend on these forms)

@@ -2,7 +2,21 @@
 (whose coverage of the dispatcher tests/test_mlp_cpu.py asserts without a GPU): the packers bit for bit against the stage order of
 the header comment, the lean engine (plain, index maps, dumps and sign bits, padded row sets, both block orders), the chain-only
 features (rank-k init, dump tile masks, the 33..64-output final layer, the single-dump programs, masks as tensors and as sign
-bits, initial activations), the encoding prologue (psn_mlp_infer_pe, its indirect form, psn_march_sweep) and the argument checks.
+bits, initial activations), the encoding prologue (psn_mlp_infer_pe, its indirect form, psn_march_sweep), the secant root finder
+(psn_root_find) in both forms and the argument checks.
+
+The root finder (family H: eleven small networks, 1 .. 129 rays, 1 .. 11 hidden layers, layers of 10, 9, 8 and 7 weight stages, brackets
+found on the CPU by sweeping the float64 definition, a few benign and degenerate brackets in every case).  D[k] = the depths after k
+iterations.  (a) root_find_fp_kernel (16 rays per workgroup, the default) and mlp_infer_kernel<false, 16, 1> (64 rays per workgroup,
+under PSN_ROOT_FIND_ROW_PARALLEL=1) write the same bits at k = 0, 1, 2, 3, 8, 64; (b) nothing but the n depths is written; (c) D[0] ..
+D[8] of both forms equal the composition psn_secant_step / psn_mlp_infer_pe / psn_secant_step BIT FOR BIT -- measured on the first
+run on an MI355X: no iterate of any case differs, so equality is asserted, and the 1e-6 of
+test_stage1_gpu.test_root_finder_and_crossing_vs_stepwise_formulation became torch.equal; (d) D[0] .. D[3] of the crossing rays pass
+mlp_cases.trace_check, the teacher-forced float64 check (its docstring has the rule): the figures of the two src1 / src4 rows below are
+the worst |D[k + 1] - d'| / a' and the float32 CPU definition's worst in the same case.  From iterate 4 on stuck iterates divide by
+zero in the float64 candidates, which is why (d) stops at 3 and (c) carries the rest.  A division by zero in the bracket (f_low ==
+f_high) gives inf and, from the first occupancy on, NaN -- except in a ReLU network, where v_max_f32 answers max(NaN, 0) = 0 and the
+depth stays inf; the forms agree on which.
 
 Bound: helpers.assert_vs_truth, rtol 1e-5, atol 'max', per tensor, with the float32 CPU definition as the reference arithmetic;
 test_mlp_cpu.py shows that this reference never passes half the bound, so the kernel is allowed no element beyond it.  Every
@@ -10,25 +24,33 @@ output and dump buffer starts as NaNs of a fixed bit pattern inside a larger buf
 
 Measured worst r_hip per instantiation (units of the bound) on an MI355X:
     instantiation          r_hip   r_ref   worst tensor
-    chain/16               0.120   0.072   F-tiles-w256-00f0 second1
-    chain/16/froma         0.043   0.033   F-softplus_bwd_a out
-    chain/16/trim          0.043   0.023   F-chain-trim dump1
+    chain/16               0.140   0.045   F-wide33 second1
+    chain/16/froma         0.065   0.017   F-mul2_a dump1
+    chain/16/trim          0.060   0.024   F-chain-trim second1
     chain/16/trim/froma    0.041   0.028   F-froma-trim out
     chain/4                0.017   0.022   F-act_init-w64 dump1
     chain/8                0.082   0.045   F-tiles-w128-ffff second1
     lean/16                0.088   0.057   C-pair-P128-G3-init out
     lean/16/src2/trim      0.104   0.038   G-rows129 out
     lean/16/src3/trim      0.117   0.058   G-sweep-rays3-steps192 occ
+    lean/16/src1/trim      0.199   0.109   H-rays17-depth4-trim ray 13 D[2]   (units of the allowance a' of trace_check)
+    lean/16/src4/trim      0.199   0.109   H-rays17-depth4-trim ray 13 D[2]   (the same bits as src1, as (a) asserts)
     lean/16/trim           0.076   0.037   B-trim217 out
     lean/4                 0.134   0.021   B-rows1-w64 out
     lean/8                 0.711   0.133   B-rows1-w128 out   (one row, one output: the bound is purely relative there)
-212 tests, 3.5 s of wall time for the module.
+254 tests, 4.3 s of wall time for the module (the 42 root-finder tests: 1.2 s).
+
+Family H found no defect in either form of the root finder.  One change of the library came with it: psn_root_find on no rays
+now clears the thread's last path, so that psn_mlp_last_path does not answer with an earlier launch.
 
 Finding of this suite (fixed in csrc/mlp_infer.hip, cases C-pointmajor-rows and C-pointmajor-rows-G7 kept): the lean engine took the
 B-side init row through LDS whenever the first and the last row of a workgroup mapped to the same B-table row.  With b_div * b_mod
 < 64 (point-major rows, b_div = 1) the index wraps inside the block -- 63 % 3 == 63 % 7 == 0 -- and all 64 rows were given the
 init row of the first one (168 of 300 outputs wrong, up to 6e4 x the bound).  The test is now the same quotient row / b_div.
 """
+import contextlib
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -84,6 +106,7 @@ def assert_path(c, net, path, **kw):
     """What the library launched (PsnMlpPath) is the instantiation mlp_cases.dispatch states for the case."""
     d = mc.dispatch(c, net, **kw)
     assert path.blocks > 0, '%s: nothing was launched' % c['id']
+    assert 'blocks' not in d or path.blocks == d['blocks'], '%s: a grid of %d workgroups' % (c['id'], path.blocks)
     got = dict(chain=bool(path.chain), hid=path.width16 // 2, src=path.src, trim=bool(path.trim), from_a=bool(path.from_a),
                point_major=path.pm_period != 0)
     assert got == {k: d[k] for k in got}, '%s: launched %s' % (c['id'], got)
@@ -393,6 +416,179 @@ def test_encoding_prologue_vs_float64(mods, cuda, c):
     assert_path(c, net, launched)
     assert torch.equal(got.view(torch.int32), out[:cnt].view(torch.int32)), '%s: differs from the plain launch' % c['id']
     check(c, path, 'out', got, t64['out'][:cnt], t32['out'][:cnt])
+
+
+# --------------------------------------------------------------------------- H: the secant root finder, both forms
+ROOT_FORMS = (False, True)     # row_parallel: False = root_find_fp_kernel (the default), True = mlp_infer_kernel<false, 16, 1> (the hook)
+_ROOT_D = {}                   # (case id, row_parallel, n_iter) -> D[n_iter] as float32 ndarray [n]
+ROOT_TAIL = 70                 # rows behind the n outputs, inside the NaN buffer: more than a workgroup of either form
+
+
+@contextlib.contextmanager
+def root_form(row_parallel):
+    """The library's hook PSN_ROOT_FIND_ROW_PARALLEL (read at every call) set to the wanted form around the calls."""
+    old = os.environ.pop('PSN_ROOT_FIND_ROW_PARALLEL', None)
+    if row_parallel:
+        os.environ['PSN_ROOT_FIND_ROW_PARALLEL'] = '1'
+    try:
+        yield
+    finally:
+        os.environ.pop('PSN_ROOT_FIND_ROW_PARALLEL', None)
+        if old is not None:
+            os.environ['PSN_ROOT_FIND_ROW_PARALLEL'] = old
+
+
+def root_device(c, mods, cuda):
+    net, inp = mc.root_inputs(c)
+    dev = {k: torch.from_numpy(inp[k]).to(cuda).contiguous() for k in ('origin', 'direction', 'bracket')}
+    return net, inp, pack_net(net, mods, cuda), dev
+
+
+def root_depths(c, net, inp, pk, dev, mods, cuda, n_iter, row_parallel):
+    """D[n_iter] of one form: one launch into a NaN buffer.  (b): the guard rows and the ROOT_TAIL rows behind the n outputs keep their
+    bits; the launch is the instantiation and the grid mlp_cases.dispatch states for the form."""
+    key = (c['id'], row_parallel, n_iter)
+    if key not in _ROOT_D:
+        hip, _ = mods
+        n = c['n']
+        whole, view = nan_buffer(n + ROOT_TAIL, 1, cuda, G_OUT)
+        path = hip.PsnMlpPath()
+        with root_form(row_parallel):
+            hip.root_find(pk.desc, pk.w, pk.b, dev['origin'], dev['direction'], dev['bracket'], inp['tau'], n_iter, c['octaves'],
+                          c['pe_scale'], out=view[:n].reshape(-1), path=path)
+        assert_path(c, net, path, row_parallel=row_parallel)
+        what = '%s n_iter=%d row_parallel=%s' % (c['id'], n_iter, row_parallel)
+        assert guards_intact(whole, n + ROOT_TAIL, G_OUT) and untouched(view[n:]), what + ': a row behind the rays was written'
+        _ROOT_D[key] = view[:n].reshape(-1).cpu().numpy().copy()
+    return _ROOT_D[key]
+
+
+def assert_same_depths(a, b, inp, what):
+    """int32 bits equal; on the rays whose bracket divides by zero (f_low == f_high) NaN in the same places and all other bits equal."""
+    ff = np.array([k == 'ff' for k in inp['kinds']])
+    ai, bi = a.view(np.int32), b.view(np.int32)
+    assert np.array_equal(ai[~ff], bi[~ff]), '%s: %d rays differ, the first is ray %d: %r vs %r' % (
+        what, int((ai != bi)[~ff].sum()), int(np.flatnonzero((ai != bi) & ~ff)[0]), a[(ai != bi) & ~ff][0], b[(ai != bi) & ~ff][0])
+    na, nb = np.isnan(a[ff]), np.isnan(b[ff])
+    assert np.array_equal(na, nb) and np.array_equal(ai[ff][~na], bi[ff][~na]), what + ': the degenerate rays differ'
+
+
+@pytest.mark.parametrize('c', mc.H_CASES, ids=mc.case_id)
+def test_root_finder_forms_agree_bit_for_bit(mods, cuda, c):
+    """(a) + (b): at n_iter = 0, 1, 2, 3, 8 and 64 the feature-parallel and the row-parallel form write the same bits, and nothing but the
+    n depths."""
+    net, inp, pk, dev = root_device(c, mods, cuda)
+    for k in mc.H_N_ITER:
+        fp, rp = (root_depths(c, net, inp, pk, dev, mods, cuda, k, form) for form in ROOT_FORMS)
+        assert_same_depths(fp, rp, inp, '%s n_iter=%d: feature-parallel vs row-parallel' % (c['id'], k))
+    # the rays that are no division by zero stay finite to the end; d_low == d_high stays where it is
+    last = root_depths(c, net, inp, pk, dev, mods, cuda, 64, False)
+    kinds = np.array(inp['kinds'])
+    # (a division by zero gives inf, and NaN from the first occupancy on -- unless the network is a ReLU one: v_max_f32 answers
+    #  max(NaN, 0) = 0, the occupancy of the infinite point is a number and the depth stays inf)
+    assert np.isfinite(last[kinds != 'ff']).all() and not np.isfinite(last[kinds == 'ff']).any()
+    assert np.array_equal(last[kinds == 'dd'], inp['bracket'][0][kinds == 'dd'])
+    x = inp['crossing']
+    assert ((last[x] >= inp['bracket'][0][x]) & (last[x] <= inp['bracket'][1][x])).all(), c['id'] + ': a depth left its bracket'
+
+
+@pytest.mark.parametrize('c', mc.H_CASES, ids=mc.case_id)
+def test_root_finder_equals_the_stepwise_composition(mods, cuda, c):
+    """(c): D[k], k = 0 .. 8, of both forms against the composition of kernels this suite gates elsewhere: psn_secant_step without an
+    occupancy for the first estimate and query point, then per iteration psn_mlp_infer_pe on the query points and psn_secant_step with
+    its occupancies.  Bit for bit: see the module docstring for the outcome on the device."""
+    hip, _ = mods
+    net, inp, pk, dev = root_device(c, mods, cuda)
+    n = c['n']
+    d_pred = torch.empty(n, device=cuda)
+    d_low, d_high, f_low, f_high = (dev['bracket'][r].clone() for r in range(4))
+    p_mid = torch.empty(n, 3, device=cuda)
+    hip.secant_step(None, inp['tau'], d_pred, d_low, d_high, f_low, f_high, dev['origin'], dev['direction'], p_mid)
+    steps = [d_pred.cpu().numpy().copy()]
+    for k in range(mc.H_STEPWISE):
+        occ = pk.on_points(p_mid, c['octaves'], c['pe_scale']).reshape(-1)
+        hip.secant_step(occ, inp['tau'], d_pred, d_low, d_high, f_low, f_high, dev['origin'], dev['direction'], p_mid)
+        steps.append(d_pred.cpu().numpy().copy())
+    for k in range(mc.H_STEPWISE + 1):
+        for form in ROOT_FORMS:
+            got = root_depths(c, net, inp, pk, dev, mods, cuda, k, form)
+            assert_same_depths(got, steps[k], inp, '%s D[%d] row_parallel=%s vs step by step' % (c['id'], k, form))
+
+
+@pytest.mark.parametrize('c', mc.H_CASES, ids=mc.case_id)
+def test_root_finder_iterates_vs_float64(mods, cuda, c):
+    """(d): D[0] .. D[3] of both forms through mlp_cases.trace_check, the float64 check that follows the kernel's own iterates: D[0] has
+    the bits of the float32 formula, every later iterate of a crossing ray lies within the allowance of an admissible float64
+    candidate, and no (ray, iterate) pair is unchecked."""
+    net, inp, pk, dev = root_device(c, mods, cuda)
+    r_ref = mc.trace_check(net, inp, mc.root_find_definition(net, inp, mc.H_TRACE))
+    assert r_ref['failures'] == 0 and r_ref['unchecked'] == 0 and r_ref['worst'] <= 0.5
+    for form in ROOT_FORMS:
+        D = [root_depths(c, net, inp, pk, dev, mods, cuda, k, form) for k in range(mc.H_TRACE + 1)]
+        r = mc.trace_check(net, inp, D)
+        name = mc.dispatch(c, net, row_parallel=form)['name']
+        print('%s %-18s worst ratio %.3f at %s (float32 definition %.3f)' % (c['id'], name, r['worst'], r['where'], r_ref['worst']))
+        assert r['first_equal'], '%s %s: D[0] is not the float32 secant estimate of the bracket' % (c['id'], name)
+        assert r['failures'] == 0 and r['unchecked'] == 0, '%s %s: %r' % (c['id'], name, r)
+        if r['worst'] > _WORST.get(name, (-1.0,))[0]:
+            _WORST[name] = (r['worst'], r_ref['worst'], '%s ray %d D[%d]' % ((c['id'],) + (r['where'][0], r['where'][1] + 1)))
+
+
+def _root_arg_setup(mods, cuda):
+    c = [c for c in mc.H_CASES if c['id'] == 'H-rays65-depth4-skip8'][0]
+    return (c,) + root_device(c, mods, cuda)
+
+
+@pytest.mark.parametrize('a', mc.H_ARG_CASES, ids=mc.case_id)
+def test_root_finder_argument_checks(mods, cuda, a):
+    """PSN_E_ARG with the words of the check the case is built for, nothing launched (the thread's last path, zeroed by a call on no
+    rays just before, stays zero) and the output untouched."""
+    import ctypes
+    import re
+    hip, _ = mods
+    c, net, inp, pk, dev = _root_arg_setup(mods, cuda)
+    desc = type(pk.desc).from_buffer_copy(pk.desc)
+    for k, v in a.get('desc', {}).items():
+        setattr(desc, k, hip.W_BF16X2 if v == 'bf16x2' else v)
+    if 'final_act' in a:
+        desc.layers[desc.n_layers - 1].act = mc.ACT[a['final_act']]
+    n = c['n']
+    whole, view = nan_buffer(n, 1, cuda, G_OUT)
+    args = lambda d, rays, n_iter: (ctypes.byref(d), pk.w.data_ptr(), pk.b.data_ptr(), dev['origin'].data_ptr(), dev['direction'].data_ptr(),
+                                    dev['bracket'].data_ptr(), rays, float(inp['tau']), n_iter, c['octaves'], float(c['pe_scale']),
+                                    view.data_ptr(), hip._stream())
+    assert hip._lib.psn_root_find(*args(pk.desc, 0, 8)) == 0
+    path = hip.PsnMlpPath()
+    with pytest.raises(RuntimeError, match=re.escape(a['refusal'])):
+        hip.root_find(desc, pk.w, pk.b, dev['origin'], dev['direction'], dev['bracket'], inp['tau'], a.get('n_iter', 8), c['octaves'],
+                      c['pe_scale'], out=view.reshape(-1), path=path)
+    hip._last_path(path)
+    torch.cuda.synchronize()
+    assert path.blocks == 0 and untouched(whole)
+
+
+def test_root_finder_on_no_rays(mods, cuda):
+    """n_rays = 0: PSN_OK, nothing launched, psn_mlp_last_path answers zeros (not the launch before), the output untouched; through
+    the wrapper an empty result and a zeroed path."""
+    import ctypes
+    hip, _ = mods
+    c, net, inp, pk, dev = _root_arg_setup(mods, cuda)
+    n = c['n']
+    whole, view = nan_buffer(n, 1, cuda, G_OUT)
+    path = hip.PsnMlpPath()
+    hip.root_find(pk.desc, pk.w, pk.b, dev['origin'], dev['direction'], dev['bracket'], inp['tau'], 1, c['octaves'], c['pe_scale'], path=path)
+    assert path.blocks == (n + 15) // 16 and path.src == mc.SRC_ROOT
+    rc = hip._lib.psn_root_find(ctypes.byref(pk.desc), pk.w.data_ptr(), pk.b.data_ptr(), dev['origin'].data_ptr(), dev['direction'].data_ptr(),
+                                dev['bracket'].data_ptr(), 0, float(inp['tau']), 8, c['octaves'], float(c['pe_scale']), view.data_ptr(),
+                                hip._stream())
+    hip._last_path(path)
+    torch.cuda.synchronize()
+    assert rc == 0 and untouched(whole)
+    assert (path.blocks, path.chain, path.width16, path.src, path.trim, path.from_a, path.x3) == (0, 0, 0, 0, 0, 0, 0)
+    path.blocks = 7
+    out = hip.root_find(pk.desc, pk.w, pk.b, dev['origin'][:0], dev['direction'][:0], dev['bracket'][:, :0].contiguous(), inp['tau'], 8,
+                        c['octaves'], c['pe_scale'], path=path)
+    assert out.shape == (0,) and path.blocks == 0
 
 
 # --------------------------------------------------------------------------- argument checks

@@ -2,7 +2,10 @@
 dispatcher's table (recomputed from a pure-Python copy of its conditions) and straddle every kernel's grid cap; the float32
 reference arithmetic stays inside the cap that keeps the GPU test's allowance from hiding a failure (measured ratios printed);
 deliberately wrong formulations are rejected by the GPU test's own bound; the constructed crossing profiles give what their
-construction says; and the forced sample depths do reach the sort."""
+construction says; and the forced sample depths do reach the sort.  The per-ray kernels' float32 definitions (secant step,
+stage-1 rays) stay within half the float64 bound, their edge inputs give what the construction says (f_mid == 0 moves the high end,
+under == 0 is a miss, x = w is the last pixel, exact ties round half to even, a coordinate of +-box is inside), and the wrong forms
+-- the y axis over fy, the strict box test, floor(x + 0.5) for rint -- are rejected.  78 tests, 40 s (the composite references)."""
 import numpy as np
 import pytest
 import torch
@@ -233,3 +236,125 @@ def test_sample_cases_reach_the_sort(c0, c1, N, noise):
         assert bool((d[:, 1:] >= d[:, :-1]).all())
     ref = rc.sample_reference(case, c0, c1, case['flags']['mixed'])
     assert ref.shape == (N, c0 + c1, 3) and bool(torch.isfinite(ref).all())
+
+
+# ================================================================================= the per-ray kernels around the root finder
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=np.float32).view(np.int32)
+
+
+@pytest.mark.parametrize('n', rc.PR_N)
+def test_secant_step_definition_and_its_edge_rays(n):
+    """float32 against float64 on the regular rays over the initial step and three updates (d_pred and p_mid, ATOL_UNIT: within
+    half the bound); f_mid == 0 moves the HIGH end; d_low == d_high stays where it is; f_low == f_high gives inf or NaN."""
+    c = rc.secant_case(n, 0.5 if n % 2 else 0.3)
+    reg = np.ones(n, dtype=bool)
+    if n >= 8:
+        reg[[3, 4]] = False
+    st32 = st64 = {k: c[k] for k in ('d_low', 'd_high', 'f_low', 'f_high')}
+    d32 = d64 = None
+    for step in range(4):
+        occ = None if step == 0 else c['occ'][step - 1]
+        before = st32
+        st32, d32, p32 = rc.secant_step_definition(st32, occ, c['tau'], d32, c['origin'], c['direction'])
+        st64, d64, p64 = rc.secant_step_definition(st64, occ, c['tau'], d64, c['origin'], c['direction'], np.float64)
+        for name, a, t in (('d_pred', d32[reg], d64[reg]), ('p_mid', p32[reg], p64[reg])):
+            _, r_ref, _, _, _ = truth_ratios(a, a, t, rc.RTOL, rc.ATOL_UNIT)
+            assert float(r_ref.max()) <= 0.5, (n, step, name, float(r_ref.max()))
+        if n >= 8 and step > 0:
+            assert st32['d_high'][2] == before_d[2] and st32['f_high'][2] == 0 and st32['d_low'][2] == before['d_low'][2]
+        if n >= 8:
+            assert d32[3] == c['d_low'][3] and not np.isfinite(d32[4]) and (step > 0 or np.isinf(d32[4]))
+            assert d32[5] == (0.5 if step == 0 else d32[5])
+        before_d = d32
+    assert np.isfinite(d32[reg]).all()
+
+
+@pytest.mark.parametrize('scene', rc.RAY_SCENES)
+@pytest.mark.parametrize('n', rc.PR_N)
+def test_stage1_rays_definition_within_half_the_bound_and_fy_rejected(n, scene):
+    pix, K, W, radius = rc.rays_case(n, scene)
+    c32, d32, f32, u32 = rc.stage1_rays_definition(pix, K, W, radius)
+    c64, d64, f64, u64 = rc.stage1_rays_definition(pix, K, W, radius, np.float64)
+    assert (np.abs(u64) >= rc.RAY_UNDER_MIN).all() and np.array_equal(u32 > 0, u64 > 0) and np.array_equal(_bits(c32), _bits(c64))
+    for name, a, t, atol in (('rays', d32, d64, rc.ATOL_UNIT), ('far', f32, f64, 'max')):
+        _, r_ref, _, n_allowed, _ = truth_ratios(a, a, t, rc.RTOL, atol)
+        assert n_allowed == 0 and float(r_ref.max()) <= 0.5, (name, float(r_ref.max()))
+    if n > 1:
+        assert {'outside': 0 < (f32 == 0).sum() < n, 'inside': (f32 > 0).all(), 'behind': (f32 == 0).all() and (u32 > 0).any()}[scene]
+    # both axes over fy instead of fx: rejected by the bound on the directions
+    bad = rc.stage1_rays_definition(pix, K, W, radius, wrong='fy')
+    with pytest.raises(AssertionError):
+        assert_vs_truth('rays fy', bad[1], d32, d64, rc.RTOL, rc.ATOL_UNIT)
+    # a 3 x 3 camera matrix is the same definition
+    assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(rc.stage1_rays_definition(pix, K[:3, :3], W, radius), (c32, d32, f32, u32)))
+
+
+def test_stage1_rays_explicit_sign_of_under():
+    K = np.eye(4, dtype=np.float32)
+    K[0, 0], K[1, 1], K[0, 2], K[1, 2] = 70.0, 66.0, 31.5, 23.25
+    for cam, r2, far in rc.RAY_UNDER_EXPLICIT:
+        W = np.eye(4, dtype=np.float32)
+        W[:3, 3] = cam
+        c, d, f, under = rc.stage1_rays_definition(np.array([[31.5, 23.25]], dtype=np.float32), K, W, np.sqrt(np.float64(r2)))
+        assert d.tolist() == [[0.0, 0.0, 1.0]] and under[0] == np.float32(r2) - (np.float32(np.dot(cam, cam)) - np.float32(cam[2]) ** 2)
+        assert f[0] == (far if far is not None else np.sqrt(under[0])) and (far is not None or f[0] > 0)
+
+
+@pytest.mark.parametrize('n', rc.PR_N)
+def test_surface_points_definition_table(n):
+    d_pred, flags, cam, rays = rc.surface_case(n)
+    d_i, dists, obj, pts = rc.surface_points_definition(d_pred, flags, cam, rays)
+    if n >= 16:
+        # flags 3 (crossing, starts free): the depth; flags 2 (no crossing): inf -> dist 1, no object; bit 1 clear: 0 -> dist 0
+        want = {(3, 0): (0.75, 0.75, True), (3, 1): (0.0, 0.0, False), (3, 2): (np.inf, 1.0, False), (2, 0): (np.inf, 1.0, False),
+                (1, 0): (0.0, 0.0, False), (0, 3): (0.0, 0.0, False)}
+        for (f, v), (di, dist, o) in want.items():
+            i = 4 * f + v
+            assert (d_i[i], dists[i], bool(obj[i])) == (di, dist, o), (f, v)
+        assert np.isnan(d_i[15]) and dists[15] == 1.0 and not obj[15]
+    assert np.array_equal(pts, cam + rays * dists[:, None]) and 0 < obj.sum() + (n > 1) <= n
+
+
+@pytest.mark.parametrize('h,w', rc.TG_SIZES)
+def test_targets_definition_ties_bounds_and_wrong_rounding(h, w):
+    c = rc.targets_case(h, w, 257)
+    iy, ix, inside, fx, fy = rc.nearest_index(c['pix'], h, w)
+    pix = c['pix']
+    # x = w and y = h are the last pixel (2 w / w - 1 = 1 with align_corners=True); x = -1 (from three columns on), w + 1, h + 1 and
+    # (w + 5, -3) are outside: zeros.  An image of one column (row) has fx = x * 0: every x (y) is inside.
+    assert inside[[0, 1, 3, 4]].all() and (iy[1], ix[1]) == (h - 1, w - 1) and ix[3] == w - 1 and iy[4] == h - 1
+    rgb = rc.targets_definition(c)[0]
+    assert np.array_equal(rgb[1], c['img'][:, h - 1, w - 1]) and np.array_equal(rgb[3], c['img'][:, 0, w - 1])
+    out = [k for k, on in ((2, w >= 3), (5, w >= 2 or h >= 2), (12, w >= 2), (13, h >= 2)) if on]
+    assert not inside[out].any() and (rgb[out] == 0).all() and ((h, w) == (1, 1) or len(out) >= 2)
+    # the exact ties of even sizes: fx = (w - 1) / 2 exactly, rounded half to even
+    if w % 2 == 0:
+        assert fx[6] == (w - 1) / 2.0 and ix[6] == 2 * round((w - 1) / 4.0)
+    if h % 2 == 0:
+        assert fy[7] == (h - 1) / 2.0 and iy[7] == 2 * round((h - 1) / 4.0)
+    bad = rc.targets_definition(c, wrong='floor')[0]
+    if (h, w) == (6, 8):      # 2.5 -> 2 (rint) but 3 (floor(x + 0.5)): the wrong rounding reads another pixel
+        assert iy[7] == 2 and not np.array_equal(bad, rgb)
+    # the angle mask: n2 == cos exactly is kept, one ulp below is dropped
+    full = rc.targets_definition(c, want_normal=True, use_angle=True)
+    plain = rc.targets_definition(c, want_normal=True, use_angle=False)
+    assert full[3][0] and plain[3][0] and plain[3][1] and (not full[3][1] or (h, w) == (1, 1))
+    assert np.array_equal(full[4], plain[4]) and full[4].dtype == np.float32
+
+
+@pytest.mark.parametrize('case', rc.SH_CASES, ids=lambda c: 'ns%d-nl%d-S%d-%s' % (c[0], c[1], c[2], c[5]))
+def test_shadow_definition_counts_and_strict_box_rejected(case):
+    ns, nl, S, lnear, box, kind = case
+    surf, ldir, u, omu = rc.shadow_case(*case)
+    rows, pts = rc.shadow_points_definition(surf, ldir, u, omu, lnear, rc.SH_LFAR, box)
+    total = ns * nl * S
+    assert total % 64 != 0 or total == 0
+    assert {'random': 0 < len(rows) < total or total <= 1, 'all': len(rows) == total, 'none': len(rows) == 0,
+            'edge': 0 < len(rows) < total}[kind]
+    if kind == 'edge':
+        # step 0 of light 0: the point is the surface point; +-box inside, one ulp beyond outside
+        first = [(0 * ns + s) * S for s in range(8)]
+        assert [r in rows for r in first] == [True, True, True, False, False, False, True, False]
+        srows, _ = rc.shadow_points_definition(surf, ldir, u, omu, lnear, rc.SH_LFAR, box, strict=True)
+        assert len(srows) < len(rows) and not any(r in srows for r in first)
