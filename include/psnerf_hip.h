@@ -1095,6 +1095,51 @@ int psn_img_metrics(const void* pred, const void* gt, int image_type, const unsi
 int psn_normal_mae(const float* pred, const float* gt, const unsigned char* mask, int mask_batch, int normalize, int B, int64_t n_pixels,
                    double* partial, double* sums, double* err_map, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Calibrated photometric stereo: one view's images under L known directional lights -> the normal map of the stage-1 normal loss, the
+ * per-light intensities and light_avg.py's light-averaged image (csrc/photostereo.hip; the float64 numpy definition, with every step
+ * and operation order, is psnerf_amd/photostereo.py:host_*).  float64 arithmetic in the definition's order; no floating-point atomics.
+ *   images     [L, n_pixels, 3], PSN_IMG_U8 (a byte u is the double u / 255.0) or PSN_IMG_F32 (converted exactly);
+ *              PSN_PS_MIN_LIGHTS <= L <= PSN_PS_MAX_LIGHTS, 1 <= n_pixels <= PSN_PS_MAX_PIXELS.
+ *   mask       bytes (0 / non-0) [n_pixels], or null = every pixel.
+ *   light_dir  double [L, 3], used as given (not normalised).
+ *
+ * psn_ps_normals: light_int null, or double [L, 3], the divisor per light and channel.  Per masked pixel: g[l] = (v0 + v1) + v2 with
+ *   v = I / light_int; a light is lit if g > dark; the lit lights are ranked by g ascending, ties by light index, and light i is kept
+ *   if floor(low n_lit) <= rank[i] < n_lit - floor(high n_lit); A = sum l l^T and b = sum l g over the kept lights in index order;
+ *   m = adj(A) b; valid if kept >= min_lights, det A > cond t^3 (t = trace A / 3) and |m| > 0; normal = m / |m|; albedo [c] =
+ *   sum v[l, c] s[l] / sum s[l]^2, s = max(n . l, 0) over the kept lights.  Outputs, written for every pixel: normal / albedo double
+ *   [n_pixels, 3], valid bytes [n_pixels], kept int32 [n_pixels] (the kept count of a masked pixel); an invalid or unmasked pixel gets
+ *   zeros.  They equal the definition bit for bit on either path: PSN_PS_PATH_TILE keeps the wave's g tile in LDS
+ *   (L <= PSN_PS_TILE_LIGHTS), PSN_PS_PATH_REFORM re-forms g from the images (any L), PSN_PS_PATH_AUTO picks TILE where it fits.
+ * psn_ps_light_intensity: intensity [L, 3] = sum_p I m / sum_p m^2 with m = albedo [p, c] max(n_p . l, 0) over the pixels with a
+ *   non-0 valid byte whose I [l, p, c] lies in the open interval (dark, bright); 0 where the denominator is 0.  sums [L, 6] = the three
+ *   numerators and the three denominators.  Each workgroup writes one row of six partial sums into ``partial`` (psn_ps_workspace
+ *   doubles; every row on every call) and a second, fixed-order step adds them: two calls on the same input give the same bits.
+ * psn_ps_light_average: light_avg.py:58-67.  limg [l] = I * mask, divided by relat_int [l, c] (double [L, 3]) unless that is null;
+ *   mean double [n_pixels, 3] = the sequential sum over l divided by L; mean_u8 = round-half-even(clip(mean, 0, 1) * 255); norm_u8
+ *   null, or bytes [L, n_pixels, 3] = the same rounding of every limg [l].
+ * psn_ps_workspace: the doubles ``partial`` must hold for (L, n_pixels); -1 on a bad argument.
+ * Errors: PSN_E_ARG for null pointers, L or n_pixels out of range, an unknown image_type or path, PSN_PS_PATH_TILE with
+ *   L > PSN_PS_TILE_LIGHTS, low or high outside [0, 1) or low + high >= 1, min_lights < PSN_PS_MIN_LIGHTS; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_PS_MAX_LIGHTS 256
+#define PSN_PS_MIN_LIGHTS 3
+#define PSN_PS_TILE_LIGHTS 96
+#define PSN_PS_MAX_PIXELS 1073741824
+#define PSN_PS_PATH_AUTO 0
+#define PSN_PS_PATH_TILE 1
+#define PSN_PS_PATH_REFORM 2
+int64_t psn_ps_workspace(int L, int64_t n_pixels);
+int psn_ps_normals(const void* images, int image_type, const unsigned char* mask, const double* light_dir, const double* light_int, int L,
+                   int64_t n_pixels, double low, double high, double dark, int min_lights, double cond, int path, double* normal,
+                   double* albedo, unsigned char* valid, int32_t* kept, void* stream);
+int psn_ps_light_intensity(const void* images, int image_type, const double* normal, const double* albedo, const unsigned char* valid,
+                           const double* light_dir, int L, int64_t n_pixels, double dark, double bright, double* partial, double* sums,
+                           double* intensity, void* stream);
+int psn_ps_light_average(const void* images, int image_type, const unsigned char* mask, const double* relat_int, int L, int64_t n_pixels,
+                         double* mean, unsigned char* mean_u8, unsigned char* norm_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1899,3 +1899,92 @@ def normal_mae(pred, gt, mask, normalize=True, full=False):
         _check(_lib.psn_normal_mae(pred.data_ptr(), gt.data_ptr(), mp, mb, int(bool(normalize)), B, N, partial.data_ptr(), sums.data_ptr(),
                                    None if err is None else err.data_ptr(), _stream()), 'normal_mae')
     return sums, partial, err
+
+
+# --------------------------------------------------------------------------- photometric stereo (csrc/photostereo.hip)
+PS_PATHS = {'auto': PS_PATH_AUTO, 'tile': PS_PATH_TILE, 'reform': PS_PATH_REFORM}  # noqa: F821
+
+
+def _ps_images(what, images, mask):
+    """The checks every photometric-stereo entry shares -> (image_type, mask pointer or None, L, n_pixels)."""
+    _tptr(images, '%s: images' % what, tuple(IMG_TYPES))
+    if images.dim() != 3 or images.shape[2] != 3:
+        raise RuntimeError('%s: images [L, n_pixels, 3] expected, got %s' % (what, tuple(images.shape)))
+    L, N = int(images.shape[0]), int(images.shape[1])
+    if not PS_MIN_LIGHTS <= L <= PS_MAX_LIGHTS or N < 1:  # noqa: F821
+        raise RuntimeError('%s: %d lights (%d .. %d) of %d pixels (at least one)' % (what, L, PS_MIN_LIGHTS, PS_MAX_LIGHTS, N))  # noqa: F821
+    mp = _tptr(mask, '%s: mask' % what, (torch.uint8, torch.bool), allow_none=True)
+    if mask is not None and (tuple(mask.shape) != (N,) or mask.device != images.device):
+        raise RuntimeError('%s: mask [%d] on the images\' device expected, got %s' % (what, N, tuple(mask.shape)))
+    return IMG_TYPES[images.dtype], mp, L, N
+
+
+def _ps_table(what, name, t, L, device, allow_none=False):
+    """A float64 [L, 3] device table (light directions, intensities) -> pointer or None."""
+    ptr = _tptr(t, '%s: %s' % (what, name), torch.float64, allow_none=allow_none)
+    if t is not None and (tuple(t.shape) != (L, 3) or t.device != device):
+        raise RuntimeError('%s: %s [%d, 3] on the images\' device expected, got %s' % (what, name, L, tuple(t.shape)))
+    return ptr
+
+
+def ps_normals(images, mask, light_dir, light_int=None, low=0.1, high=0.25, dark=0.0, min_lights=3, cond=1e-4, path='auto', out=None):
+    """psn_ps_normals: images [L, N, 3] (uint8 or float32), mask [N] (uint8 / bool) or None, light_dir float64 [L, 3], light_int float64
+    [L, 3] or None -> (normal float64 [N, 3], albedo float64 [N, 3], valid uint8 [N], kept int32 [N]); ``out``: the four, preallocated."""
+    ty, mp, L, N = _ps_images('ps_normals', images, mask)
+    dev = images.device
+    if path not in PS_PATHS:
+        raise RuntimeError('ps_normals: path %r (auto, tile, reform)' % (path,))
+    o = out if out is not None else (None, None, None, None)
+    normal = _out(o[0], (N, 3), images, 'ps_normals: normal', torch.float64)
+    albedo = _out(o[1], (N, 3), images, 'ps_normals: albedo', torch.float64)
+    valid = _out(o[2], (N,), images, 'ps_normals: valid', torch.uint8)
+    kept = _out(o[3], (N,), images, 'ps_normals: kept', torch.int32)
+    with _Prof('ps_normals', L * N * 3 * images.element_size()):
+        _check(_lib.psn_ps_normals(images.data_ptr(), ty, mp, _ps_table('ps_normals', 'light_dir', light_dir, L, dev),
+                                   _ps_table('ps_normals', 'light_int', light_int, L, dev, allow_none=True), L, N, float(low), float(high),
+                                   float(dark), int(min_lights), float(cond), PS_PATHS[path], normal.data_ptr(), albedo.data_ptr(),
+                                   valid.data_ptr(), kept.data_ptr(), _stream()), 'ps_normals')
+    return normal, albedo, valid, kept
+
+
+def ps_light_intensity(images, normal, albedo, valid, light_dir, dark=0.0, bright=1.0, out=None):
+    """psn_ps_light_intensity: images [L, N, 3], normal / albedo float64 [N, 3], valid [N] (uint8 / bool), light_dir float64 [L, 3] ->
+    (intensity float64 [L, 3], sums float64 [L, 6], partial rows); ``out``: (intensity, sums), preallocated."""
+    ty, vp, L, N = _ps_images('ps_light_intensity', images, valid)
+    dev = images.device
+    if valid is None:
+        raise RuntimeError('ps_light_intensity: valid: tensor required')
+    for name, t in (('normal', normal), ('albedo', albedo)):
+        _tptr(t, 'ps_light_intensity: %s' % name, torch.float64)
+        if tuple(t.shape) != (N, 3) or t.device != dev:
+            raise RuntimeError('ps_light_intensity: %s [%d, 3] on the images\' device expected, got %s' % (name, N, tuple(t.shape)))
+    n = int(_lib.psn_ps_workspace(L, N))
+    if n < 0:
+        raise RuntimeError('psn_ps_workspace(%d, %d) refused' % (L, N))
+    partial = torch.empty(n, dtype=torch.float64, device=dev)
+    o = out if out is not None else (None, None)
+    intensity = _out(o[0], (L, 3), images, 'ps_light_intensity: intensity', torch.float64)
+    sums = _out(o[1], (L, 6), images, 'ps_light_intensity: sums', torch.float64)
+    with _Prof('ps_light_intensity', L * N * (3 * images.element_size() + 49)):
+        _check(_lib.psn_ps_light_intensity(images.data_ptr(), ty, normal.data_ptr(), albedo.data_ptr(), vp,
+                                           _ps_table('ps_light_intensity', 'light_dir', light_dir, L, dev), L, N, float(dark), float(bright),
+                                           partial.data_ptr(), sums.data_ptr(), intensity.data_ptr(), _stream()), 'ps_light_intensity')
+    return intensity, sums, partial
+
+
+def ps_light_average(images, mask, relat_int=None, normalised=None, out=None):
+    """psn_ps_light_average: images [L, N, 3], mask [N] or None, relat_int float64 [L, 3] or None -> (mean float64 [N, 3], mean_u8 [N, 3],
+    the normalised images uint8 [L, N, 3] or None); ``normalised``: whether to write those (default: when relat_int is given); ``out``:
+    (mean, mean_u8, normalised images or None), preallocated."""
+    ty, mp, L, N = _ps_images('ps_light_average', images, mask)
+    dev = images.device
+    o = out if out is not None else (None, None, None)
+    mean = _out(o[0], (N, 3), images, 'ps_light_average: mean', torch.float64)
+    mean_u8 = _out(o[1], (N, 3), images, 'ps_light_average: mean_u8', torch.uint8)
+    want = (relat_int is not None) if normalised is None else bool(normalised)
+    norm = _out(o[2], (L, N, 3), images, 'ps_light_average: normalised images', torch.uint8) if want else None
+    with _Prof('ps_light_average', L * N * 3 * images.element_size() * (2 if want else 1)):
+        _check(_lib.psn_ps_light_average(images.data_ptr(), ty, mp, _ps_table('ps_light_average', 'relat_int', relat_int, L, dev, allow_none=True),
+                                         L, N, mean.data_ptr(), mean_u8.data_ptr(), None if norm is None else norm.data_ptr(), _stream()),
+               'ps_light_average')
+    return mean, mean_u8, norm

@@ -87,6 +87,10 @@ def _main():
     ap.add_argument('--shipped-steps', type=int, default=0,
                     help='second stage-2 leg at the shipped shapes (light_bs 10, all in-mask pixels): iterations run with the REAL train_fix '
                          'schedule from iteration 0 (>= 5000 to cross the switch); 0 = skip')
+    ap.add_argument('--ps-normals', action='store_true',
+                    help='stage 1 with the normal regularisation on (training.normal_loss): per-view normal maps by calibrated photometric stereo '
+                         '(psnerf_amd.photostereo, csrc/photostereo.hip) from the rendered images and the known light directions; the normal '
+                         'term starts halfway through the stage-1 steps.  Default: off, the run as it always was')
     ap.add_argument('--json-out', default=None, help='also write the JSON line to this file')
     ap.add_argument('--backend', default=None, help='torch.distributed backend under torchrun (default nccl = RCCL; gloo for dry runs on one GPU)')
     ap.add_argument('--single-device', action='store_true', help='dry run: every rank uses cuda:0')
@@ -132,6 +136,8 @@ def _main():
     # ------------------------------------------------------------------ scene
     x3 = args.precision == 'bf16x3'
     cfg = stage1_cfg('bunny', **{'training.n_training_points': args.rays, 'training.normal_loss': False,
+                                 **({'training.normal_loss': True, 'training.est_norm': True,
+                                     'training.normal_after': args.s1_it0 + args.s1_steps // 2} if args.ps_normals else {}),
                                  **({'training.chain_precision': 'bf16x3', 'training.wgrad_precision': 'bf16x3'} if x3 else {}),
                                  **({'rendering.num_points_in': 96, 'rendering.num_points_out': 32} if args.full else {})})
     K, _, S = stage1_camera(cfg, h=h, w=w)
@@ -159,6 +165,29 @@ def _main():
         mean_img = torch.where(omasks[v].reshape(1, 1, h, w), mean_img, torch.ones_like(mean_img))  # white background
         batches.append({'img': mean_img.to(dev), 'img.mask': omasks[v].reshape(1, h, w).float().to(dev),
                         'img.world_mat': poses[v][None].to(dev), 'img.camera_mat': K.to(dev), 'img.scale_mat': S.to(dev)})
+    ps_report = None
+    if args.ps_normals:
+        # the calibrated lights in each view's OpenGL camera frame (what params.json: light_direction holds, and the frame of img.normal:
+        # the trainer maps a normal to the world by R diag(1, -1, -1)), the 8-bit images as the PNGs hold them
+        from psnerf_amd import photostereo
+        flip = torch.tensor([1.0, -1.0, -1.0])
+        mae, frac = [], []
+        torch.cuda.synchronize()
+        t0 = time.time()
+        for v in range(args.views):
+            to_cam = lambda x: (x @ poses[v][:3, :3]) * flip
+            u8 = torch.from_numpy(np.rint(images[v].numpy() * 255.0).astype(np.uint8)).reshape(args.lights, h, w, 3).to(dev)
+            res = photostereo.estimate(u8, omasks[v].reshape(h, w).to(dev), to_cam(lights[v]).double().to(dev))
+            maps = photostereo.stage1_normals(res)
+            batches[v]['img.normal'], batches[v]['img.norm_mask'] = maps['img.normal'][None], maps['img.norm_mask'][None]
+            ok = (res['valid'] != 0).reshape(-1).cpu()
+            cosn = (res['normal'].reshape(-1, 3).cpu().float()[ok] * to_cam(gt_normals[v])[ok]).sum(-1).clamp(-1, 1)
+            mae.append(float(torch.rad2deg(torch.acos(cosn)).mean()) if ok.any() else float('nan'))
+            frac.append(float(ok.sum()) / max(int(omasks[v].sum()), 1))
+        torch.cuda.synchronize()
+        assert min(frac) > 0.5, ('photometric stereo: too few valid pixels', frac)
+        ps_report = {'normal_mae_deg_vs_analytic_sphere': [round(x, 3) for x in mae], 'valid_fraction_of_mask': [round(x, 3) for x in frac],
+                     'normal_after': cfg['training']['normal_after'], 'seconds': round(time.time() - t0, 3)}
     s1_losses = []
     if x3:
         net1.inference_precision = 'bf16x3'   # the ray-march sweep of the training steps
@@ -417,7 +446,7 @@ def _main():
         line = json.dumps({
             'e2e': 'ok', 'n_gpus': world, 'image': [h, w], 'views': args.views, 'lights_per_view': args.lights,
             'surface_pixels': n_surf, 'stage1': {'steps': args.s1_steps, 'loss_first': s1_losses[0], 'loss_last': s1_losses[-1],
-                                                 'seconds': round(t_s1, 2)},
+                                                 'seconds': round(t_s1, 2), 'ps_normals': ps_report},
             'precision': args.precision, 'shape_extract_seconds': round(t_extract, 2), 'handoff_dir': out_dir, 'occ_bf16x6': occ_cmp,
             'stage2_graph': rep2.get('graph'),
             'stage2': dict(rep2, switch_at=switch), 'stage2_shipped_shapes': shipped, 'host_sampler_probe': host_probe,
