@@ -1140,6 +1140,41 @@ int psn_ps_light_intensity(const void* images, int image_type, const double* nor
 int psn_ps_light_average(const void* images, int image_type, const unsigned char* mask, const double* relat_int, int L, int64_t n_pixels,
                          double* mean, unsigned char* mean_u8, unsigned char* norm_u8, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Baking a per-point field onto a mesh: the texel <-> surface maps of the two-faces-per-cell atlas (csrc/meshbake.hip; the numpy
+ * definition, which is THE definition, is psnerf_amd/meshbake.py: Atlas, host_atlas_points, host_atlas_scatter, host_atlas_sample).
+ * The atlas (T, cell, n_faces): a T x T texture of G = T / cell cells per side, PSN_ATLAS_MIN_CELL <= cell <= T <= PSN_ATLAS_MAX_SIZE,
+ * G * G >= ceil(n_faces / 2); n = cell - 3, K = (n + 2)(n + 3) / 2 rows per face.  Face f: cell q = f / 2 with origin ((q % G) cell,
+ * (q / G) cell), half f % 2; local texel (i, j), i + j <= n + 1, is texel (X0 + i, Y0 + j) in half 0 and (X0 + cell - 1 - i,
+ * Y0 + cell - 1 - j) in half 1 (x = column, y = row of the array); its row is f K + j (n + 2) - j (j - 1) / 2 + i.  Corners: (0, 0),
+ * (n, 0), (0, n).  All float64 arithmetic is the definition's, in its order: every output equals the definition bit for bit.
+ *
+ * psn_atlas_points: vertices double [V, 3], faces int64 [F, 3], vertex_normals null or double [V, 3]; for the rows of the faces
+ *   f0 <= f < f1: points double [(f1 - f0) K, 3] = (v0 + (i / n) e1) + (j / n) e2 (gutter rows continue the plane beyond the
+ *   hypotenuse, unclamped), points_f32 = the same rounded once to float, normals double = normalise((b0 n0 + b1 n1) + b2 n2) with
+ *   b = (1 - (i + j) / n, i / n, j / n), or normalise(e1 x e2) without vertex normals; a zero vector stays zero.  A face with a
+ *   vertex index outside 0 .. V - 1 gives NaN rows.
+ * psn_atlas_scatter: rows float [(f1 - f0) K, C] -> the texels of the faces f0 <= f < f1 of texture [T, T, C], PSN_IMG_F32 (copied) or
+ *   PSN_IMG_U8 (in float: clip to [0, 1], x 255, round half to even; NaN -> 0).  No other texel is written.
+ * psn_atlas_fill: every texel that NO face owns (cell diagonals, the free half of a last cell, free cells, the margin beyond G cell)
+ *   := fill (through the same rule for PSN_IMG_U8); owned texels are left alone.
+ * psn_atlas_sample: face int64 [Q], bary double [Q, 3] in the corner order of psn_ray_cast, texture float [T, T, C] -> out double
+ *   [Q, C]: (x, y) = (b0 (x0, y0) + b1 (x1, y1)) + b2 (x2, y2) over the corner texels; x0 = clamp(floor x, 0, T - 1), x1 = min(x0 + 1,
+ *   T - 1), fx = x - floor x, likewise y; out = (1 - fy)((1 - fx) t00 + fx t10) + fy ((1 - fx) t01 + fx t11) in double.  A face
+ *   outside 0 .. n_faces - 1 (a miss is -1) or a position that is not finite gives a NaN row.
+ * Errors: PSN_E_ARG for null pointers, sizes, channel counts or face ranges out of range, an unknown texture_type; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_ATLAS_MIN_CELL 4
+#define PSN_ATLAS_MAX_SIZE 32768
+#define PSN_ATLAS_MAX_CHANNELS 32
+int psn_atlas_points(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, const double* vertex_normals, int T,
+                     int cell, int64_t f0, int64_t f1, double* points, float* points_f32, double* normals, void* stream);
+int psn_atlas_scatter(const float* rows, int C, int T, int cell, int64_t n_faces, int64_t f0, int64_t f1, void* texture, int texture_type,
+                      void* stream);
+int psn_atlas_fill(float fill, int C, int T, int cell, int64_t n_faces, void* texture, int texture_type, void* stream);
+int psn_atlas_sample(const int64_t* face, const double* bary, int64_t n_queries, const float* texture, int C, int T, int cell,
+                     int64_t n_faces, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1988,3 +1988,82 @@ def ps_light_average(images, mask, relat_int=None, normalised=None, out=None):
                                          L, N, mean.data_ptr(), mean_u8.data_ptr(), None if norm is None else norm.data_ptr(), _stream()),
                'ps_light_average')
     return mean, mean_u8, norm
+
+
+# --------------------------------------------------------------------------- texture atlas of a mesh (csrc/meshbake.hip)
+def _atlas_texture(what, tex, T):
+    """A [T, T, C] float32 or uint8 device texture -> (pointer, C, texture type)."""
+    ptr = _tptr(tex, '%s: texture' % what, tuple(IMG_TYPES))
+    if tex.dim() != 3 or tex.shape[0] != T or tex.shape[1] != T or not 1 <= tex.shape[2] <= ATLAS_MAX_CHANNELS:  # noqa: F821
+        raise RuntimeError('%s: texture [%d, %d, 1 .. %d] expected, got %s' % (what, T, T, ATLAS_MAX_CHANNELS, tuple(tex.shape)))  # noqa: F821
+    return ptr, int(tex.shape[2]), IMG_TYPES[tex.dtype]
+
+
+def atlas_points(vertices, faces, vertex_normals, T, cell, f0=0, f1=None, out=None):
+    """psn_atlas_points: vertices float64 [V, 3], faces int64 [F, 3], vertex_normals float64 [V, 3] or None; the rows of the faces
+    f0 <= f < f1 -> (points float64 [R, 3], points_f32 float32 [R, 3], normals float64 [R, 3]), R = (f1 - f0) K; ``out``: the three,
+    preallocated."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    f1 = F if f1 is None else int(f1)
+    f0 = int(f0)
+    np_ = _tptr(vertex_normals, 'atlas_points: vertex_normals', torch.float64, allow_none=True)
+    if vertex_normals is not None and (tuple(vertex_normals.shape) != (V, 3) or vertex_normals.device != vertices.device):
+        raise RuntimeError('atlas_points: vertex_normals [%d, 3] on the mesh\'s device expected, got %s' % (V, tuple(vertex_normals.shape)))
+    if not (cell >= ATLAS_MIN_CELL and 0 <= f0 <= f1 <= F):  # noqa: F821
+        raise RuntimeError('atlas_points: cell %d (at least %d), face range [%d, %d) of %d faces' % (cell, ATLAS_MIN_CELL, f0, f1, F))  # noqa: F821
+    R = (f1 - f0) * ((cell - 1) * cell // 2)
+    o = out if out is not None else (None, None, None)
+    points = _out(o[0], (R, 3), vertices, 'atlas_points: points', torch.float64)
+    points_f32 = _out(o[1], (R, 3), vertices, 'atlas_points: points_f32', torch.float32)
+    normals = _out(o[2], (R, 3), vertices, 'atlas_points: normals', torch.float64)
+    with _Prof('atlas_points', R):
+        _check(_lib.psn_atlas_points(vp, V, fp, F, np_, int(T), int(cell), f0, f1, _eptr(points, vertices), _eptr(points_f32, vertices),
+                                     _eptr(normals, vertices), _stream()), 'atlas_points')
+    return points, points_f32, normals
+
+
+def atlas_scatter(rows, texture, cell, n_faces, f0=0, f1=None):
+    """psn_atlas_scatter: rows float32 [(f1 - f0) K, C] -> the texels of the faces f0 <= f < f1 of ``texture`` [T, T, C] (float32, or
+    uint8 by the to_img rule), in place; no other texel is written."""
+    T = int(texture.shape[0])
+    tp, C, ty = _atlas_texture('atlas_scatter', texture, T)
+    f1 = int(n_faces) if f1 is None else int(f1)
+    f0 = int(f0)
+    if not (cell >= ATLAS_MIN_CELL and 0 <= f0 <= f1 <= n_faces):  # noqa: F821
+        raise RuntimeError('atlas_scatter: cell %d (at least %d), face range [%d, %d) of %d faces' % (cell, ATLAS_MIN_CELL, f0, f1, n_faces))  # noqa: F821
+    R = (f1 - f0) * ((cell - 1) * cell // 2)
+    _tptr(rows, 'atlas_scatter: rows')
+    if tuple(rows.shape) != (R, C) or rows.device != texture.device:
+        raise RuntimeError('atlas_scatter: rows [%d, %d] on the texture\'s device expected, got %s' % (R, C, tuple(rows.shape)))
+    with _Prof('atlas_scatter', R * C * 4 + R * C * texture.element_size()):
+        _check(_lib.psn_atlas_scatter(_eptr(rows, texture), C, T, int(cell), int(n_faces), f0, f1, tp, ty, _stream()), 'atlas_scatter')
+    return texture
+
+
+def atlas_fill(texture, cell, n_faces, fill=0.0):
+    """psn_atlas_fill: the texels of ``texture`` [T, T, C] that no face owns := fill, in place (owned texels are left alone)."""
+    T = int(texture.shape[0])
+    tp, C, ty = _atlas_texture('atlas_fill', texture, T)
+    with _Prof('atlas_fill', T * T * C * texture.element_size()):
+        _check(_lib.psn_atlas_fill(float(fill), C, T, int(cell), int(n_faces), tp, ty, _stream()), 'atlas_fill')
+    return texture
+
+
+def atlas_sample(face, bary, texture, cell, n_faces, out=None):
+    """psn_atlas_sample: face int64 [Q] (-1: a miss), bary float64 [Q, 3], texture float32 [T, T, C] -> float64 [Q, C], NaN rows for
+    the misses."""
+    T = int(texture.shape[0])
+    tp, C, ty = _atlas_texture('atlas_sample', texture, T)
+    if ty != IMG_F32:  # noqa: F821
+        raise RuntimeError('atlas_sample: the texture must be float32, got %s' % texture.dtype)
+    _tptr(face, 'atlas_sample: face', torch.int64)
+    _tptr(bary, 'atlas_sample: bary', torch.float64)
+    Q = int(face.shape[0])
+    if face.dim() != 1 or tuple(bary.shape) != (Q, 3) or face.device != texture.device or bary.device != texture.device:
+        raise RuntimeError('atlas_sample: face [Q] and bary [Q, 3] on the texture\'s device expected, got %s and %s' % (tuple(face.shape), tuple(bary.shape)))
+    out = _out(out, (Q, C), texture, 'atlas_sample: out', torch.float64)
+    with _Prof('atlas_sample', Q * C):
+        _check(_lib.psn_atlas_sample(_eptr(face, texture), _eptr(bary, texture), Q, tp, C, T, int(cell), int(n_faces), _eptr(out, texture),
+                                     _stream()), 'atlas_sample')
+    return out

@@ -42,7 +42,8 @@ def _mesh_tensors(index):
 
 
 @torch.no_grad()
-def render_mesh(mesh, pixels, camera_mat, world_mat, scale_mat=None, vertex_normals=None, device=None, sort_rays=True):
+def render_mesh(mesh, pixels, camera_mat, world_mat, scale_mat=None, vertex_normals=None, device=None, sort_rays=True, textures=None,
+                atlas=None):
     """The mesh as the camera of a dataset view sees it.  pixels [1, N, 2] (or [N, 2]) in the units of camera_mat, camera_mat
     [1, 3|4, 3|4], world_mat [1, 4, 4] (camera to world, the dataset's 'img.camera_mat' / 'img.world_mat').  ``scale_mat`` is taken for
     the signature's sake and, exactly as in ``Renderer.shape_extract`` (and stage1/model/common.py:205-207), not used.
@@ -54,7 +55,10 @@ def render_mesh(mesh, pixels, camera_mat, world_mat, scale_mat=None, vertex_norm
         tri      int64, the triangle hit (-1 on a miss)
         normals  unit length and turned to face the camera: the geometric normal of the triangle, or with ``vertex_normals``
                  [V, 3] (e.g. Extractor3D.estimate_normals) their barycentric interpolation, normalised
-    ``mesh``: a Mesh, a (vertices, faces) pair or a ready MeshIndex (one index serves every view)."""
+    ``mesh``: a Mesh, a (vertices, faces) pair or a ready MeshIndex (one index serves every view).
+    ``textures`` ({name: float32 [T, T, C]}, e.g. the maps of meshbake.bake_materials) with their ``atlas`` (a meshbake.Atlas): the
+    dict also holds, under each name, the texture looked up bilinearly at the first hits (meshbake.atlas_sample) -> float64 [N, C],
+    NaN wherever the ray misses.  Without them the dict is what it always was."""
     from .stage1.rendering import camera_origin, pixel_rays
     index = _index(mesh, device)
     if pixels.dim() == 2:
@@ -81,8 +85,29 @@ def render_mesh(mesh, pixels, camera_mat, world_mat, scale_mat=None, vertex_norm
     nrm = torch.where(length > 0, nrm / torch.where(length > 0, length, torch.ones_like(length)), zero)
     away = (nrm * d).sum(dim=1, keepdim=True) > 0
     nrm = torch.where(hit[:, None], torch.where(away, -nrm, nrm), zero)
-    return {'mask': hit, 't': t, 'depth': t * d.norm(dim=1), 'points': torch.where(hit[:, None], o + t[:, None] * d, zero),
-            'tri': tri, 'normals': nrm}
+    out = {'mask': hit, 't': t, 'depth': t * d.norm(dim=1), 'points': torch.where(hit[:, None], o + t[:, None] * d, zero),
+           'tri': tri, 'normals': nrm}
+    if textures:
+        out.update(_sample_textures(textures, atlas, tri, bary, out))
+    return out
+
+
+def _sample_textures(textures, atlas, tri, bary, out):
+    """Each texture at the first hits, on the path the cast took: device tensors through the kernel, otherwise the numpy definition."""
+    from . import meshbake
+    if atlas is None:
+        raise ValueError('render_mesh: textures need the atlas they were baked on')
+    sampled = {}
+    for name, tex in textures.items():
+        if name in out:
+            raise ValueError('render_mesh: the texture name %r is a key of the result' % name)
+        if tri.is_cuda:
+            tex = torch.as_tensor(tex).to(device=tri.device, dtype=torch.float32).contiguous()
+            sampled[name] = meshbake.atlas_sample(atlas, tri, bary, tex)
+        else:
+            tex = tex.detach().cpu().numpy() if torch.is_tensor(tex) else np.asarray(tex)
+            sampled[name] = torch.from_numpy(meshbake.host_atlas_sample(atlas, tri.numpy(), bary.numpy(), tex.astype(np.float32, copy=False)))
+    return sampled
 
 
 @functools.lru_cache(maxsize=8)
@@ -96,12 +121,12 @@ def tile_pixels(H, W, tile=8):
 
 
 @torch.no_grad()
-def render_view(mesh, camera_mat, world_mat, H, W, scale_mat=None, vertex_normals=None, device=None):
+def render_view(mesh, camera_mat, world_mat, H, W, scale_mat=None, vertex_normals=None, device=None, textures=None, atlas=None):
     """render_mesh over the whole H x W pixel grid (integer pixel coordinates, as handoff.arange_pixels makes them), handed over
-    in 8 x 8 tiles -> the same dict with [H, W] / [H, W, 3] maps."""
+    in 8 x 8 tiles -> the same dict with [H, W] / [H, W, 3] maps (and [H, W, C] per texture of ``textures``)."""
     px = tile_pixels(H, W)
     out = render_mesh(mesh, px[None].to(device=camera_mat.device, dtype=camera_mat.dtype), camera_mat, world_mat, scale_mat, vertex_normals,
-                      device, sort_rays=False)
+                      device, sort_rays=False, textures=textures, atlas=atlas)
     maps = {}
     for key, val in out.items():
         full = torch.zeros((H, W) + tuple(val.shape[1:]), dtype=val.dtype, device=val.device)

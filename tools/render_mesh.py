@@ -4,7 +4,7 @@ binary shadow maps -- the maps of the ASSET (or of a ground-truth scan), to be c
 
     python tools/render_mesh.py --mesh test_out/bear/test_1/mesh.ply --cameras data/bear/params.json --out mesh_maps
                                 [--views 1 5 9] [--hw H W] [--vertex-normals] [--gt-normal data/bear/normal/npy]
-                                [--gt-mask data/bear/norm_mask] [--lights FILE] [--host]
+                                [--gt-mask data/bear/norm_mask] [--lights FILE] [--textures] [--host]
 
 --cameras is the dataset's params.json, read as stage1/dataloading/dataset.py and tools/evaluate.py read it: 'K' (intrinsics),
 'pose_c2w' (camera to world per view, OpenGL axes: columns 1 and 2 are negated to get the OpenCV pose the renderer takes), 'imhw',
@@ -19,6 +19,10 @@ agree; ground-truth normals in camera space ('gt_normal_world' false) are rotate
 --lights FILE: the light directions of the shadow maps: the cameras file itself (its 'light_direction'), a .npy / .json [L, 3], or a
 text table.  shadow/view_VV.npy is bool [L, H, W]: True where the light is visible from the surface point under the pixel going by
 the mesh (meshrender.mesh_light_visibility: binary occlusion, not the network's transmittance); off the mesh True.
+--textures: --mesh is a textured asset of tools/bake_materials.py (name.obj with name_albedo.png / name_normal.png /
+name_specular.npy beside it, whichever exist); each map is looked up at the first hits (meshbake.atlas_sample) and written as
+<map>/view_VV.npy (float32 [H, W, C], NaN off the mesh) and, for albedo and normal, .png.  The PNG maps are read back as the bytes they
+are (albedo u / 255, normal 2 u / 255 - 1): what another renderer would see.
 On a GPU everything runs on the device; --host takes the numpy definition (small meshes only: it is a brute force)."""
 import argparse
 import json
@@ -59,6 +63,25 @@ def save_png(path, array):
     return True
 
 
+def read_textures(mesh_path, n_faces):
+    """The maps beside a baked name.obj -> ({name: float32 [T, T, C]}, Atlas)."""
+    from PIL import Image
+    from psnerf_amd import meshbake as mb
+    base = os.path.splitext(mesh_path)[0]
+    maps = {}
+    for name, decode in (('albedo', lambda u: u / np.float32(255.0)), ('normal', lambda u: u * np.float32(2.0 / 255.0) - np.float32(1.0))):
+        if os.path.exists(base + '_%s.png' % name):
+            maps[name] = decode(np.asarray(Image.open(base + '_%s.png' % name).convert('RGB')).astype(np.float32))
+    if os.path.exists(base + '_specular.npy'):
+        maps['specular'] = np.load(base + '_specular.npy').astype(np.float32)
+    if not maps:
+        raise SystemExit('render_mesh: --textures, but no %s_albedo.png / _normal.png / _specular.npy' % base)
+    sizes = set(m.shape[:2] for m in maps.values())
+    if len(sizes) != 1 or len(set(sizes.pop())) != 1:
+        raise SystemExit('render_mesh: the maps of %s are not square textures of one size' % base)
+    return maps, mb.Atlas(next(iter(maps.values())).shape[0], n_faces)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Normal, depth, mask and shadow maps of a mesh from a dataset\'s cameras.')
     ap.add_argument('--mesh', required=True, help='.obj or .ply (meshdist.load_mesh)')
@@ -70,6 +93,7 @@ def main(argv=None):
     ap.add_argument('--gt-normal', default=None, help='directory of ground-truth normal maps view_VV.npy')
     ap.add_argument('--gt-mask', default=None, help='directory of ground-truth masks view_VV.png')
     ap.add_argument('--lights', default=None, help='light directions for binary shadow maps')
+    ap.add_argument('--textures', action='store_true', help='--mesh is a baked asset: also look its maps up at the first hits')
     ap.add_argument('--host', action='store_true', help='run the float64 numpy definition on the CPU')
     args = ap.parse_args(argv)
 
@@ -87,6 +111,9 @@ def main(argv=None):
             raise SystemExit('render_mesh: %s carries no vertex normals' % args.mesh)
         vn = mesh.vertex_normals
     index = mr._index(mesh, dev if dev is not None else 'cpu')       # one index for every view
+    textures, atlas = read_textures(args.mesh, len(mesh.faces)) if args.textures else (None, None)
+    if textures is not None and dev is not None:
+        textures = dict((k, torch.from_numpy(np.ascontiguousarray(t)).to(dev)) for k, t in textures.items())
     with open(args.cameras) as f:
         para = json.load(f)
     H, W = args.hw if args.hw is not None else para['imhw']
@@ -95,7 +122,7 @@ def main(argv=None):
     pose = pose_gl.copy()
     pose[:, :3, 1:3] *= -1.0                                          # OpenGL -> OpenCV, stage1/dataloading/dataset.py:56
     views = args.views if args.views else list(range(1, int(para.get('n_view', len(pose))) + 1))
-    for sub in ('normal', 'depth', 'mask') + (('shadow',) if args.lights else ()):
+    for sub in ('normal', 'depth', 'mask') + (('shadow',) if args.lights else ()) + tuple('tex_' + k for k in (textures or ())):
         os.makedirs(os.path.join(args.out, sub), exist_ok=True)
     maes, wrote_png = [], True
     for vi in views:
@@ -104,9 +131,9 @@ def main(argv=None):
         name = 'view_%02d' % vi
         c2w = torch.from_numpy(pose[vi - 1])[None]
         if dev is not None:
-            out = mr.render_view(index, K.to(dev), c2w.to(dev), H, W, vertex_normals=vn)
+            out = mr.render_view(index, K.to(dev), c2w.to(dev), H, W, vertex_normals=vn, textures=textures, atlas=atlas)
         else:
-            out = mr.render_view(index, K, c2w, H, W, vertex_normals=vn)
+            out = mr.render_view(index, K, c2w, H, W, vertex_normals=vn, textures=textures, atlas=atlas)
         mask = out['mask']
         normal = out['normals'].to(torch.float32)
         depth = out['depth'].to(torch.float32)
@@ -120,6 +147,12 @@ def main(argv=None):
                      and save_png(os.path.join(args.out, 'depth', name + '.png'), im.to_img(shade).cpu().numpy())
                      and save_png(os.path.join(args.out, 'mask', name + '.png'), im.to_img(mask.to(torch.float32)).cpu().numpy()))
         line = '%s: %d of %d pixels on the mesh, depth %.4f .. %.4f' % (name, int(mask.sum()), H * W, lo, hi)
+        for key in (textures or ()):
+            tex = out[key].to(torch.float32)
+            np.save(os.path.join(args.out, 'tex_' + key, name + '.npy'), tex.cpu().numpy())
+            if key in ('albedo', 'normal'):
+                shown = torch.nan_to_num((tex + 1.0) / 2.0 if key == 'normal' else tex, nan=0.0) * mask[..., None]
+                save_png(os.path.join(args.out, 'tex_' + key, name + '.png'), im.to_img(shown).cpu().numpy())
         if args.gt_normal:
             gt = np.load(os.path.join(args.gt_normal, name + '.npy')).astype(np.float32)
             if not para.get('gt_normal_world', True):
