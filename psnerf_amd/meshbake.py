@@ -39,6 +39,8 @@ import os
 import numpy as np
 import torch
 
+from .meshcore import Phase, device_mesh, face_cross, host_mesh, mesh_parts, on_device, to_numpy
+
 MIN_CELL = 4                 # PSN_ATLAS_MIN_CELL
 MAX_SIZE = 32768             # PSN_ATLAS_MAX_SIZE
 MAX_CHANNELS = 32            # PSN_ATLAS_MAX_CHANNELS
@@ -126,19 +128,6 @@ def to_img(x):
 
 
 # ------------------------------------------------------------------------------------------------ host path: the definition
-def _mesh_arrays(vertices, faces, vertex_normals):
-    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1, 3))
-    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
-    if f.shape[0] and (f.min() < 0 or f.max() >= v.shape[0]):
-        raise ValueError('atlas: a face refers to a vertex outside 0 .. %d' % (v.shape[0] - 1))
-    vn = None
-    if vertex_normals is not None:
-        vn = np.ascontiguousarray(np.asarray(vertex_normals, dtype=np.float64).reshape(-1, 3))
-        if vn.shape[0] != v.shape[0]:
-            raise ValueError('atlas: %d vertex normals for %d vertices' % (vn.shape[0], v.shape[0]))
-    return v, f, vn
-
-
 def _unit(m):
     """m / |m| with |m| = sqrt((m0 m0 + m1 m1) + m2 m2); a vector whose length is not > 0 becomes zero."""
     with np.errstate(all='ignore'):
@@ -150,7 +139,7 @@ def _unit(m):
 def host_atlas_points(atlas, vertices, faces, vertex_normals=None, f0=0, f1=None):
     """The surface points and normals of the rows of the faces f0 <= f < f1 -> (points float64 [R, 3], points_f32 float32 [R, 3] = the
     points rounded once, normals float64 [R, 3]), R = (f1 - f0) K."""
-    v, f, vn = _mesh_arrays(vertices, faces, vertex_normals)
+    v, f, vn = host_mesh(vertices, faces, vertex_normals, prefix='atlas', widen_normals=True)
     if f.shape[0] != atlas.F:
         raise ValueError('atlas: %d faces, the atlas was laid out for %d' % (f.shape[0], atlas.F))
     f0, f1 = atlas._range(f0, f1)
@@ -166,8 +155,7 @@ def host_atlas_points(atlas, vertices, faces, vertex_normals=None, f0=0, f1=None
             b0 = (1.0 - (i + j).astype(np.float64) / nd)[None, :, None]
             m = (b0 * vn[tri[:, 0]][:, None, :] + u * vn[tri[:, 1]][:, None, :]) + w * vn[tri[:, 2]][:, None, :]
         else:
-            a, b = e1[:, 0, :], e2[:, 0, :]
-            m = np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=-1)
+            m = np.stack(face_cross(v, tri), axis=-1)
             m = np.broadcast_to(m[:, None, :], (f1 - f0, atlas.K, 3))
         return p, p.astype(np.float32), _unit(m.reshape(-1, 3))
 
@@ -232,10 +220,6 @@ def host_atlas_sample(atlas, face, bary, texture):
 
 
 # ------------------------------------------------------------------------------------------------ one code path over both
-def _on_device(x):
-    return torch.is_tensor(x) and x.is_cuda
-
-
 def _no_cpu_tensor(x, what):
     if torch.is_tensor(x) and not x.is_cuda:
         raise RuntimeError('%s: a HIP device tensor (the kernels) or a numpy array (the host definition) expected, got a CPU tensor' % what)
@@ -244,7 +228,7 @@ def _no_cpu_tensor(x, what):
 def atlas_points(atlas, vertices, faces, vertex_normals=None, f0=0, f1=None):
     """host_atlas_points for numpy arrays; for device tensors the same through psn_atlas_points (bit for bit), device tensors out."""
     _no_cpu_tensor(vertices, 'atlas_points')
-    if not _on_device(vertices):
+    if not on_device(vertices):
         return host_atlas_points(atlas, vertices, faces, vertex_normals, f0, f1)
     from . import hip
     if faces.shape[0] != atlas.F:
@@ -255,7 +239,7 @@ def atlas_points(atlas, vertices, faces, vertex_normals=None, f0=0, f1=None):
 def atlas_scatter(atlas, rows, f0=0, f1=None, out=None, fill=None, u8=False):
     """host_atlas_scatter for numpy arrays; for device tensors the same through psn_atlas_scatter / psn_atlas_fill."""
     _no_cpu_tensor(rows, 'atlas_scatter')
-    if not _on_device(rows):
+    if not on_device(rows):
         return host_atlas_scatter(atlas, rows, f0, f1, out, fill, u8)
     from . import hip
     if out is None:
@@ -272,20 +256,13 @@ def atlas_scatter(atlas, rows, f0=0, f1=None, out=None, fill=None, u8=False):
 def atlas_sample(atlas, face, bary, texture):
     """host_atlas_sample for numpy arrays; for device tensors the same through psn_atlas_sample."""
     _no_cpu_tensor(texture, 'atlas_sample')
-    if not _on_device(texture):
+    if not on_device(texture):
         return host_atlas_sample(atlas, face, bary, texture)
     from . import hip
     return hip.atlas_sample(face.contiguous(), bary.contiguous(), texture, atlas.c, atlas.F)
 
 
 # ------------------------------------------------------------------------------------------------ the bake
-def _mesh_parts(mesh):
-    """A Mesh, anything with .vertices / .faces (/ .vertex_normals), or a (vertices, faces[, vertex_normals]) tuple."""
-    if isinstance(mesh, (tuple, list)):
-        return mesh[0], mesh[1], (mesh[2] if len(mesh) > 2 else None)
-    return mesh.vertices, mesh.faces, getattr(mesh, 'vertex_normals', None)
-
-
 def host_embed(x, n_freqs):
     """[x, sin(2^k x), cos(2^k x)]_{k < n_freqs} of CPU points [R, 3] in float32 (the columns psn_pe_encode writes on the device)."""
     out = [x]
@@ -338,44 +315,9 @@ def material_rows(model, x, row_normals, maps=MAPS, cache=None):
     return out
 
 
-def _host_mesh(vertices, faces, vnormals):
-    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else a
-    return _mesh_arrays(to_np(vertices), to_np(faces), None if vnormals is None else to_np(vnormals))
-
-
-def _device_mesh(vertices, faces, vnormals, dev):
-    """The mesh as contiguous device tensors (moved there once; device tensors are taken as they are), checked as _mesh_arrays checks."""
-    def put(a, dtype):
-        a = a if torch.is_tensor(a) else torch.from_numpy(np.array(a, dtype=np.float64 if dtype == torch.float64 else np.int64))
-        return a.to(device=dev, dtype=dtype).reshape(-1, 3).contiguous()
-    v, f = put(vertices, torch.float64), put(faces, torch.int64)
-    vn = None if vnormals is None else put(vnormals, torch.float64)
-    if f.shape[0] and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
-        raise ValueError('atlas: a face refers to a vertex outside 0 .. %d' % (v.shape[0] - 1))
-    if vn is not None and vn.shape[0] != v.shape[0]:
-        raise ValueError('atlas: %d vertex normals for %d vertices' % (vn.shape[0], v.shape[0]))
-    return v, f, vn
-
-
 # When set to a list (tools/bench_bake.py), bake_materials appends (phase, start_event, end_event) recorded on the stream: 'points',
 # one phase per map (encoding + network + its output glue) and 'scatter'.
 PHASE_EVENTS = None
-
-
-class _Phase(object):
-    def __init__(self, name):
-        self.name, self.events = name, PHASE_EVENTS
-
-    def __enter__(self):
-        if self.events is not None:
-            self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            self.e0.record()
-
-    def __exit__(self, *exc):
-        if self.events is not None and exc[0] is None:
-            self.e1.record()
-            self.events.append((self.name, self.e0, self.e1))
-        return False
 
 
 @torch.no_grad()
@@ -396,7 +338,13 @@ def bake_materials(model, mesh, size=2048, maps=MAPS, chunk_faces=None, fill=0.0
     if dev != param.device:
         raise ValueError('bake_materials: the model is on %s, device = %s' % (param.device, dev))
     on_dev = dev.type == 'cuda'
-    v, f, vn = _device_mesh(*_mesh_parts(mesh), dev) if on_dev else _host_mesh(*_mesh_parts(mesh))
+    v, f, vn = mesh_parts(mesh)
+    if on_dev:
+        v, f, vn = device_mesh(v, f, vn, dev, prefix='atlas', widen_normals=True)
+        if f.shape[0] and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):   # (two host reads: the atlas kernels have no status word)
+            raise ValueError('atlas: a face refers to a vertex outside 0 .. %d' % (v.shape[0] - 1))
+    else:
+        v, f, vn = host_mesh(to_numpy(v), to_numpy(f), to_numpy(vn), prefix='atlas', widen_normals=True)
     atlas = Atlas(size, f.shape[0])
     step = max(1, CHUNK_ROWS // atlas.K) if chunk_faces is None else int(chunk_faces)
     if step < 1:
@@ -407,15 +355,15 @@ def bake_materials(model, mesh, size=2048, maps=MAPS, chunk_faces=None, fill=0.0
     try:
         for f0 in range(0, atlas.F, step):
             f1 = min(f0 + step, atlas.F)
-            with _Phase('points'):
+            with Phase(PHASE_EVENTS, 'points'):
                 _, x, nrm = atlas_points(atlas, v, f, vn, f0, f1)
             if not on_dev:
                 x, nrm = torch.from_numpy(x), torch.from_numpy(nrm)
             cache = {}                                                   # the encodings of this chunk's points
             for name in maps:
-                with _Phase(name):
+                with Phase(PHASE_EVENTS, name):
                     rows = material_rows(model, x, nrm, (name,), cache)[name].float().contiguous()
-                with _Phase('scatter'):
+                with Phase(PHASE_EVENTS, 'scatter'):
                     out[name] = atlas_scatter(atlas, rows if on_dev else rows.numpy(), f0, f1, out.get(name), fill if name not in out else None)
     finally:
         model.train(was_training)
@@ -434,15 +382,13 @@ def export_textured(path, mesh, baked, gamma=1.0):
     folder, name = os.path.dirname(os.path.abspath(base)), os.path.basename(base)
     os.makedirs(folder, exist_ok=True)
     atlas = baked['atlas']
-    vertices, faces, vnormals = _mesh_parts(mesh)
-    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    v, f, vn = _mesh_arrays(to_np(vertices), to_np(faces), None if vnormals is None else to_np(vnormals))
+    v, f, vn = host_mesh(*(to_numpy(x) for x in mesh_parts(mesh)), prefix='atlas', widen_normals=True)
     if f.shape[0] != atlas.F:
         raise ValueError('export_textured: %d faces, the atlas was laid out for %d' % (f.shape[0], atlas.F))
     files = {'obj': os.path.join(folder, name + '.obj'), 'mtl': os.path.join(folder, name + '.mtl')}
     mtl = ['newmtl %s' % name, 'Ka 0 0 0', 'Kd 1 1 1', 'Ks 0 0 0', 'illum 1']
     if 'albedo' in baked:
-        a = to_np(baked['albedo']).astype(np.float32)
+        a = to_numpy(baked['albedo']).astype(np.float32)
         if gamma != 1.0:
             a = np.power(a.clip(0, 1), np.float32(1.0 / gamma)).astype(np.float32)
         files['albedo'] = os.path.join(folder, name + '_albedo.png')
@@ -450,11 +396,11 @@ def export_textured(path, mesh, baked, gamma=1.0):
         mtl.append('map_Kd %s_albedo.png' % name)
     if 'normal' in baked:
         files['normal'] = os.path.join(folder, name + '_normal.png')
-        Image.fromarray(to_img(to_np(baked['normal']).astype(np.float32) / np.float32(2.0) + np.float32(0.5))).save(files['normal'])
+        Image.fromarray(to_img(to_numpy(baked['normal']).astype(np.float32) / np.float32(2.0) + np.float32(0.5))).save(files['normal'])
         mtl += ['# object-space normals, stored as n / 2 + 0.5', 'norm %s_normal.png' % name]
     if 'specular' in baked:
         files['specular'] = os.path.join(folder, name + '_specular.npy')
-        np.save(files['specular'], to_np(baked['specular']).astype(np.float32))
+        np.save(files['specular'], to_numpy(baked['specular']).astype(np.float32))
         mtl.append('# specular: %s_specular.npy, float32 [T, T, C]' % name)
     with open(files['mtl'], 'w') as out:
         out.write('\n'.join(mtl) + '\n')

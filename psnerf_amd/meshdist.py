@@ -36,12 +36,11 @@ triangle by the same edge functions without the shear, with an edge function tha
 so that a line through a shared edge or a vertex crosses exactly one of the triangles around it; per point the triangles of the
 WHOLE mesh crossed above it, below it and at it are counted, and inside = the parity of those above.
 """
-import os
-
 import numpy as np
 import torch
 
-from .stage1.extracting import Mesh
+from .meshcore import Phase, device_mesh, face_areas, host_mesh, mesh_parts, on_device, to_numpy
+from .meshcore import load_mesh   # noqa: F401 (the evaluation tools and tests read meshes through this module)
 
 _PAIRS_PER_CHUNK = 1 << 20   # host path: point-triangle pairs evaluated at a time (some forty float64 temporaries of that size)
 
@@ -110,18 +109,10 @@ def _closest_on_triangles(p, a, b, c):
         return out
 
 
-def _as_mesh_arrays(vertices, faces):
-    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1, 3))
-    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
-    if f.shape[0] and (f.min() < 0 or f.max() >= v.shape[0]):
-        raise ValueError('mesh: a face refers to vertex %d of %d' % (int(f.max() if f.max() >= v.shape[0] else f.min()), v.shape[0]))
-    return v, f
-
-
 def host_point_triangle(vertices, faces, points, triangle_id):
     """Closest point and distance from points [Q, 3] to the triangles triangle_id [Q] (one triangle per point) ->
     (closest float64 [Q, 3], distance float64 [Q])."""
-    v, f = _as_mesh_arrays(vertices, faces)
+    v, f, _ = host_mesh(vertices, faces)
     pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     t = f[np.asarray(triangle_id, dtype=np.int64)]
     p = [pts[:, i] for i in range(3)]
@@ -134,7 +125,7 @@ def host_closest_point(vertices, faces, points):
     triangle_id int64 [Q]) by brute force over all triangles, in chunks of queries so that memory stays bounded.  Ties on the
     distance go to the lowest triangle index.  Unlike trimesh, zero-area triangles take part with their true (segment / point)
     distance and no NaN arises (see the module docstring)."""
-    v, f = _as_mesh_arrays(vertices, faces)
+    v, f, _ = host_mesh(vertices, faces)
     if f.shape[0] == 0:
         raise ValueError('host_closest_point: the mesh has no faces')
     pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
@@ -196,7 +187,7 @@ def host_ray_triangle(vertices, faces, origins, directions, triangle_id):
     """The watertight test of rays [Q] against the triangles triangle_id [Q] (one triangle per ray), without a window on t ->
     (t float64 [Q], barycentrics float64 [Q, 3] = (U, V, W) / det, accepted bool [Q]).  Where the test does not accept (or the id is
     negative) t is inf and the barycentrics are NaN."""
-    v, f = _as_mesh_arrays(vertices, faces)
+    v, f, _ = host_mesh(vertices, faces)
     valid, k, o, S = _ray_frames(origins, directions)
     tid = np.asarray(triangle_id, dtype=np.int64).reshape(-1)
     valid = valid & (tid >= 0)
@@ -215,7 +206,7 @@ def host_ray_cast(vertices, faces, origins, directions, t_min=0.0, t_max=np.inf,
     bounded -> (t float64 [Q], triangle_id int64 [Q], barycentrics float64 [Q, 3], hit bool [Q]): the first accepted hit with
     t_min <= t <= t_max, ties on t to the lowest triangle index; a miss is (inf, -1, NaN, False).  ``any_hit``: only ``hit`` is
     computed, the other three hold the values of a miss.  See the module docstring for the definition."""
-    v, f = _as_mesh_arrays(vertices, faces)
+    v, f, _ = host_mesh(vertices, faces)
     if f.shape[0] == 0:
         raise ValueError('host_ray_cast: the mesh has no faces')
     if not t_min <= t_max:
@@ -286,7 +277,7 @@ def host_crossings(vertices, faces, points, axis=2):
     can agree for a point anywhere on the slivers' line), the three sides are equal and non-zero and det = U + V + W != 0, with
     z = (U Az + V Bz + W Cz) / det; a non-finite z counts nowhere.  Zero-area and edge-on triangles are never counted; a point with a
     non-finite coordinate gets three zeros."""
-    v, f = _as_mesh_arrays(vertices, faces)
+    v, f, _ = host_mesh(vertices, faces)
     if f.shape[0] == 0:
         raise ValueError('host_crossings: the mesh has no faces')
     if axis not in (0, 1, 2):
@@ -307,13 +298,8 @@ def host_crossings(vertices, faces, points, axis=2):
 
 
 def host_face_areas(vertices, faces):
-    v, f = _as_mesh_arrays(vertices, faces)
-    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
-    ab, ac = b - a, c - a
-    nx = ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1]
-    ny = ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2]
-    nz = ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]
-    return 0.5 * np.sqrt(nx * nx + ny * ny + nz * nz)
+    v, f, _ = host_mesh(vertices, faces)
+    return face_areas(v, f)
 
 
 def _draw(rng, count):
@@ -328,7 +314,7 @@ def host_sample_surface(vertices, faces, count, rng=None, return_cumulative=Fals
     """trimesh.sample.sample_surface(mesh, count) -> (points float64 [count, 3], face_index int64 [count]): faces drawn with
     probability proportional to their area, a uniform point per draw.  ``rng``: an np.random.RandomState (default: the global
     np.random, as the reference)."""
-    v, f = _as_mesh_arrays(vertices, faces)
+    v, f, _ = host_mesh(vertices, faces)
     if f.shape[0] == 0:
         raise ValueError('host_sample_surface: the mesh has no faces')
     pick, uv = _draw(rng, int(count))
@@ -356,14 +342,8 @@ class MeshIndex(object):
 
     def __init__(self, vertices, faces, device=None, name='mesh', profile=False):
         from . import hip
-        if not torch.is_tensor(vertices):
-            vertices = torch.as_tensor(np.asarray(vertices, dtype=np.float64))
-        if not torch.is_tensor(faces):
-            faces = torch.as_tensor(np.asarray(faces, dtype=np.int64))
-        if device is None:
-            device = vertices.device if vertices.is_cuda else torch.device('cuda')
-        self.vertices = vertices.to(device=device, dtype=torch.float64).reshape(-1, 3).contiguous()
-        self.faces = faces.to(device=device, dtype=torch.int64).reshape(-1, 3).contiguous()
+        self.vertices, self.faces, _ = device_mesh(vertices, faces, None, device)
+        device = self.vertices.device
         if self.faces.shape[0] == 0 or self.vertices.shape[0] == 0:
             raise ValueError('%s is empty (%d vertices, %d faces)' % (name, self.vertices.shape[0], self.faces.shape[0]))
         v, f = self.vertices, self.faces
@@ -402,8 +382,7 @@ class MeshIndex(object):
         self.over_list, self.n_over, self.n_entries = over_list[:n_over].clone(), n_over, n_entries
 
     def _phase(self, name):
-        from .stage1.extracting import _Phase
-        return _Phase(self.build_events, name)
+        return Phase(self.build_events, name)
 
     @property
     def index_bytes(self):
@@ -483,13 +462,7 @@ class MeshIndex(object):
         return _contains(self, points, axis, vote)
 
     def face_areas_cumulative(self):
-        v, f = self.vertices, self.faces
-        a = v[f[:, 0]]
-        ab, ac = v[f[:, 1]] - a, v[f[:, 2]] - a
-        nx = ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1]
-        ny = ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2]
-        nz = ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]
-        return torch.cumsum(0.5 * torch.sqrt(nx * nx + ny * ny + nz * nz), dim=0)
+        return torch.cumsum(face_areas(self.vertices, self.faces), dim=0)
 
     def sample_surface(self, count, rng=None, return_cumulative=False):
         """host_sample_surface on the device: the uniforms are drawn on the host from ``rng`` in the host path's order and uploaded
@@ -512,7 +485,7 @@ class _HostMesh(object):
     """The host twin of MeshIndex (same methods), so that the Chamfer functions below and meshrender are written once."""
 
     def __init__(self, vertices, faces, name='mesh'):
-        self.vertices, self.faces = _as_mesh_arrays(vertices, faces)
+        self.vertices, self.faces, _ = host_mesh(vertices, faces)
         if self.faces.shape[0] == 0 or self.vertices.shape[0] == 0:
             raise ValueError('%s is empty (%d vertices, %d faces)' % (name, self.vertices.shape[0], self.faces.shape[0]))
 
@@ -523,11 +496,10 @@ class _HostMesh(object):
         return host_closest_point(self.vertices, self.faces, points)
 
     def ray_cast(self, origins, directions, t_min=0.0, t_max=np.inf, any_hit=False, n_tests=None):
-        to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x
-        return host_ray_cast(self.vertices, self.faces, to_np(origins), to_np(directions), t_min, t_max, any_hit)
+        return host_ray_cast(self.vertices, self.faces, to_numpy(origins), to_numpy(directions), t_min, t_max, any_hit)
 
     def crossings(self, points, axis=2, below=True, n_tests=None):
-        above, under, on = host_crossings(self.vertices, self.faces, points.detach().cpu().numpy() if torch.is_tensor(points) else points, axis)
+        above, under, on = host_crossings(self.vertices, self.faces, to_numpy(points), axis)
         return above, (under if below else None), on
 
     def contains(self, points, axis=2, vote=False):
@@ -543,18 +515,14 @@ def _contains(mesh, points, axis, vote):
 
 
 def _prepare(mesh, device, name):
-    """A mesh (anything with .vertices and .faces; a MeshIndex is taken as it is) -> MeshIndex or _HostMesh."""
+    """A mesh (anything meshcore.mesh_parts takes; a MeshIndex or _HostMesh is taken as it is) -> MeshIndex or _HostMesh.
+    device='cpu' with device tensors: the caller asked for the host path."""
     if isinstance(mesh, (MeshIndex, _HostMesh)):
         return mesh
-    v, f = mesh.vertices, mesh.faces
-    on_device = torch.is_tensor(v) and v.is_cuda
-    if device is not None and torch.device(device).type == 'cuda':
-        return MeshIndex(v, f, device=v.device if on_device else torch.device(device), name=name)
-    if on_device:
-        if device is not None:   # device='cpu' with device tensors: the caller asked for the host path
-            return _HostMesh(v.cpu().numpy(), f.cpu().numpy(), name)
-        return MeshIndex(v, f, name=name)
-    return _HostMesh(v.numpy() if torch.is_tensor(v) else v, f.numpy() if torch.is_tensor(f) else f, name)
+    v, f, _ = mesh_parts(mesh)
+    if on_device(v, device):
+        return MeshIndex(v, f, device=device, name=name)
+    return _HostMesh(to_numpy(v), to_numpy(f), name)
 
 
 def get_chamfer_dist(src_mesh, tgt_mesh, num_samples=10000, rng=None, device=None):
@@ -579,141 +547,3 @@ def get_surface_dist(src_mesh, tgt_mesh, num_samples=10000, rng=None, device=Non
     src_surf_pts, _ = src.sample_surface(num_samples, rng)
     _, src_tgt_dist, _ = tgt.closest_point(src_surf_pts)
     return float(src_tgt_dist.mean())
-
-
-# ------------------------------------------------------------------------------------------------ reading meshes
-_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
-              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
-
-
-def _fan(polygons):
-    """Polygons (lists of vertex indices) -> triangles, a fan around the first corner."""
-    out = []
-    for p in polygons:
-        if len(p) < 3:
-            raise ValueError('a face with %d corners' % len(p))
-        out.extend((p[0], p[k], p[k + 1]) for k in range(1, len(p) - 1))
-    return np.asarray(out, dtype=np.int64).reshape(-1, 3)
-
-
-def _load_obj(path):
-    vertices, normals, polygons = [], [], []
-    with open(path, 'r') as fh:
-        for line in fh:
-            tok = line.split()
-            if not tok or tok[0].startswith('#'):
-                continue
-            if tok[0] == 'v':
-                vertices.append([float(x) for x in tok[1:4]])
-            elif tok[0] == 'vn':
-                normals.append([float(x) for x in tok[1:4]])
-            elif tok[0] == 'f':
-                idx = [int(t.split('/')[0]) for t in tok[1:]]
-                polygons.append([i - 1 if i > 0 else len(vertices) + i for i in idx])   # (negative: relative to the end)
-    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
-    vn = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
-    return Mesh(v, _fan(polygons), vertex_normals=vn if len(vn) == len(v) and len(v) else None)
-
-
-def _load_ply(path):
-    with open(path, 'rb') as fh:
-        data = fh.read()
-    end = data.find(b'end_header')
-    if not data.startswith(b'ply') or end < 0:
-        raise ValueError('no PLY header')
-    body = data.index(b'\n', end) + 1
-    fmt, elements = None, []
-    for line in data[:end].decode('ascii', 'replace').splitlines()[1:]:
-        tok = line.split()
-        if not tok or tok[0] in ('comment', 'obj_info'):
-            continue
-        if tok[0] == 'format':
-            fmt = tok[1]
-        elif tok[0] == 'element':
-            elements.append((tok[1], int(tok[2]), []))
-        elif tok[0] == 'property':
-            if not elements:
-                raise ValueError('a property before any element')
-            elements[-1][2].append((tok[-1], (tok[2], tok[3])) if tok[1] == 'list' else (tok[-1], tok[1]))
-    if fmt not in ('ascii', 'binary_little_endian'):
-        raise ValueError('format %r (supported: ascii, binary_little_endian)' % fmt)
-    vertices, polygons, normals = None, [], None
-    tokens, tpos = (data[body:].split(), 0) if fmt == 'ascii' else (None, 0)
-    pos = body
-    for name, count, props in elements:
-        has_list = any(isinstance(t, tuple) for _, t in props)
-        if any((t if not isinstance(t, tuple) else t[0]) not in _PLY_TYPES or (isinstance(t, tuple) and t[1] not in _PLY_TYPES)
-               for _, t in props):
-            raise ValueError('element %s: unknown property type' % name)
-        if not has_list:
-            if fmt == 'ascii':
-                rows = np.asarray(tokens[tpos:tpos + count * len(props)], dtype=np.float64).reshape(count, len(props))
-                tpos += count * len(props)
-                cols = dict((p, rows[:, i]) for i, (p, _) in enumerate(props))
-            else:
-                dt = np.dtype([(p, '<' + _PLY_TYPES[t]) for p, t in props])
-                rec = np.frombuffer(data, dtype=dt, count=count, offset=pos)
-                pos += count * dt.itemsize
-                cols = dict((p, rec[p]) for p, _ in props)
-            if name == 'vertex':
-                vertices = np.stack([cols['x'], cols['y'], cols['z']], axis=1).astype(np.float64)
-                if all(k in cols for k in ('nx', 'ny', 'nz')):
-                    normals = np.stack([cols['nx'], cols['ny'], cols['nz']], axis=1).astype(np.float64)
-            continue
-        is_face = name == 'face'
-        if fmt == 'binary_little_endian' and len(props) == 1 and count > 0:
-            # the common case (and what Mesh.export writes): one list property, every face with as many corners as the first
-            ct, it = _PLY_TYPES[props[0][1][0]], _PLY_TYPES[props[0][1][1]]
-            k = int(np.frombuffer(data, dtype='<' + ct, count=1, offset=pos)[0])
-            dt = np.dtype([('n', '<' + ct), ('i', '<' + it, (k,))])
-            if pos + count * dt.itemsize <= len(data):
-                rec = np.frombuffer(data, dtype=dt, count=count, offset=pos)
-                if (rec['n'] == k).all():
-                    pos += count * dt.itemsize
-                    if is_face:
-                        polygons = rec['i'].astype(np.int64).reshape(count, k)
-                    continue
-        rows = []
-        for _ in range(count):
-            row = None
-            for pname, t in props:
-                if isinstance(t, tuple):
-                    if fmt == 'ascii':
-                        k = int(tokens[tpos])
-                        idx = [int(x) for x in tokens[tpos + 1:tpos + 1 + k]]
-                        tpos += 1 + k
-                    else:
-                        ct, it = np.dtype('<' + _PLY_TYPES[t[0]]), np.dtype('<' + _PLY_TYPES[t[1]])
-                        k = int(np.frombuffer(data, dtype=ct, count=1, offset=pos)[0])
-                        idx = np.frombuffer(data, dtype=it, count=k, offset=pos + ct.itemsize).astype(np.int64).tolist()
-                        pos += ct.itemsize + k * it.itemsize
-                    if pname in ('vertex_indices', 'vertex_index'):
-                        row = idx
-                elif fmt == 'ascii':
-                    tpos += 1
-                else:
-                    pos += np.dtype(_PLY_TYPES[t]).itemsize
-            if is_face and row is not None:
-                rows.append(row)
-        if is_face:
-            polygons = rows
-    if vertices is None:
-        raise ValueError('no vertex element')
-    faces = _fan([list(p) for p in polygons]) if len(polygons) else np.zeros((0, 3), dtype=np.int64)
-    return Mesh(vertices, faces, vertex_normals=normals)
-
-
-def load_mesh(path):
-    """Read what ``Mesh.export`` writes, and ground-truth scans of the same kinds: Wavefront .obj (v / vn / f with a, a/b, a/b/c or
-    a//n corners) and .ply (ascii or binary little-endian).  Polygons with more than three corners are fan-triangulated.
-    Anything else raises a ValueError that names the file."""
-    ext = os.path.splitext(path)[1].lower()
-    if ext not in ('.obj', '.ply'):
-        raise ValueError('load_mesh: %s: unsupported extension %r (supported: .obj, .ply)' % (path, ext))
-    try:
-        mesh = _load_obj(path) if ext == '.obj' else _load_ply(path)
-    except (ValueError, KeyError, IndexError) as e:
-        raise ValueError('load_mesh: %s: %s' % (path, e))
-    if len(mesh.faces) and (mesh.faces.min() < 0 or mesh.faces.max() >= len(mesh.vertices)):
-        raise ValueError('load_mesh: %s: a face refers to a vertex that does not exist' % path)
-    return mesh

@@ -11,6 +11,7 @@ draws of get_chamfer_dist in its order --, then the IoU points.
 import numpy as np
 import torch
 
+from .meshcore import face_cross
 from .meshdist import MeshIndex, _prepare
 
 DEFAULT_THRESHOLDS = (0.005, 0.01, 0.02)   # fractions of the ground truth's bounding-box diagonal
@@ -22,13 +23,9 @@ def _xp(x):
 
 def _unit_face_normals(mesh):
     """Unit normals of a mesh's faces [F, 3]; the normal of a zero-area triangle is the zero vector."""
-    v, f = mesh.vertices, mesh.faces
-    a = v[f[:, 0]]
-    ab, ac = v[f[:, 1]] - a, v[f[:, 2]] - a
-    xp = _xp(v)
-    n = xp.stack([ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1], ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2],
-                  ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]], 1)
-    length = xp.sqrt((n * n).sum(1))
+    xp = _xp(mesh.vertices)
+    n = xp.stack(face_cross(mesh.vertices, mesh.faces), 1)
+    length = xp.sqrt((n * n).sum(1))   # (a reduction: not the order of meshcore.face_areas' nx nx + ny ny + nz nz, and kept as it is)
     return n / xp.where(length > 0.0, length, xp.ones_like(length))[:, None]
 
 

@@ -11,18 +11,16 @@ dtype of the inputs and then converted to float64, in which all the geometry run
 As everywhere in meshdist: a mesh on the device (a MeshIndex, device tensors, or ``device='cuda'``) takes the device path and
 returns device tensors; anything else takes the numpy definition and returns CPU tensors."""
 import functools
-import types
 
 import numpy as np
 import torch
 
 from . import meshdist as md
+from .meshcore import to_numpy
 
 
 def _index(mesh, device):
     """A Mesh, a (vertices, faces) pair, a MeshIndex or a _HostMesh -> MeshIndex or _HostMesh."""
-    if isinstance(mesh, (tuple, list)):
-        mesh = types.SimpleNamespace(vertices=mesh[0], faces=mesh[1])
     return md._prepare(mesh, device, 'mesh')
 
 
@@ -105,7 +103,7 @@ def _sample_textures(textures, atlas, tri, bary, out):
             tex = torch.as_tensor(tex).to(device=tri.device, dtype=torch.float32).contiguous()
             sampled[name] = meshbake.atlas_sample(atlas, tri, bary, tex)
         else:
-            tex = tex.detach().cpu().numpy() if torch.is_tensor(tex) else np.asarray(tex)
+            tex = np.asarray(to_numpy(tex))
             sampled[name] = torch.from_numpy(meshbake.host_atlas_sample(atlas, tri.numpy(), bary.numpy(), tex.astype(np.float32, copy=False)))
     return sampled
 

@@ -66,7 +66,7 @@ import math
 import numpy as np
 import torch
 
-from .stage1.extracting import Mesh
+from .meshcore import Mesh, Phase, device_mesh, face_cross, host_mesh, mesh_parts, on_device, to_numpy
 
 MAX_RESOLUTION = 4096          # == PSN_VC_MAX_RESOLUTION
 MAX_CLUSTERS = (1 << 21) - 1   # == PSN_VC_MAX_CLUSTERS
@@ -114,21 +114,7 @@ def _too_many(n_clusters):
     return ValueError('simplify: %d clusters (at most %d); use a coarser cell' % (n_clusters, MAX_CLUSTERS))
 
 
-def _arrays(vertices, faces):
-    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1, 3))
-    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
-    if not np.isfinite(v).all():
-        raise ValueError('simplify: a vertex coordinate is not finite')
-    if f.shape[0] and (f.min() < 0 or f.max() >= v.shape[0]):
-        raise ValueError('mesh: a face refers to vertex %d of %d' % (int(f.max() if f.max() >= v.shape[0] else f.min()), v.shape[0]))
-    return v, f
-
-
 # ------------------------------------------------------------------------------------------------ host path: the definition
-def _cross(ab, ac):
-    return (ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1], ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2], ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0])
-
-
 def host_cell_keys(v, grid):
     origin, h, dims = grid
     c = [np.minimum(np.maximum(np.floor((v[:, a] - origin[a]) / h), 0.0), float(dims[a] - 1)).astype(np.int64) for a in range(3)]
@@ -201,8 +187,8 @@ def host_quadrics(v, f, cluster, n_clusters):
     index order, each bin starting from 0)."""
     count = np.bincount(cluster, minlength=n_clusters)
     x0 = np.stack([np.bincount(cluster, weights=v[:, a], minlength=n_clusters) for a in range(3)], axis=1) / count[:, None]
-    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
-    n = _cross(b - a, c - a)
+    a = v[f[:, 0]]
+    n = face_cross(v, f)
     k = cluster[f].reshape(-1)                                   # ascending (face, corner)
     n3 = [np.repeat(x, 3) for x in n]
     a3 = np.repeat(a, 3, axis=0)
@@ -244,8 +230,7 @@ def _host_at(v, f, grid, regularisation, resolution, probes, deduplicate=True, c
     keep = host_keep_faces(key) if deduplicate else key >= 0
     x, clamped = host_positions(v, f, cluster, cell_key, grid, regularisation, clamp, minimiser)
     out_g = g[keep]
-    old = _cross(v[f[keep, 1]] - v[f[keep, 0]], v[f[keep, 2]] - v[f[keep, 0]])
-    new = _cross(x[out_g[:, 1]] - x[out_g[:, 0]], x[out_g[:, 2]] - x[out_g[:, 0]])
+    old, new = face_cross(v, f[keep]), face_cross(x, out_g)
     flipped = ((old[0] * new[0] + old[1] * new[1]) + old[2] * new[2]) < 0.0
     used = np.zeros(n_clusters, dtype=bool)
     used[out_g.reshape(-1)] = True
@@ -292,7 +277,7 @@ def host_simplify(vertices, faces, target_faces=None, cell=None, resolution=None
     """-> (vertices float64 [V', 3], faces int64 [F', 3], report).  ``wrong``: deduplicate / clamp / minimiser = False switch one
     rule of the definition off (tests only)."""
     _check_sizes(target_faces, cell, resolution, regularisation)
-    v, f = _arrays(vertices, faces)
+    v, f, _ = host_mesh(vertices, faces, finite='simplify')
     if target_faces is not None and f.shape[0] <= int(target_faces):
         return v, f, _unchanged_report(v.shape[0], f.shape[0])
     if v.shape[0] == 0:
@@ -326,11 +311,10 @@ class _DeviceGrid(object):
 
     def __init__(self, v, f, grid, full, events=None):
         from . import hip
-        from .stage1.extracting import _Phase
         n_v, n_f = v.shape[0], f.shape[0]
         dev = v.device
         self.grid = grid
-        with _Phase(events, 'clusters'):
+        with Phase(events, 'clusters'):
             keys = hip.vc_cell_keys(v, grid)
             self.cell_key_sorted, self.vertex_order = torch.sort(keys, stable=True)
             head = torch.ones(n_v, dtype=torch.bool, device=dev)
@@ -338,7 +322,7 @@ class _DeviceGrid(object):
             self.rank_sorted = torch.cumsum(head, dim=0, dtype=torch.int64) - 1          # the cluster of each sorted vertex
             self.cluster = torch.empty(n_v, dtype=torch.int64, device=dev)
             self.cluster[self.vertex_order] = self.rank_sorted
-        with _Phase(events, 'face keys'):
+        with Phase(events, 'face keys'):
             status = torch.zeros(1, dtype=torch.int32, device=dev)
             self.corner_keys, face_keys, self.g = hip.vc_face_keys(f, self.cluster, status, want_corners=full)
             self.face_key_sorted, self.face_order = torch.sort(face_keys, stable=True)
@@ -351,7 +335,6 @@ class _DeviceGrid(object):
 
 def _device_at(v, f, grid, regularisation, resolution, probes, events=None):
     from . import hip
-    from .stage1.extracting import _Phase
     origin, h, dims = grid
     n_v, n_f = v.shape[0], f.shape[0]
     dev = v.device
@@ -367,17 +350,17 @@ def _device_at(v, f, grid, regularisation, resolution, probes, events=None):
     n_c = d.n_clusters
     if n_c > MAX_CLUSTERS:
         raise _too_many(n_c)
-    with _Phase(events, 'runs'):
+    with Phase(events, 'runs'):
         bounds = torch.arange(n_c + 1, dtype=torch.int64, device=dev)
         vertex_start = torch.searchsorted(d.rank_sorted, bounds)
         corner_sorted = torch.sort(d.corner_keys).values
         corner_start = torch.searchsorted(corner_sorted, bounds * (3 * n_f))
         face_keep = torch.zeros(n_f, dtype=torch.uint8, device=dev)
         face_keep[d.face_order] = d.face_head.to(torch.uint8)
-    with _Phase(events, 'solve'):
+    with Phase(events, 'solve'):
         x, clamped = hip.vc_solve(v, f, d.vertex_order, vertex_start, d.cell_key_sorted, corner_sorted, corner_start, n_c, grid,
                                   float(regularisation))
-    with _Phase(events, 'compaction'):
+    with Phase(events, 'compaction'):
         vertex_keep, flipped = hip.vc_face_flags(v, f, d.g, x, face_keep)
         face_incl, vertex_incl = torch.cumsum(face_keep, dim=0, dtype=torch.int64), torch.cumsum(vertex_keep, dim=0, dtype=torch.int64)
         totals = torch.stack([face_incl[-1], vertex_incl[-1], clamped.sum(), flipped.sum()]).tolist()
@@ -404,7 +387,6 @@ def _device_clusters(v, grid):
 def _device_simplify(v, f, target_faces=None, cell=None, resolution=None, regularisation=1e-3, events=None):
     """host_simplify on device tensors (float64 [V, 3], int64 [F, 3], contiguous) -> (vertices, faces: device tensors, report)."""
     from . import ops
-    from .stage1.extracting import _Phase
     _check_sizes(target_faces, cell, resolution, regularisation)
     ops._hit('MeshSimplify')
     if target_faces is not None and f.shape[0] <= int(target_faces):
@@ -418,7 +400,7 @@ def _device_simplify(v, f, target_faces=None, cell=None, resolution=None, regula
     probes, missed = [], False
     if target_faces is not None:
         def count(n):
-            with _Phase(events, 'probes'):
+            with Phase(events, 'probes'):
                 d = _DeviceGrid(v, f, make_grid(lo, hi, None, n), False)
             return math.inf if d.n_clusters > MAX_CLUSTERS else d.n_faces
         resolution, probes, missed = choose_resolution(int(target_faces), count)
@@ -434,17 +416,12 @@ def simplify_mesh(mesh, target_faces=None, cell=None, resolution=None, regularis
     """``mesh``: anything with .vertices and .faces, or a tuple (vertices, faces[, normals]) -> (Mesh, report); exactly one of
     ``target_faces``, ``cell`` and ``resolution``.  Device tensors, or ``device='cuda'``, take the device path (only the result is
     copied back); otherwise the host path.  Normals do not ride along (an untouched mesh keeps its own)."""
-    from .meshclean import _numpy, _on_device, _to_device
-    if isinstance(mesh, (tuple, list)):
-        vertices, faces = mesh[0], mesh[1]
-        normals = mesh[2] if len(mesh) > 2 else None
-    else:
-        vertices, faces, normals = mesh.vertices, mesh.faces, getattr(mesh, 'vertex_normals', None)
-    if _on_device(vertices, device):
-        v, f, _ = _to_device(vertices, faces, None, device)
+    vertices, faces, normals = mesh_parts(mesh)
+    if on_device(vertices, device):
+        v, f, _ = device_mesh(vertices, faces, None, device)
         v, f, report = _device_simplify(v, f, target_faces, cell, resolution, regularisation)
         v, f = v.cpu().numpy(), f.cpu().numpy()
     else:
-        v, f, report = host_simplify(_numpy(vertices), _numpy(faces), target_faces, cell, resolution, regularisation)
+        v, f, report = host_simplify(to_numpy(vertices), to_numpy(faces), target_faces, cell, resolution, regularisation)
     keep_normals = report.get('unchanged') and normals is not None
-    return Mesh(v, f, vertex_normals=_numpy(normals) if keep_normals else None), report
+    return Mesh(v, f, vertex_normals=to_numpy(normals) if keep_normals else None), report

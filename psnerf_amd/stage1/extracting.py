@@ -46,6 +46,8 @@ import time
 import numpy as np
 import torch
 
+from ..meshcore import Mesh, Phase
+
 PAD_VALUE = -1e6
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _TABLE = None
@@ -223,73 +225,6 @@ def to_world(vertices, n, box_size):
     return box_size * (v - 0.5)
 
 
-# ------------------------------------------------------------------------------------------------ mesh container
-class Mesh(object):
-    """What the extraction returns: vertices float64 [V, 3], faces int64 [F, 3], optional vertex normals.  Stands in for
-    trimesh.Trimesh(vertices, faces, vertex_normals=normals, process=False) as far as extract_mesh.py uses it."""
-
-    def __init__(self, vertices, faces, vertex_normals=None):
-        self.vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
-        self.faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-        self.vertex_normals = None if vertex_normals is None else np.asarray(vertex_normals).reshape(-1, 3)
-
-    @property
-    def is_empty(self):
-        return self.vertices.shape[0] == 0
-
-    def export(self, path):
-        ext = os.path.splitext(path)[1].lower()
-        if ext == '.obj':
-            with open(path, 'w') as f:
-                for v in self.vertices:
-                    f.write('v %.17g %.17g %.17g\n' % tuple(v))
-                if self.vertex_normals is not None:
-                    for v in self.vertex_normals:
-                        f.write('vn %.9g %.9g %.9g\n' % tuple(v))
-                for t in self.faces + 1:
-                    if self.vertex_normals is not None:
-                        f.write('f %d//%d %d//%d %d//%d\n' % (t[0], t[0], t[1], t[1], t[2], t[2]))
-                    else:
-                        f.write('f %d %d %d\n' % tuple(t))
-        elif ext == '.ply':
-            props = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if self.vertex_normals is not None else [])
-            head = ['ply', 'format binary_little_endian 1.0', 'element vertex %d' % self.vertices.shape[0]]
-            head += ['property float %s' % p for p in props]
-            head += ['element face %d' % self.faces.shape[0], 'property list uchar int vertex_indices', 'end_header']
-            vert = self.vertices.astype('<f4')
-            if self.vertex_normals is not None:
-                vert = np.concatenate([vert, self.vertex_normals.astype('<f4')], axis=1)
-            rec = np.empty(self.faces.shape[0], dtype=[('n', 'u1'), ('i', '<i4', (3,))])
-            rec['n'] = 3
-            rec['i'] = self.faces
-            with open(path, 'wb') as f:
-                f.write(('\n'.join(head) + '\n').encode('ascii'))
-                f.write(np.ascontiguousarray(vert).tobytes())
-                f.write(rec.tobytes())
-        else:
-            raise NotImplementedError('Mesh.export: %r (supported: .obj, .ply)' % ext)
-        return path
-
-
-class _Phase(object):
-    """``with _Phase(log, name):`` brackets device work with HIP events when ``log`` is a list (tools/bench_mesh.py)."""
-
-    def __init__(self, log, name):
-        self.log, self.name = log, name
-
-    def __enter__(self):
-        if self.log is not None:
-            self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            self.e0.record()
-        return self
-
-    def __exit__(self, *exc):
-        if self.log is not None and exc[0] is None:
-            self.e1.record()
-            self.log.append((self.name, self.e0, self.e1))
-        return False
-
-
 # ------------------------------------------------------------------------------------------------ the extractor
 class Extractor3D(object):
     """extracting.py:15-52, same constructor and methods."""
@@ -393,13 +328,13 @@ class Extractor3D(object):
         t0 = time.time()
         if torch.is_tensor(occ_hat) and occ_hat.is_cuda:
             from .. import hip
-            with _Phase(self.phase_events, 'marching cubes'):
+            with Phase(self.phase_events, 'marching cubes'):
                 v, f = hip.marching_cubes(occ_hat.contiguous(), threshold, box_size)
             if clean:   # on the device tensors: less is copied back, fewer normals are computed
                 from .. import meshclean
                 torch.cuda.synchronize(occ_hat.device)
                 t1 = time.time()
-                with _Phase(self.phase_events, 'components'):
+                with Phase(self.phase_events, 'components'):
                     v, f, _, report = meshclean._device_clean(v, f, None, self.keep_components, self.min_component_faces, 'faces')
                 torch.cuda.synchronize(occ_hat.device)
                 t0 += self._clean_stats(stats_dict, report, time.time() - t1)   # ('time (marching cubes)' stays what it was)
@@ -408,11 +343,11 @@ class Extractor3D(object):
                 torch.cuda.synchronize(occ_hat.device)
                 t1 = time.time()
                 n_from = f.shape[0]
-                with _Phase(self.phase_events, 'simplify'):
+                with Phase(self.phase_events, 'simplify'):
                     v, f, report = meshsimplify._device_simplify(v, f, target_faces=self.simplify_nfaces)
                 torch.cuda.synchronize(occ_hat.device)
                 t0 += self._simplify_stats(stats_dict, report, n_from, time.time() - t1)
-            with _Phase(self.phase_events, 'copy-back'):
+            with Phase(self.phase_events, 'copy-back'):
                 vertices, faces = v.cpu().numpy(), f.cpu().numpy()
             stats_dict['time (marching cubes)'] = time.time() - t0
         else:
@@ -525,14 +460,14 @@ class Extractor3D(object):
         n_pending = (res0 + 1) ** 3
         n_eval = n_rounds = 0
         while n_pending > 0:
-            with _Phase(self.phase_events, 'collect + evaluate'):
+            with Phase(self.phase_events, 'collect + evaluate'):
                 rows, points = hip.mise_collect(flags, res, box_size, n_pending, counts[0:1])
                 if pack is not None:
                     pack.on_points(points, self.model.octaves_pe, 1.0 / self.model.rescale, out=grid, n_rows_dev=counts[0:1],
                                    out_rows=rows)
                 else:
                     grid[rows] = self.eval_points(points, None, **kwargs).to(torch.float32)
-            with _Phase(self.phase_events, 'refine'):
+            with Phase(self.phase_events, 'refine'):
                 hip.mise_refine(grid, flags, vox, res0, depth, threshold, counts[1:2])
             n_eval += n_pending
             n_rounds += 1
@@ -540,7 +475,7 @@ class Extractor3D(object):
         stats_dict['n_points_evaluated'], stats_dict['n_rounds'] = n_eval, n_rounds
         grid = grid.view(n, n, n)
         self.last_known = (flags[:n * n * n] == 2).view(n, n, n)
-        with _Phase(self.phase_events, 'fill'):
+        with Phase(self.phase_events, 'fill'):
             hip.grid_ffill(grid)
         return grid
 

@@ -48,6 +48,38 @@ def _same_mesh(a, b):
         (a.vertex_normals is None and b.vertex_normals is None) or a.vertex_normals.tobytes() == b.vertex_normals.tobytes())
 
 
+def test_device_mover_takes_every_kind_of_input():
+    """meshcore.device_mesh, which every device path starts with: nothing is launched but copies."""
+    from psnerf_amd.meshcore import device_mesh
+    tet_v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], dtype=np.float64)
+    tet_f = np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]], dtype=np.int64)
+    frozen_v, frozen_f = np.frombuffer(tet_v.tobytes(), dtype=np.float64).reshape(4, 3), np.frombuffer(tet_f.tobytes(), dtype=np.int64).reshape(4, 3)
+    assert not frozen_v.flags.writeable and not frozen_f.flags.writeable
+    placed = device_mesh(tet_v, tet_f, device=DEV)
+    forms = [placed[:2], device_mesh(frozen_v, frozen_f, device=DEV)[:2],
+             device_mesh(torch.from_numpy(tet_v).float(), torch.from_numpy(tet_f).int(), device=DEV)[:2], device_mesh(placed[0], placed[1])[:2],
+             device_mesh(placed[0], placed[1], device=DEV)[:2]]
+    for v, f in forms:
+        assert v.is_cuda and f.is_cuda and v.dtype == torch.float64 and f.dtype == torch.int64 and v.is_contiguous() and f.is_contiguous()
+        assert v.shape == (4, 3) and f.shape == (4, 3) and torch.equal(v, placed[0]) and torch.equal(f, placed[1])
+    assert np.array_equal(placed[0].cpu().numpy(), tet_v) and np.array_equal(placed[1].cpu().numpy(), tet_f) and placed[2] is None
+    for v, f in forms[3:]:                                                        # already in place: no copy
+        assert v.data_ptr() == placed[0].data_ptr() and f.data_ptr() == placed[1].data_ptr()
+    v, f, _ = device_mesh(tet_v, np.zeros((0, 3), dtype=np.int64), device=DEV)
+    assert f.shape == (0, 3) and f.dtype == torch.int64 and f.is_cuda and v.shape == (4, 3)
+    v, f, _ = device_mesh(np.zeros((0, 3)), [], device=DEV)
+    assert v.shape == (0, 3) and f.shape == (0, 3) and v.dtype == torch.float64 and f.dtype == torch.int64
+    n32 = np.arange(12, dtype=np.float32).reshape(4, 3)
+    for normals in (n32, torch.from_numpy(n32), torch.from_numpy(n32).to(DEV)):
+        kept = device_mesh(tet_v, tet_f, normals, device=DEV)[2]                   # meshclean's rule: the bits ride along
+        wide = device_mesh(tet_v, tet_f, normals, device=DEV, widen_normals=True)[2]   # meshbake's rule
+        assert kept.is_cuda and kept.dtype == torch.float32 and kept.cpu().numpy().tobytes() == n32.tobytes()
+        assert wide.is_cuda and wide.dtype == torch.float64 and np.array_equal(wide.cpu().numpy(), n32)
+    assert device_mesh(tet_v, tet_f, n32.astype(np.float16), device=DEV)[2].dtype == torch.float64    # neither float32 nor float64: widened
+    with pytest.raises(ValueError, match=r'^atlas: 3 normals for 4 vertices'):
+        device_mesh(tet_v, tet_f, n32[:3], device=DEV, prefix='atlas')
+
+
 def test_degenerate_sizes():
     none_v, none_f = np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int64)
     labels, table = mc.components(none_v, none_f, device=DEV)

@@ -15,23 +15,18 @@ moves the bytes the two atlas kernels move (points: 60 B written per row; scatte
     python tools/bench_bake.py [--repeats 7] [--warmup 2] [--out profiles/mesh_bake.json]
 """
 import argparse
-import json
 import os
 import socket
 import subprocess
 import sys
 import time
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _stat(xs):
-    xs = [float(x) for x in xs]
-    return {'median_ms': float(np.median(xs)), 'min_ms': min(xs), 'max_ms': max(xs)}
+from benchlib import extracted_mesh, stat as _stat, sum_kernels, sum_phases, write_profile  # noqa: E402
 
 
 def timed(fn, warmup, repeats):
@@ -69,12 +64,7 @@ def measure(net, v, f, T, repeats, warmup):
         del baked
         if it < warmup:
             continue
-        phases, kernels = {}, {}
-        for name, a, b in phase:
-            phases[name] = phases.get(name, 0.0) + a.elapsed_time(b)
-        for name, _units, a, b, _fl in kern:
-            kernels[name] = kernels.get(name, 0.0) + a.elapsed_time(b)
-        runs.append(dict(phases=phases, kernels=kernels, call_ms=e0.elapsed_time(e1), wall_ms=1e3 * wall, peak_mib=peak))
+        runs.append(dict(phases=sum_phases(phase), kernels=sum_kernels(kern), call_ms=e0.elapsed_time(e1), wall_ms=1e3 * wall, peak_mib=peak))
     rows = atlas.F * atlas.K
     channels = 3 + net.nbasis + 3
     out = {'texture': T, 'faces': atlas.F, 'cell': atlas.c, 'rows_per_face': atlas.K, 'rows': rows, 'owned_fraction_of_the_texels': rows / float(T * T),
@@ -124,11 +114,10 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_bake: no GPU (this is a measurement; there is no host fall-back)')
-    from psnerf_amd import hip, meshsimplify, ops
+    from psnerf_amd import meshsimplify, ops
     import psnerf_amd.stage1 as s1
     import psnerf_amd.stage2 as s2
     from psnerf_amd.synthetic import stage1_cfg
-    from psnerf_amd.stage1.extracting import Extractor3D, iso_value
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     geo = s1.NeuralNetwork(stage1_cfg('bear')).to(dev)
@@ -140,10 +129,7 @@ def main():
         except Exception:
             pass
     with ops.strict():
-        ex = Extractor3D(geo, device=dev, resolution0=args.resolution, upsampling_steps=args.upsampling_steps)
-        ex.generate_mesh()
-        v, f = hip.marching_cubes(ex.last_grid.contiguous(), iso_value(ex.threshold), 2 + ex.padding)
-        del ex
+        v, f = extracted_mesh(geo, dev, args.resolution, args.upsampling_steps)
         sv, sf, report = meshsimplify._device_simplify(v, f, target_faces=f.shape[0] // 10)
         out = {'device': torch.cuda.get_device_name(0), 'box': socket.gethostname(), 'parent_commit': commit,
                'grid': '%d^3' % ((args.resolution << args.upsampling_steps) + 1), 'repeats': args.repeats, 'warmup': args.warmup,
@@ -161,11 +147,7 @@ def main():
                    'C-ABI calls; context = the same networks on as many contiguous rows in one call each, and a copy that moves as many '
                    'bytes as psn_atlas_points writes and psn_atlas_scatter reads and writes; peak_device_memory = torch.cuda.max_memory_allocated over one '
                    'call, the mesh, both networks and the workspaces of earlier calls included')
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as fh:
-        json.dump(out, fh, indent=1, sort_keys=True)
-        fh.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':

@@ -23,57 +23,19 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _stat(xs):
-    xs = [float(x) for x in xs]
-    return {'median_ms': float(np.median(xs)), 'min_ms': min(xs), 'max_ms': max(xs)}
+from benchlib import extracted_mesh, stat as _stat, sum_phases, write_profile  # noqa: E402
 
 
-class _Timer(object):
-    def __init__(self):
-        self.events = []
-
-    def __call__(self, name):
-        timer = self
-
-        class _Ctx(object):
-            def __enter__(self):
-                self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                self.e0.record()
-
-            def __exit__(self, *exc):
-                self.e1.record()
-                timer.events.append((name, self.e0, self.e1))
-                return False
-        return _Ctx()
-
-    def collect(self):
-        torch.cuda.synchronize()
-        out = {}
-        for name, e0, e1 in self.events:
-            out[name] = out.get(name, 0.0) + e0.elapsed_time(e1)
-        self.events = []
-        return out
-
-
-def extract(net, dev, steps):
-    from psnerf_amd import hip
-    from psnerf_amd.stage1.extracting import Extractor3D, iso_value
-    ex = Extractor3D(net, device=dev, resolution0=64, upsampling_steps=steps)
-    ex.generate_mesh()
-    return hip.marching_cubes(ex.last_grid.contiguous(), iso_value(ex.threshold), 2 + ex.padding)
-
-
-def one_pass(md, meshes, n, seed, timer, sort=True, counters=None):
-    """One Chamfer evaluation with every phase bracketed -> (chamfer, indices)."""
+def one_pass(md, meshes, n, seed, events, sort=True, counters=None):
+    """One Chamfer evaluation with every phase bracketed (appended to ``events``) -> (chamfer, indices)."""
+    from psnerf_amd.meshcore import Phase
     idx = []
     for v, f in meshes:
         index = md.MeshIndex(v, f, profile=True)
-        for name, e0, e1 in index.build_events:
-            timer.events.append(('index ' + name, e0, e1))
+        events.extend(('index ' + name, e0, e1) for name, e0, e1 in index.build_events)
         idx.append(index)
     rng = np.random.RandomState(seed)
-    with timer('sampler'):
+    with Phase(events, 'sampler'):
         pts = [index.sample_surface(n, rng)[0] for index in idx]
     def query(index, p, n_tests):
         if sort:
@@ -81,7 +43,7 @@ def one_pass(md, meshes, n, seed, timer, sort=True, counters=None):
         from psnerf_amd import hip   # the same kernel on the points as they come: the binding below MeshIndex
         return hip.closest_point(index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over, p,
                                  order=None, n_tests=n_tests)[1]
-    with timer('query'):
+    with Phase(events, 'query'):
         d01 = query(idx[1], pts[0], None if counters is None else counters[1:2])
         d10 = query(idx[0], pts[1], None if counters is None else counters[0:1])
     return float((d01.mean() + d10.mean()) / 2), idx
@@ -101,10 +63,9 @@ def main():
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     net = s1.NeuralNetwork(stage1_cfg('bear')).to(dev)
-    timer = _Timer()
     out = {'device': torch.cuda.get_device_name(0), 'box': socket.gethostname(), 'repeats': args.repeats, 'warmup': args.warmup, 'sizes': {}}
     with ops.strict():
-        meshes = [extract(net, dev, 3), extract(net, dev, 2)]
+        meshes = [extracted_mesh(net, dev, 64, 3), extracted_mesh(net, dev, 64, 2)]
         for n in (10000, 1000000):
             runs = {'sorted': [], 'unsorted': []}
             counters = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -114,8 +75,10 @@ def main():
                     torch.cuda.synchronize()
                     torch.cuda.reset_peak_memory_stats()
                     counters.zero_()
-                    ch, idx = one_pass(md, meshes, n, 0, timer, sort=mapping == 'sorted', counters=counters)
-                    phases = timer.collect()
+                    events = []
+                    ch, idx = one_pass(md, meshes, n, 0, events, sort=mapping == 'sorted', counters=counters)
+                    torch.cuda.synchronize()
+                    phases = sum_phases(events)
                     assert chamfer is None or ch == chamfer, 'the result depends on the run'
                     chamfer = ch
                     if it >= args.warmup:
@@ -148,11 +111,7 @@ def main():
             pass
     out['note'] = ('HIP events on the stream; "index *" = both meshes; "query" = both directions incl. the sort by home cell; memory peak '
                    'includes the two meshes')
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':

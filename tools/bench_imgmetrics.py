@@ -11,7 +11,6 @@ host definition's time for one image pair on this machine's CPU.
     python tools/bench_imgmetrics.py [--repeats 7] [--warmup 2] [--out profiles/img_metrics.json]
 """
 import argparse
-import json
 import os
 import socket
 import sys
@@ -27,9 +26,7 @@ H, W = 512, 612
 STREAM_BYTES_PER_S = 6.29e12     # measured float4 copy rate of an MI355X (79 % of the 8 TB/s of the data sheet)
 
 
-def _stat(xs):
-    xs = [float(x) for x in xs]
-    return {'median_ms': float(np.median(xs)), 'min_ms': min(xs), 'max_ms': max(xs)}
+from benchlib import stat as _stat, write_profile  # noqa: E402
 
 
 def synthetic(B, dev, seed=0):
@@ -106,11 +103,7 @@ def main():
     out['note'] = ('HIP events on the stream around the whole call (kernel launches and the allocation of the outputs); '
                    'evaluate_images = psn_img_metrics + its fixed-order reduce; inten_normalize adds psn_img_scale_sums; full_map also '
                    'writes the float64 [B, H, W, 3] SSIM map')
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':

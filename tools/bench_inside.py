@@ -15,7 +15,6 @@ Nothing gates on these numbers.
     python tools/bench_inside.py [--repeats 7] [--warmup 2] [--out profiles/mesh_inside.json]
 """
 import argparse
-import json
 import os
 import socket
 import sys
@@ -28,7 +27,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tools.bench_chamfer import extract  # noqa: E402
+from benchlib import extracted_mesh, write_profile  # noqa: E402
 from tools.bench_raycast import timed  # noqa: E402
 
 
@@ -51,8 +50,8 @@ def main():
     net = s1.NeuralNetwork(stage1_cfg('bear')).to(dev)
     out = {'device': torch.cuda.get_device_name(0), 'box': socket.gethostname(), 'repeats': args.repeats, 'warmup': args.warmup}
     with ops.strict():
-        v, f = extract(net, dev, 3)
-        coarse = extract(net, dev, 2)
+        v, f = extracted_mesh(net, dev, 64, 3)
+        coarse = extracted_mesh(net, dev, 64, 2)
         index = md.MeshIndex(v, f)
         lo, hi = np.asarray(index.lo), np.asarray(index.hi)
         n = args.points
@@ -101,11 +100,7 @@ def main():
                                'counts_equal_to_the_device': bool(all(np.array_equal(a, b) for a, b in zip(host_counts, dev_counts)))}
     out['note'] = ('HIP events on the stream; "kernel" = psn_mesh_crossings alone on uploaded points, the sort outside the bracket; "whole_call" = '
                    'the public method, the sort by column inside; evaluate_mesh includes both index builds, the host draws and their upload')
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as fh:
-        json.dump(out, fh, indent=1, sort_keys=True)
-        fh.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':

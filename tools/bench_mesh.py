@@ -8,7 +8,6 @@ on_points call over the same number of contiguous points timed in the same run.
     python tools/bench_mesh.py [--repeats 7] [--warmup 2] [--resolution 64] [--upsampling-steps 3] [--out profiles/mesh_extract.json]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -19,10 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _stat(xs):
-    xs = [float(x) for x in xs]
-    return {'median_ms': float(np.median(xs)), 'min_ms': min(xs), 'max_ms': max(xs)}
+from benchlib import stat as _stat, sum_kernels, sum_phases, write_profile  # noqa: E402
 
 
 def main():
@@ -56,12 +52,8 @@ def main():
             kern, hip.PROFILE_EVENTS = hip.PROFILE_EVENTS, None
             if it < args.warmup:
                 continue
-            phases = {}
-            for name, e0, e1 in ex.phase_events:
-                phases[name] = phases.get(name, 0.0) + e0.elapsed_time(e1)
-            for name, _units, e0, e1, _fl in kern:
-                key = 'kernel ' + name
-                phases[key] = phases.get(key, 0.0) + e0.elapsed_time(e1)
+            phases = sum_phases(ex.phase_events)
+            phases.update(('kernel ' + name, ms) for name, ms in sum_kernels(kern).items())
             runs.append(dict(phases=phases, wall_ms=1e3 * wall, stats=stats, n_vertices=len(mesh.vertices), n_faces=len(mesh.faces),
                              peak_mib=torch.cuda.max_memory_allocated() / 2.0 ** 20))
         # the yardstick: the same pack over the same number of CONTIGUOUS points, gathered outputs
@@ -95,11 +87,7 @@ def main():
         'note': 'phases without the "kernel" prefix partition the device work of one extraction (HIP events on the stream); "kernel *" '
                 'entries are the brackets around single C-ABI launches inside them (mlp_infer = all rounds summed)',
     }
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':

@@ -20,10 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _stat(xs):
-    xs = [float(x) for x in xs]
-    return {'median_ms': float(np.median(xs)), 'min_ms': min(xs), 'max_ms': max(xs)}
+from benchlib import extracted_mesh, stat as _stat, sum_phases, write_profile  # noqa: E402
 
 
 def octahedra(count, seed=0, radius=0.004, box=1.1):
@@ -50,11 +47,8 @@ def measure(v, f, repeats, warmup, copy_gb_per_s):
         kern, hip.PROFILE_EVENTS = hip.PROFILE_EVENTS, None
         if it < warmup:
             continue
-        phases = {}
-        for name, e0, e1 in events:
-            phases[name] = phases.get(name, 0.0) + e0.elapsed_time(e1)
         kernels = dict((name, (e0.elapsed_time(e1), units)) for name, units, e0, e1, _fl in kern)
-        runs.append(dict(phases=phases, kernels=kernels, wall_ms=1e3 * wall))
+        runs.append(dict(phases=sum_phases(events), kernels=kernels, wall_ms=1e3 * wall))
     kernels = {}
     for name in sorted(runs[0]['kernels']):
         ms, nbytes = _stat([r['kernels'][name][0] for r in runs]), runs[0]['kernels'][name][1]
@@ -83,17 +77,14 @@ def main():
     ap.add_argument('--pieces', type=int, default=4096)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'mesh_clean.json'))
     args = ap.parse_args()
-    from psnerf_amd import hip, ops
+    from psnerf_amd import ops
     import psnerf_amd.stage1 as s1
     from psnerf_amd.synthetic import stage1_cfg
-    from psnerf_amd.stage1.extracting import Extractor3D, iso_value
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     net = s1.NeuralNetwork(stage1_cfg('bear')).to(dev)
     with ops.strict():
-        ex = Extractor3D(net, device=dev, resolution0=args.resolution, upsampling_steps=args.upsampling_steps)
-        ex.generate_mesh()
-        v, f = hip.marching_cubes(ex.last_grid.contiguous(), iso_value(ex.threshold), 2 + ex.padding)
+        v, f = extracted_mesh(net, dev, args.resolution, args.upsampling_steps)
         # the yardstick of the byte counts: a device-to-device copy of 256 MiB (read + write), timed here
         src = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
         copies = []
@@ -121,11 +112,7 @@ def main():
                    'each contain one host read); kernels = the brackets around single C-ABI calls with the bytes they must move '
                    '(psnerf_amd/hip.py), against a 256 MiB device-to-device copy timed in the same run; labelling is one pass, no rounds; '
                    'host_definition_ms = meshclean.host_clean (numpy) on the same box, 3 runs')
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as fh:
-        json.dump(out, fh, indent=1, sort_keys=True)
-        fh.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':

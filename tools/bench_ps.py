@@ -9,7 +9,6 @@ definition on this machine's CPU (once; --no-host skips it), whose result is als
     python tools/bench_ps.py [--repeats 7] [--warmup 2] [--out profiles/ps_normals.json]
 """
 import argparse
-import json
 import os
 import socket
 import sys
@@ -24,9 +23,7 @@ sys.path.insert(0, ROOT)
 H, W, L = 512, 612, 96
 
 
-def _stat(xs):
-    xs = [float(x) for x in xs]
-    return {'median_ms': float(np.median(xs)), 'min_ms': min(xs), 'max_ms': max(xs)}
+from benchlib import stat as _stat, write_profile  # noqa: E402
 
 
 def synthetic(dev, seed=0):
@@ -127,11 +124,7 @@ def main():
             'light_intensity_max_relative_difference': float(np.abs(d_e / h_e - 1.0).max()), 'light_intensity_gate': N * 2.0 ** -50}
     out['note'] = ('HIP events on the stream around the whole call; ps_normals writes into preallocated outputs, the other entries allocate '
                    'theirs; estimate_one_round = normals + intensities through psnerf_amd.photostereo.estimate')
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':

@@ -14,7 +14,6 @@ ray set, scaled to nothing: it is reported as seconds per 1 000 rays.  Nothing g
     python tools/bench_raycast.py [--repeats 7] [--warmup 2] [--out profiles/mesh_raycast.json]
 """
 import argparse
-import json
 import os
 import socket
 import sys
@@ -26,7 +25,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tools.bench_chamfer import _stat, extract  # noqa: E402
+from benchlib import extracted_mesh, stat as _stat, write_profile  # noqa: E402
 
 
 def timed(fn, warmup, repeats):
@@ -64,7 +63,7 @@ def main():
     H, W, n_points, n_lights = 512, 612, 20000, 96
     out = {'device': torch.cuda.get_device_name(0), 'box': socket.gethostname(), 'repeats': args.repeats, 'warmup': args.warmup}
     with ops.strict():
-        v, f = extract(net, dev, 3)
+        v, f = extracted_mesh(net, dev, 64, 3)
         index = md.MeshIndex(v, f)
         raw = lambda o, d, t_min, t_max, order, any_hit, n_tests=None: hip.ray_cast(
             index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over, o, d, t_min, t_max, order=order,
@@ -123,11 +122,7 @@ def main():
     out.update({'view_512x612': view, 'shadow_20k_x_96': shadow, 'numpy_definition': host})
     out['note'] = ('HIP events on the stream; "whole_call" = the public function (ray set-up, the sort by entry cell where there is one, the '
                    'kernel, the maps); "kernel" = psn_ray_cast alone on prepared rays in the order the public function uses')
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as fh:
-        json.dump(out, fh, indent=1, sort_keys=True)
-        fh.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':

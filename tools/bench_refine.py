@@ -22,10 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _stat(xs):
-    xs = [float(x) for x in xs]
-    return {'median_ms': float(np.median(xs)), 'min_ms': min(xs), 'max_ms': max(xs)}
+from benchlib import stat as _stat  # noqa: E402
 
 
 def _timed(fn, repeats, warmup, inner=1):

@@ -24,10 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _stat(xs):
-    xs = [float(x) for x in xs]
-    return {'median_ms': float(np.median(xs)), 'min_ms': min(xs), 'max_ms': max(xs)}
+from benchlib import extracted_mesh, stat as _stat, sum_kernels, sum_phases, write_profile  # noqa: E402
 
 
 def measure(v, f, repeats, warmup, host_runs, **size):
@@ -43,12 +40,7 @@ def measure(v, f, repeats, warmup, host_runs, **size):
         kern, hip.PROFILE_EVENTS = hip.PROFILE_EVENTS, None
         if it < warmup:
             continue
-        phases, kernels = {}, {}
-        for name, e0, e1 in events:
-            phases[name] = phases.get(name, 0.0) + e0.elapsed_time(e1)
-        for name, _units, e0, e1, _fl in kern:
-            kernels[name] = kernels.get(name, 0.0) + e0.elapsed_time(e1)
-        runs.append(dict(phases=phases, kernels=kernels, wall_ms=1e3 * wall))
+        runs.append(dict(phases=sum_phases(events), kernels=sum_kernels(kern), wall_ms=1e3 * wall))
     hv, hf = v.cpu().numpy(), f.cpu().numpy()
     host = []
     for _ in range(host_runs):
@@ -79,21 +71,15 @@ def main():
     ap.add_argument('--host-runs', type=int, default=2)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'mesh_simplify.json'))
     args = ap.parse_args()
-    from psnerf_amd import hip, meshsimplify, ops
+    from psnerf_amd import meshsimplify, ops
     from psnerf_amd.meshdist import MeshIndex, get_surface_dist
     import psnerf_amd.stage1 as s1
     from psnerf_amd.synthetic import stage1_cfg
-    from psnerf_amd.stage1.extracting import Extractor3D, iso_value
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     net = s1.NeuralNetwork(stage1_cfg('bear')).to(dev)
-
-    def extract(steps):
-        ex = Extractor3D(net, device=dev, resolution0=args.resolution, upsampling_steps=steps)
-        ex.generate_mesh()
-        return hip.marching_cubes(ex.last_grid.contiguous(), iso_value(ex.threshold), 2 + ex.padding)
     with ops.strict():
-        v, f = extract(args.upsampling_steps)
+        v, f = extracted_mesh(net, dev, args.resolution, args.upsampling_steps)
         tenth = f.shape[0] // 10
         out = {'device': torch.cuda.get_device_name(0), 'grid': '%d^3' % ((args.resolution << args.upsampling_steps) + 1),
                'repeats': args.repeats, 'warmup': args.warmup,
@@ -101,7 +87,7 @@ def main():
                'fixed_resolution': measure(v, f, args.repeats, args.warmup, args.host_runs, resolution=args.resolution_fixed),
                'coarse_resolution': measure(v, f, args.repeats, args.warmup, args.host_runs, resolution=args.resolution_coarse)}
         # quality: the fine mesh against its simplification to a quarter of its faces, and against the extraction one step coarser
-        coarse_v, coarse_f = extract(args.upsampling_steps - 1)
+        coarse_v, coarse_f = extracted_mesh(net, dev, args.resolution, args.upsampling_steps - 1)
         quarter = f.shape[0] // 4
         simple_v, simple_f, report = meshsimplify._device_simplify(v, f, target_faces=quarter)
         fine, simple, coarse = MeshIndex(v, f), MeshIndex(simple_v, simple_f), MeshIndex(coarse_v, coarse_f)
@@ -129,11 +115,7 @@ def main():
                    '"compaction" (psn_vc_face_flags, two scans, the totals read, psn_cc_compact); kernel_launches = the brackets around '
                    'single C-ABI calls summed over the call (probes included); host_definition_ms = meshsimplify.host_simplify (numpy) on '
                    'the same box; quality = mean distance of surface samples (meshdist.get_surface_dist), world units, box edge 2.4')
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as fh:
-        json.dump(out, fh, indent=1, sort_keys=True)
-        fh.write('\n')
-    print(json.dumps(out))
+    write_profile(args.out, out)
 
 
 if __name__ == '__main__':
