@@ -212,18 +212,18 @@ def measure(hip, ref, truth):
                 n_tensors=len(live), bad=bad)
 
 
-def report_line(what, m):
+def report_line(what, m, prefix='step-grad'):
     rt = m['hip_t'] / (FACTOR * m['E_t']) if m['E_t'] > 0 else float('nan')
     rr = m['hip_r'] / (FACTOR * m['E_r']) if m['E_r'] > 0 else float('nan')
-    return ('step-grad %-18s tensors %2d | E_t %.2e (%s) E_r %.2e (%s) | hip e_t %.2e = %.2f of allowance (%s) | hip e_r %.2e = %.2f of allowance (%s)'
-            % (what, m['n_tensors'], m['E_t'], m['ref_t_name'], m['E_r'], m['ref_r_name'], m['hip_t'], rt, m['hip_t_name'],
+    return ('%s %-18s tensors %2d | E_t %.2e (%s) E_r %.2e (%s) | hip e_t %.2e = %.2f of allowance (%s) | hip e_r %.2e = %.2f of allowance (%s)'
+            % (prefix, what, m['n_tensors'], m['E_t'], m['ref_t_name'], m['E_r'], m['ref_r_name'], m['hip_t'], rt, m['hip_t_name'],
                m['hip_r'], rr, m['hip_r_name']))
 
 
-def check(hip, ref, truth, what):
+def check(hip, ref, truth, what, prefix='step-grad'):
     """The gate of the module docstring; prints one line per case and returns the figures."""
     m = measure(hip, ref, truth)
-    print(report_line(what, m))
+    print(report_line(what, m, prefix))
     assert not m['bad'], '%s: %d violation(s) of the gradient gate:\n  %s' % (what, len(m['bad']), '\n  '.join(m['bad']))
     return m
 
