@@ -1175,6 +1175,41 @@ int psn_atlas_fill(float fill, int C, int T, int cell, int64_t n_faces, void* te
 int psn_atlas_sample(const int64_t* face, const double* bary, int64_t n_queries, const float* texture, int C, int T, int cell,
                      int64_t n_faces, double* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Silhouette carving: dilated object masks, the visual-hull test of points and of the lattice of a value grid (csrc/hull.hip; the
+ * numpy definition, which is THE definition, is psnerf_amd/hull.py: host_dilate, host_project, host_carve_points, host_carve_grid).
+ *   masks      bytes [V, H, W], non-0 = set; V, H, W >= 1.
+ *   views      double [V, 16] on the device: world_mat[:3, :3] row-major (9), world_mat[:3, 3] (3), K[0, 0], K[0, 2], K[1, 2], 0
+ *              (world_mat = camera to world, K in pixel units; hull._views builds the table).
+ *
+ * psn_mask_dilate: half_widths = a HOST table of 2 r + 1 half-widths w[dy], dy = -r .. r, 0 <= w <= r <= PSN_HULL_MAX_RADIUS;
+ *   out[v, y, x] = OR over dy, |dx| <= w[dy] of the mask at (y + dy, x + dx), bytes 0 / 1, where a pixel outside the image has the
+ *   value ``border``.  invert = 1: the input is negated before and the output after (with border = 1: the erosion).  workspace:
+ *   psn_mask_dilate_workspace(V, H, W) 8-byte words on the device (-1 on a bad argument), the bit-packed rows.  Exact for every size.
+ * psn_hull_points: points [n_points, 3], PSN_HULL_F32 (widened exactly) or PSN_HULL_F64.  Per point and view, in float64, each
+ *   product and sum one operation: d = p - o; x_c = (d0 R[0, c] + d1 R[1, c]) + d2 R[2, c]; u = K[0, 2] + K[0, 0] (x_0 / x_2),
+ *   v = K[1, 2] + K[0, 0] (x_1 / x_2); the image contains the point if x_2 > 0, 0 <= floor(u + 0.5) < W and 0 <= floor(v + 0.5) < H.
+ *   carved_by int32 [n_points] = the lowest view whose image contains the point and whose mask is 0 at (floor(v + 0.5), floor(u + 0.5)),
+ *   -2 if no image contains it, else -1; keep bytes [n_points] = (carved_by == -1).  The views are taken PSN_HULL_VIEW_CHUNK at a
+ *   time, chained inside the launch: V has no upper bound.
+ * psn_hull_grid: the same for the lattice point (axis[x], axis[y], axis[z]) of every element of grid float [n, n, n] (x-major; axis
+ *   double [n]): ``value`` is stored where the point is not kept, no other element is written; the number stored is ADDED to *count
+ *   (the caller zeroes it).  2 <= n <= PSN_MESH_MAX_RESOLUTION + 1.
+ * Errors: PSN_E_ARG for null pointers, V < 1, H or W < 1, n out of range, r out of range, border or invert not 0 / 1, a negative
+ *   half-width or one above r, an unknown point_type; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_HULL_MAX_RADIUS 64
+#define PSN_HULL_VIEW_CHUNK 32
+#define PSN_HULL_F32 0
+#define PSN_HULL_F64 1
+int64_t psn_mask_dilate_workspace(int V, int H, int W);
+int psn_mask_dilate(const unsigned char* masks, int V, int H, int W, const int32_t* half_widths, int r, int border, int invert,
+                    unsigned long long* workspace, unsigned char* out, void* stream);
+int psn_hull_points(const void* points, int point_type, int64_t n_points, const double* views, int V, const unsigned char* masks, int H,
+                    int W, unsigned char* keep, int32_t* carved_by, void* stream);
+int psn_hull_grid(float* grid, int n, const double* axis, const double* views, int V, const unsigned char* masks, int H, int W, float value,
+                  unsigned long long* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2067,3 +2067,75 @@ def atlas_sample(face, bary, texture, cell, n_faces, out=None):
         _check(_lib.psn_atlas_sample(_eptr(face, texture), _eptr(bary, texture), Q, tp, C, T, int(cell), int(n_faces), _eptr(out, texture),
                                      _stream()), 'atlas_sample')
     return out
+
+
+# --------------------------------------------------------------------------- silhouette carving (csrc/hull.hip)
+def _hull_masks(what, masks):
+    """A uint8 [V, H, W] device tensor of masks -> (pointer, V, H, W)."""
+    ptr = _tptr(masks, '%s: masks' % what, torch.uint8)
+    if masks.dim() != 3 or min(masks.shape) < 1:
+        raise RuntimeError('%s: masks [V, H, W] (at least 1 x 1 x 1) expected, got %s' % (what, tuple(masks.shape)))
+    return ptr, int(masks.shape[0]), int(masks.shape[1]), int(masks.shape[2])
+
+
+def _hull_views(what, views, V, device):
+    ptr = _tptr(views, '%s: views' % what, torch.float64)
+    if tuple(views.shape) != (V, 16) or views.device != device:
+        raise RuntimeError('%s: views [%d, 16] on the masks\' device expected, got %s' % (what, V, tuple(views.shape)))
+    return ptr
+
+
+def mask_dilate(masks, half_widths, border=0, invert=False, out=None):
+    """psn_mask_dilate: masks uint8 [V, H, W] (non-0 = set), half_widths = a host table of 2 r + 1 integers -> uint8 0 / 1 [V, H, W];
+    ``invert``: negate the input before and the output after (with border = 1: the erosion)."""
+    mp, V, H, W = _hull_masks('mask_dilate', masks)
+    table = [int(w) for w in half_widths]
+    if len(table) % 2 != 1:
+        raise RuntimeError('mask_dilate: a table of 2 r + 1 half-widths expected, got %d' % len(table))
+    if any(not -2 ** 31 <= w < 2 ** 31 for w in table):
+        raise RuntimeError('mask_dilate: a half-width outside the 32-bit range')
+    n = int(_lib.psn_mask_dilate_workspace(V, H, W))
+    if n < 0:
+        raise RuntimeError('psn_mask_dilate_workspace(%d, %d, %d) refused' % (V, H, W))
+    packed = torch.empty(n, dtype=torch.int64, device=masks.device)
+    out = _out(out, (V, H, W), masks, 'mask_dilate: out', torch.uint8)
+    with _Prof('mask_dilate', 2 * V * H * W):
+        _check(_lib.psn_mask_dilate(mp, V, H, W, (ctypes.c_int32 * len(table))(*table), (len(table) - 1) // 2, int(border), int(bool(invert)),
+                                    packed.data_ptr(), out.data_ptr(), _stream()), 'mask_dilate')
+    return out
+
+
+def hull_points(points, views, masks, out=None):
+    """psn_hull_points: points float32 or float64 [Q, 3], views float64 [V, 16] (hull._views), masks uint8 [V, H, W] ->
+    (keep uint8 [Q], carved_by int32 [Q]); ``out``: the two, preallocated."""
+    mp, V, H, W = _hull_masks('hull_points', masks)
+    _tptr(points, 'hull_points: points', (torch.float32, torch.float64))
+    if points.dim() != 2 or points.shape[1] != 3 or points.device != masks.device:
+        raise RuntimeError('hull_points: points [Q, 3] on the masks\' device expected, got %s' % (tuple(points.shape),))
+    Q = int(points.shape[0])
+    o = out if out is not None else (None, None)
+    keep = _out(o[0], (Q,), masks, 'hull_points: keep', torch.uint8)
+    carved_by = _out(o[1], (Q,), masks, 'hull_points: carved_by', torch.int32)
+    with _Prof('hull_points', Q):
+        _check(_lib.psn_hull_points(_eptr(points, masks), HULL_F32 if points.dtype == torch.float32 else HULL_F64, Q,  # noqa: F821
+                                    _hull_views('hull_points', views, V, masks.device), V, mp, H, W, _eptr(keep, masks),
+                                    _eptr(carved_by, masks), _stream()), 'hull_points')
+    return keep, carved_by
+
+
+def hull_grid(grid, axis, views, masks, value=-30.0):
+    """psn_hull_grid, in place on grid float32 [n, n, n]: axis float64 [n], views float64 [V, 16], masks uint8 [V, H, W] -> the number
+    of elements set to ``value``, int64 [1] on the device."""
+    mp, V, H, W = _hull_masks('hull_grid', masks)
+    gp = _tptr(grid, 'hull_grid: grid')
+    n = int(grid.shape[0]) if grid.dim() == 3 else 0
+    if tuple(grid.shape) != (n, n, n) or grid.device != masks.device:
+        raise RuntimeError('hull_grid: a cubic grid [n, n, n] on the masks\' device expected, got %s' % (tuple(grid.shape),))
+    ap = _tptr(axis, 'hull_grid: axis', torch.float64)
+    if tuple(axis.shape) != (n,) or axis.device != masks.device:
+        raise RuntimeError('hull_grid: axis [%d] on the masks\' device expected, got %s' % (n, tuple(axis.shape)))
+    count = torch.zeros(1, dtype=torch.int64, device=masks.device)
+    with _Prof('hull_grid', 4 * grid.numel()):
+        _check(_lib.psn_hull_grid(gp, n, ap, _hull_views('hull_grid', views, V, masks.device), V, mp, H, W, float(value), count.data_ptr(),
+                                  _stream()), 'hull_grid')
+    return count

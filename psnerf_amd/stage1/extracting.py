@@ -26,6 +26,11 @@ Clean-up (not in the reference; opt-in): ``Extractor3D(..., keep_components=K, m
 Simplification (the lineage's ``simplify_nfaces``, which UNISURF and the reference dropped with its native library; opt-in):
   ``Extractor3D(..., simplify_nfaces=N)`` reduces the mesh to at most N faces by quadric vertex clustering (psnerf_amd/meshsimplify.py;
   on the device csrc/meshsimplify.hip), after the clean-up and before the copy-back and the normals.  None (the default) = off.
+Carving (the reference's ``mask_loader``, extracting.py:120-127, with the project's projection; opt-in): ``Extractor3D(..., carve=hull)``
+  with a ``psnerf_amd.hull.VisualHull`` sets the dense grid to -30 where a lattice point lies in no image, or where some image that
+  contains it shows background in its dilated mask: after to_dense (and in the upsampling_steps = 0 branch), before ``clip``.  On the
+  device grid csrc/hull.hip:psn_hull_grid, on the host path's numpy grid the definition (hull.host_carve_grid).  None (the default) =
+  off: every launch, stat and result is what it was.
 Vertex refinement (extracting.py:237-323): ``Extractor3D.refine_mesh(mesh, steps=N)`` / tools/refine_mesh.py run the reference's
   RMSprop refinement of the vertices against the field (``refine_loss`` / ``refine_vertices`` below).  The reference's method calls
   ``self.model.decoder``, which its own NeuralNetwork does not have, so it cannot run there; it is restated with
@@ -37,7 +42,8 @@ Not implemented, and refused loudly:
     ``refine_mesh`` on the extracted mesh, or tools/refine_mesh.py on the written file;
   ``mask_loader`` (extracting.py:326-377): the reference's filter_points assumes UNISURF's world -> NDC matrices, while the
     reference's own loader supplies camera-to-world poses and a pixel-unit K (stage1/dataloading/dataset.py:125-127), so a faithful
-    port would carve with the wrong projection on this project's data.
+    port would carve with the wrong projection on this project's data.  ``carve=VisualHull.from_loader(mask_loader)`` is the same rule
+    with the projection of this project's camera.
 """
 import os
 import re
@@ -231,7 +237,7 @@ class Extractor3D(object):
 
     def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0, device=None, resolution0=16,
                  upsampling_steps=3, with_normals=False, padding=0.4, refine_max_faces=10000, keep_components=None,
-                 min_component_faces=0, simplify_nfaces=None):
+                 min_component_faces=0, simplify_nfaces=None, carve=None):
         if device is None and isinstance(model, torch.nn.Module):
             device = next(model.parameters()).device   # (the reference leaves the model where it is; so do we, and follow it)
         self.model = model.to(device) if (model is not None and hasattr(model, 'to')) else model
@@ -249,6 +255,8 @@ class Extractor3D(object):
         self.min_component_faces = min_component_faces
         # simplification (meshsimplify.py): quadric vertex clustering to at most this many faces, after the clean-up; None = off
         self.simplify_nfaces = simplify_nfaces
+        # carving (hull.py): a VisualHull whose dilated masks carve the dense grid before marching cubes; None = off
+        self.carve = carve
         self.last_grid = None   # the dense value grid of the last generate_* call (device tensor or numpy array)
         self.phase_events = None  # a list: (phase, start event, end event) of the device phases are appended (measurement runs)
         self.last_known = None  # which of its points were evaluated (bool, same shape; None without upsampling: all of them)
@@ -272,7 +280,8 @@ class Extractor3D(object):
         if mask_loader is not None:
             raise NotImplementedError('Extractor3D: mask_loader (carving by dilated image masks, reference extracting.py:120-127, '
                                       '326-377) is not implemented: its projection assumes world -> NDC matrices, the data '
-                                      'loader supplies camera-to-world poses and a pixel-unit K')
+                                      'loader supplies camera-to-world poses and a pixel-unit K.  The same rule with this project\'s '
+                                      'projection: Extractor3D(..., carve=psnerf_amd.hull.VisualHull.from_loader(mask_loader))')
         kwargs.setdefault('clip', False)
         threshold = iso_value(self.threshold)
         box_size = 2 + self.padding
@@ -293,6 +302,12 @@ class Extractor3D(object):
         if on_device:
             torch.cuda.synchronize(self.device)
         stats_dict['time (eval points)'] = time.time() - t0
+        if self.carve is not None:                                                 # extracting.py:120-127 (and hull.py on the projection)
+            t1 = time.time()
+            n = value_grid.shape[0]
+            with Phase(self.phase_events, 'carve'):
+                stats_dict['n_points_carved'] = self.carve.carve_grid(value_grid, box_size * torch.linspace(-0.5, 0.5, n))
+            stats_dict['time (carve)'] = time.time() - t1
         if kwargs['clip']:                                                         # extracting.py:130-132
             n = value_grid.shape[0]
             z = box_size * torch.linspace(-0.5, 0.5, n)                            # the z coordinate of make_3d_grid

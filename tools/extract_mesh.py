@@ -4,13 +4,17 @@
     python tools/extract_mesh.py --obj_name bear --expname test_1 [--exp_folder out] [--test_out_dir test_out]
                                  [--load_iter N] [--upsampling-steps S] [--mesh_extension obj|ply] [--clip]
                                  [--keep-components K] [--min-component-faces N] [--simplify-nfaces N]
+                                 [--carve-masks DIR --cameras params.json [--carve-radius 12] [--views 1 5 9]]
 
 reads <exp_folder>/<obj_name>/<expname>/config.yaml and models/model[_N].pt, writes <test_out_dir>/<obj_name>/<expname>/mesh.<ext>.
 On a GPU the whole extraction runs on the device (psnerf_amd/stage1/extracting.py); --no-cuda takes the numpy host path with the
 model evaluated by the CPU oracle.  --keep-components K / --min-component-faces N (not in the reference; off when absent) keep the K
 largest connected components of the mesh among those with at least N faces (psnerf_amd/meshclean.py): the floaters and inner shells
 of a field trained from few views go before the mesh is written.  --simplify-nfaces N (off when absent) then reduces the mesh to at
-most N faces by quadric vertex clustering (psnerf_amd/meshsimplify.py)."""
+most N faces by quadric vertex clustering (psnerf_amd/meshsimplify.py).  --carve-masks DIR --cameras params.json (off when absent)
+carve the dense value grid with the dataset's object masks DIR/view_VV.png before marching cubes (psnerf_amd/hull.py): a lattice point
+that lies in no image, or that some image shows as background after its mask was dilated by disk(--carve-radius), is set to -30 --
+the reference's mask_loader rule with this project's projection.  --views: the view numbers (from 1) to carve with (default: all)."""
 import argparse
 import os
 import sys
@@ -38,7 +42,13 @@ def main(argv=None):
     parser.add_argument('--keep-components', type=int, default=None, help='keep the K largest connected components')
     parser.add_argument('--min-component-faces', type=int, default=0, help='drop connected components with fewer faces')
     parser.add_argument('--simplify-nfaces', type=int, default=None, help='simplify the mesh to at most this many faces')
+    parser.add_argument('--carve-masks', type=str, default=None, help='directory of view_VV.png object masks to carve the grid with')
+    parser.add_argument('--cameras', type=str, default=None, help='the dataset\'s params.json (with --carve-masks)')
+    parser.add_argument('--carve-radius', type=int, default=12, help='radius of the disk the masks are dilated by')
+    parser.add_argument('--views', type=int, nargs='*', default=None, help='view numbers from 1 to carve with (default: all)')
     args = parser.parse_args(argv)
+    if (args.carve_masks is None) != (args.cameras is None):
+        parser.error('--carve-masks and --cameras go together')
 
     torch.manual_seed(0)
     from psnerf_amd.checkpoints import CheckpointIO
@@ -54,11 +64,16 @@ def main(argv=None):
         from psnerf_amd.stage1 import NeuralNetwork
     else:
         from oracle.stage1 import NeuralNetwork  # the same state_dict keys, plain torch on the host
+    carve = None
+    if args.carve_masks is not None:
+        from psnerf_amd import hull
+        carve = hull.VisualHull.from_params(args.cameras, args.carve_masks, views=args.views, footprint=hull.disk_footprint(args.carve_radius),
+                                            device=device if is_cuda else None)
     model = NeuralNetwork(cfg)
     CheckpointIO(os.path.join(out_dir, 'models'), model=model).load('model_%d.pt' % args.load_iter if args.load_iter else 'model.pt')
     generator = Extractor3D(model, resolution0=cfg['extraction']['resolution'], upsampling_steps=cfg['extraction']['upsampling_steps'],
                             refinement_step=max(args.refinement_step, 0), device=device, keep_components=args.keep_components,
-                            min_component_faces=args.min_component_faces, simplify_nfaces=args.simplify_nfaces)
+                            min_component_faces=args.min_component_faces, simplify_nfaces=args.simplify_nfaces, carve=carve)
     model.eval()
     test_out_path = os.path.join(args.test_out_dir, args.obj_name, args.expname)
     os.makedirs(test_out_path, exist_ok=True)
@@ -68,6 +83,8 @@ def main(argv=None):
     mesh.export(mesh_out_file)
     print('%s: %d vertices, %d faces, %d points evaluated in %d rounds, %.2f s' % (
         mesh_out_file, len(mesh.vertices), len(mesh.faces), stats['n_points_evaluated'], stats['n_rounds'], time.time() - t0))
+    if 'n_points_carved' in stats:
+        print('%d lattice points carved by the masks of %d views' % (stats['n_points_carved'], carve.views.shape[0]))
     if 'n_components' in stats:
         print('%d connected components, %d faces removed' % (stats['n_components'], stats['n_faces_removed']))
     if 'n_faces_simplified_from' in stats:
