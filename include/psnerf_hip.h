@@ -940,6 +940,37 @@ int psn_ray_cast(const PsnTriGrid* grid, const double* vertices, const int64_t* 
                  unsigned char* hit, long long* n_tests, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Occlusion of surface rows by the mesh, over the same index (csrc/meshocclude.hip; the float64 numpy definition is
+ * psnerf_amd/meshocclude.py:host_occlusion_rows): per row (a point and a normal) the K rays of a direction table are formed in
+ * registers and walked through the grid by psn_ray_cast's own any-hit walk (csrc/meshray.h), so no ray is ever written to memory.
+ * The reference has no such query.  grid, vertices, faces, cell_start, list, over_list, n_over: as psn_closest_point takes them.
+ *
+ * psn_occlusion_rows: points / normals float64 [R, 3], table float64 [K, 3], 1 <= K <= PSN_OCC_MAX_DIRS.  A row whose point or normal
+ *   has a non-finite component, or whose normal is zero, casts nothing: hits = -1, visible = 0, ao = NaN, bent = 0, words = 0.
+ *   Otherwise the origin is o = p + bias n (the products, then the sums) and direction k, (x, y, z) = table[k], is
+ *     PSN_OCC_LOCAL  d = (x t + y b) + z n per component, (t, b) the branchless basis of Duff et al. about n:  s = n_z >= 0 ? 1 : -1,
+ *                    a = -1 / (s + n_z), q = (n_x n_y) a, t = (1 + (s (n_x n_x)) a, s q, (-s) n_x), b = (q, s + (n_y n_y) a, -n_y);
+ *                    every direction is cast;
+ *     PSN_OCC_WORLD  d = table[k]; cast only when it faces the normal, (n0 d0 + n1 d1) + n2 d2 > 0.
+ *   A cast direction is blocked when psn_ray_cast in mode PSN_RAY_ANY_HIT with t_min = 0 and this t_max reports a hit for (o, d).
+ *   hits int32 [R] = the cast directions that are blocked; visible int32 [R] = those that are not; ao float64 [R] = 1 - hits / K'
+ *   with K' = hits + visible (1 when K' = 0); bent float64 [R, 3] = the sum of the unblocked cast d in index order, divided by its
+ *   length sqrt((m0 m0 + m1 m1) + m2 m2), zero where that is not > 0; words int32 [R, (K + 31) / 32] or null: bit k % 32 of word
+ *   k / 32 is set iff direction k was cast and not blocked.  All arithmetic is float64 without contraction in the order written,
+ *   so every output is bitwise reproducible and equal to the definition's.  n_tests: null, or an int64 counter to which the
+ *   number of ray-triangle tests is added.  R = 0 is a no-op.
+ * Errors: PSN_E_ARG for null pointers, F, R or K out of range, a bad PsnTriGrid, an unknown mode, a bias that is not finite,
+ *   t_max < 0 or NaN; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_OCC_LOCAL 0
+#define PSN_OCC_WORLD 1
+#define PSN_OCC_MAX_DIRS 1024
+int psn_occlusion_rows(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
+                       const int* list, const int* over_list, int64_t n_over, const double* points, const double* normals, int64_t n_rows,
+                       const double* table, int n_dirs, int mode, double bias, double t_max, int* hits, int* visible, double* ao,
+                       double* bent, int* words, long long* n_tests, void* stream);
+
+/* ------------------------------------------------------------------------
  * Crossing counts of an axis-parallel line with the mesh, over the same index (csrc/meshinside.hip; the float64 numpy definition is
  * psnerf_amd/meshdist.py:host_crossings): the inside test behind volume IoU.  The reference has no such query.  grid, vertices,
  * faces, cell_start, list, over_list, n_over: as psn_closest_point takes them.

@@ -1646,6 +1646,40 @@ def ray_cast(grid, vertices, faces, cell_start, lst, over_list, n_over, origins,
     return t, tri, bary, hit
 
 
+# --------------------------------------------------------------------------- occlusion of rows (csrc/meshocclude.hip)
+def occlusion_rows(grid, vertices, faces, cell_start, lst, over_list, n_over, points, normals, table, local=True, bias=0.0, t_max=float('inf'),
+                   bits=False, n_tests=None, out=None):
+    """psn_occlusion_rows: points / normals float64 [R, 3], table float64 [K, 3] -> (hits int32 [R], visible int32 [R], ao float64 [R],
+    bent float64 [R, 3], words int32 [R, ceil(K / 32)] or None): per row the K rays of the table (about the normal with ``local``, as
+    given and only where they face the normal without) any-hit against the whole mesh.  out: the five outputs to write into (words
+    None without ``bits``); n_tests (int64 [1]) accumulates the number of ray-triangle tests."""
+    vp, fp = _mesh_ptrs(vertices, faces)
+    for name, x in (('points', points), ('normals', normals), ('table', table)):
+        _tptr(x, 'occlusion_rows: %s' % name, torch.float64)
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise RuntimeError('occlusion_rows: %s [R, 3] expected, got %s' % (name, tuple(x.shape)))
+    if points.shape != normals.shape:
+        raise RuntimeError('occlusion_rows: %d points and %d normals' % (points.shape[0], normals.shape[0]))
+    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
+    r, k = points.shape[0], table.shape[0]
+    n_words = (k + 31) // 32
+    given = (None,) * 5 if out is None else out
+    hits = _out(given[0], (r,), points, 'occlusion_rows: hits', torch.int32)
+    visible = _out(given[1], (r,), points, 'occlusion_rows: visible', torch.int32)
+    ao = _out(given[2], (r,), points, 'occlusion_rows: ao', torch.float64)
+    bent = _out(given[3], (r, 3), points, 'occlusion_rows: bent', torch.float64)
+    words = _out(given[4], (r, n_words), points, 'occlusion_rows: words', torch.int32) if bits else None
+    with _Prof('occlusion_rows', r * k):
+        _check(_lib.psn_occlusion_rows(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cell_start, 'cell_start', torch.int32),
+                                       _tptr(lst, 'list', torch.int32), _tptr(over_list, 'over_list', torch.int32), int(n_over),
+                                       _eptr(points, table), _eptr(normals, table), r, _eptr(table, vertices), k,
+                                       OCC_LOCAL if local else OCC_WORLD, float(bias), float(t_max),  # noqa: F821
+                                       _eptr(hits, table), _eptr(visible, table), _eptr(ao, table), _eptr(bent, table),
+                                       None if words is None else _eptr(words, table),
+                                       None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'occlusion_rows')
+    return hits, visible, ao, bent, words
+
+
 # --------------------------------------------------------------------------- crossing counts (csrc/meshinside.hip)
 def mesh_crossings(grid, vertices, faces, cell_start, lst, over_list, n_over, points, axis=2, order=None, want_below=True, want_on=True,
                    n_tests=None):

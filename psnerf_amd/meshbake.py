@@ -32,6 +32,9 @@ The lookup (``host_atlas_sample``): (x, y) = (b0 (x0, y0) + b1 (x1, y1)) + b2 (x
   value = (1 - fy)((1 - fx) t00 + fx t10) + fy ((1 - fx) t01 + fx t11) in float64.  A face outside 0 .. F - 1 (a miss is -1) or a
   position that is not finite gives a NaN row.
 Bytes (``to_img``, the rule of imgmetrics.to_img in float32): clip to [0, 1], x 255, round half to even; NaN -> 0.
+Baked visibility (``bake_occlusion``, or ``bake_materials(..., occlusion=K)``): the rows' points and normals go through
+  meshocclude.occlusion_rows (K cosine-weighted directions about the row's normal, any-hit against the mesh itself) and the ambient
+  occlusion and the bent normal of each row are scattered like any other map; a row that casts nothing (a zero normal) bakes ``fill``.
 """
 import math
 import os
@@ -321,13 +324,16 @@ PHASE_EVENTS = None
 
 
 @torch.no_grad()
-def bake_materials(model, mesh, size=2048, maps=MAPS, chunk_faces=None, fill=0.0, device=None):
+def bake_materials(model, mesh, size=2048, maps=MAPS, chunk_faces=None, fill=0.0, device=None, occlusion=None, occlusion_bias=None,
+                   occlusion_distance=float('inf')):
     """The material textures of a stage-2 ``PSNetwork`` on ``mesh`` -> {'atlas': Atlas, 'albedo': [T, T, 3], 'specular': [T, T, nbasis]
     (sgbasis) or [T, T, 1] (microfacet), 'normal': [T, T, 3]}, float32, T = ``size``; texels no face owns hold ``fill``.
     The model is put in eval mode for the call and nothing is jittered.  Chunk of faces by chunk of faces (``chunk_faces``; default:
     about a million rows): rows -> points -> networks -> texels, so that no more than one chunk of rows ever exists.
     One code path: a model on the device (or ``device='cuda'``: the mesh is moved there) runs the kernels and returns device tensors;
-    a CPU model with a numpy mesh runs the definition and returns numpy arrays."""
+    a CPU model with a numpy mesh runs the definition and returns numpy arrays.
+    ``occlusion`` = K: also 'occlusion' [T, T, 1] and 'bent' [T, T, 3] of ``bake_occlusion`` on the same atlas, from the same rows, with
+    K directions, ``occlusion_bias`` (None: 1e-4 x the bounding-box diagonal) and ``occlusion_distance`` (the rays' t_max)."""
     maps = tuple(maps)
     if not maps or any(m not in MAPS for m in maps):
         raise ValueError('bake_materials: maps %r (any of %s)' % (maps, ', '.join(MAPS)))
@@ -349,6 +355,7 @@ def bake_materials(model, mesh, size=2048, maps=MAPS, chunk_faces=None, fill=0.0
     step = max(1, CHUNK_ROWS // atlas.K) if chunk_faces is None else int(chunk_faces)
     if step < 1:
         raise ValueError('bake_materials: chunk_faces = %d' % step)
+    occluder = None if occlusion is None else _Occluder(v, f, int(occlusion), occlusion_bias, occlusion_distance)
     was_training = model.training
     model.eval()
     out = {'atlas': atlas}
@@ -356,7 +363,9 @@ def bake_materials(model, mesh, size=2048, maps=MAPS, chunk_faces=None, fill=0.0
         for f0 in range(0, atlas.F, step):
             f1 = min(f0 + step, atlas.F)
             with Phase(PHASE_EVENTS, 'points'):
-                _, x, nrm = atlas_points(atlas, v, f, vn, f0, f1)
+                p, x, nrm = atlas_points(atlas, v, f, vn, f0, f1)
+            if occluder is not None:
+                occluder.bake(atlas, p, nrm, f0, f1, out, fill)
             if not on_dev:
                 x, nrm = torch.from_numpy(x), torch.from_numpy(nrm)
             cache = {}                                                   # the encodings of this chunk's points
@@ -370,12 +379,73 @@ def bake_materials(model, mesh, size=2048, maps=MAPS, chunk_faces=None, fill=0.0
     return out
 
 
+# ------------------------------------------------------------------------------------------------ baked visibility
+class _Occluder(object):
+    """The mesh as its own occluder for a bake: the index (a MeshIndex for device tensors, the host twin for numpy arrays), the
+    direction table and the bias, made once; ``bake`` turns one chunk of rows into texels of 'occlusion' and 'bent'."""
+
+    def __init__(self, v, f, K, bias, t_max):
+        from . import meshdist as md, meshocclude as mo
+        self.index = md._prepare((v, f), None, 'mesh')
+        self.table = mo.hemisphere_table(K)
+        self.bias = mo.default_bias(self.index) if bias is None else float(bias)
+        self.t_max = float(t_max)
+
+    def bake(self, atlas, points, normals, f0, f1, out, fill):
+        from . import meshocclude as mo
+        with Phase(PHASE_EVENTS, 'occlusion'):
+            hits, _, ao, bent, _ = mo.occlusion_rows(self.index, points, normals, self.table, bias=self.bias, t_max=self.t_max)
+            if torch.is_tensor(ao):
+                dead = (hits < 0)[:, None]
+                rows = {'occlusion': torch.where(dead, float(fill), ao[:, None].float()), 'bent': torch.where(dead, float(fill), bent.float())}
+            else:
+                dead = (hits < 0)[:, None]
+                rows = {'occlusion': np.where(dead, np.float32(fill), ao[:, None].astype(np.float32)),
+                        'bent': np.where(dead, np.float32(fill), bent.astype(np.float32))}
+        with Phase(PHASE_EVENTS, 'scatter'):
+            for name, r in rows.items():
+                out[name] = atlas_scatter(atlas, r.contiguous() if torch.is_tensor(r) else np.ascontiguousarray(r), f0, f1, out.get(name),
+                                          fill if name not in out else None)
+
+
+def bake_occlusion(mesh, size=2048, atlas=None, K=64, bias=None, t_max=float('inf'), chunk_faces=None, fill=0.0, device=None):
+    """Ambient occlusion and bent normals of ``mesh`` under its own shadow, on its atlas -> {'atlas': Atlas, 'occlusion': float32
+    [T, T, 1] = 1 - the cosine-weighted share of the hemisphere about the row's normal that the mesh blocks within ``t_max``,
+    'bent': float32 [T, T, 3] = the normalised sum of the unblocked directions (object space)}; texels no face owns, and rows that cast
+    nothing (a zero normal), hold ``fill``.  ``atlas``: an Atlas laid out for the mesh (default: Atlas(size, F)); K directions of
+    meshocclude.hemisphere_table; ``bias`` = None: 1e-4 x the bounding-box diagonal.  Row normals are the ones atlas_points returns
+    (the mesh's vertex normals interpolated, else the face's own).  Chunk of faces by chunk of faces as bake_materials; a bake in
+    chunks equals a bake in one call bit for bit.  One code path: device tensors (or ``device='cuda'``: the mesh is moved there) run
+    the kernels and return device tensors; a numpy mesh runs the definition and returns numpy arrays."""
+    v, f, vn = mesh_parts(mesh)
+    _no_cpu_tensor(v, 'bake_occlusion')
+    if on_device(v, device):
+        v, f, vn = device_mesh(v, f, vn, device, prefix='atlas', widen_normals=True)
+    else:
+        v, f, vn = host_mesh(to_numpy(v), to_numpy(f), to_numpy(vn), prefix='atlas', widen_normals=True)
+    atlas = Atlas(size, f.shape[0]) if atlas is None else atlas
+    if atlas.F != f.shape[0]:
+        raise ValueError('bake_occlusion: %d faces, the atlas was laid out for %d' % (f.shape[0], atlas.F))
+    step = max(1, CHUNK_ROWS // atlas.K) if chunk_faces is None else int(chunk_faces)
+    if step < 1:
+        raise ValueError('bake_occlusion: chunk_faces = %d' % step)
+    occluder = _Occluder(v, f, int(K), bias, t_max)          # (building the index also checks the faces' vertex indices)
+    out = {'atlas': atlas}
+    for f0 in range(0, atlas.F, step):
+        f1 = min(f0 + step, atlas.F)
+        with Phase(PHASE_EVENTS, 'points'):
+            p, _, nrm = atlas_points(atlas, v, f, vn, f0, f1)
+        occluder.bake(atlas, p, nrm, f0, f1, out, fill)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ the writer
 def export_textured(path, mesh, baked, gamma=1.0):
     """Write the textured asset: ``name.obj`` (v, vt, f v/vt; vn and f v/vt/vn when the mesh has vertex normals), ``name.mtl``
     (map_Kd name_albedo.png; norm name_normal.png), the PNGs (bytes by ``to_img``; the albedo raised to 1 / gamma first, the normals
     stored as n / 2 + 0.5 -- OBJECT space, not tangent space) and ``name_specular.npy`` (float32 [T, T, C]: the SG weights have more
-    than three channels and are not an image).  ``path``: name.obj, or the name without an extension; ``baked``: bake_materials'
+    than three channels and are not an image); with 'occlusion' / 'bent' (bake_occlusion) also ``name_ao.png`` (one channel, map_Ka) and
+    ``name_bent.png`` (stored as n / 2 + 0.5 like the normals).  ``path``: name.obj, or the name without an extension; ``baked``: bake_materials'
     result (only the maps it holds are written) -> {what: file path}."""
     from PIL import Image
     base = path[:-4] if path.lower().endswith('.obj') else path
@@ -402,6 +472,14 @@ def export_textured(path, mesh, baked, gamma=1.0):
         files['specular'] = os.path.join(folder, name + '_specular.npy')
         np.save(files['specular'], to_numpy(baked['specular']).astype(np.float32))
         mtl.append('# specular: %s_specular.npy, float32 [T, T, C]' % name)
+    if 'occlusion' in baked:
+        files['ao'] = os.path.join(folder, name + '_ao.png')
+        Image.fromarray(to_img(to_numpy(baked['occlusion']).astype(np.float32))[:, :, 0]).save(files['ao'])
+        mtl += ['# ambient occlusion by the mesh itself, 1 = open', 'map_Ka %s_ao.png' % name]
+    if 'bent' in baked:
+        files['bent'] = os.path.join(folder, name + '_bent.png')
+        Image.fromarray(to_img(to_numpy(baked['bent']).astype(np.float32) / np.float32(2.0) + np.float32(0.5))).save(files['bent'])
+        mtl.append('# bent normals: %s_bent.png, object space, stored as n / 2 + 0.5' % name)
     with open(files['mtl'], 'w') as out:
         out.write('\n'.join(mtl) + '\n')
     uv = atlas_uv(atlas).reshape(-1, 2)

@@ -461,6 +461,23 @@ class MeshIndex(object):
         holes, where a line through a hole has the wrong parity."""
         return _contains(self, points, axis, vote)
 
+    def occlusion(self, points, normals, table, local=True, bias=0.0, t_max=float('inf'), bits=False, n_tests=None, out=None):
+        """points / normals float64 [R, 3] on the index's device, table float64 [K, 3] (a device tensor, or a numpy array that is
+        uploaded) -> (hits int32 [R], visible int32 [R], ao [R], bent [R, 3], words int32 [R, ceil(K / 32)] or None), device tensors:
+        meshocclude.host_occlusion_rows on the device (csrc/meshocclude.hip).  The rows are worked on in the order given: consecutive
+        rows should be neighbours on the surface, as the rows of an atlas are.  n_tests: an int64 [1] device tensor to which the
+        number of ray-triangle tests is added."""
+        from . import hip
+        if not (torch.is_tensor(points) and points.is_cuda and torch.is_tensor(normals) and normals.is_cuda):
+            raise RuntimeError('MeshIndex.occlusion: points and normals must be device tensors (host arrays: meshocclude.host_occlusion_rows)')
+        points = points.to(torch.float64).reshape(-1, 3).contiguous()
+        normals = normals.to(torch.float64).reshape(-1, 3).contiguous()
+        if not torch.is_tensor(table):
+            table = torch.from_numpy(np.ascontiguousarray(np.asarray(table, dtype=np.float64)))
+        table = table.to(device=points.device, dtype=torch.float64).contiguous()
+        return hip.occlusion_rows(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over, points, normals,
+                                  table, local=local, bias=bias, t_max=t_max, bits=bits, n_tests=n_tests, out=out)
+
     def face_areas_cumulative(self):
         return torch.cumsum(face_areas(self.vertices, self.faces), dim=0)
 
@@ -501,6 +518,10 @@ class _HostMesh(object):
     def crossings(self, points, axis=2, below=True, n_tests=None):
         above, under, on = host_crossings(self.vertices, self.faces, to_numpy(points), axis)
         return above, (under if below else None), on
+
+    def occlusion(self, points, normals, table, local=True, bias=0.0, t_max=np.inf, bits=False, n_tests=None):
+        from .meshocclude import host_occlusion_rows
+        return host_occlusion_rows(self.vertices, self.faces, to_numpy(points), to_numpy(normals), to_numpy(table), local, bias, t_max, bits)
 
     def contains(self, points, axis=2, vote=False):
         return _contains(self, points, axis, vote)

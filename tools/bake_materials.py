@@ -5,12 +5,15 @@ name_normal.png + name_specular.npy (psnerf_amd.meshbake: two faces per square c
     python tools/bake_materials.py --mesh test_out/bear/test_1/mesh.ply --conf exps/bear/runconf.conf
                                    --checkpoint exps/bear/checkpoints [--epoch latest] --out baked/bear.obj
                                    [--size 2048] [--maps albedo specular normal] [--simplify N] [--chunk-faces N] [--fill 0]
-                                   [--gamma 1.0] [--host]
+                                   [--gamma 1.0] [--host] [--occlusion K [--occlusion-distance D] [--occlusion-bias B]]
 
 --conf is the stage-2 run's conf file (stage2/confs/<obj>.conf or the runconf.conf a run leaves behind); --checkpoint is the run's
 checkpoint directory (ModelParameters/<epoch>.pth inside it, as stage2/trainer.py writes them) or a ModelParameters .pth file itself.
 --simplify N first reduces the mesh to about N faces (meshsimplify.simplify_mesh): a texture of T x T texels holds at most
 2 (T // 4)^2 faces, and a face wants more than the minimum of 4 x 4 texels -- the tool prints the cell size it arrived at.
+--occlusion K also bakes the mesh's own shadow on the same atlas (meshbake.bake_occlusion): name_ao.png, the ambient occlusion from K
+cosine-weighted directions per texel (map_Ka in the MTL), and name_bent.png, the bent normals; --occlusion-distance D ends the rays at D
+(default: no end), --occlusion-bias B lifts their origins by B along the normal (default: 1e-4 x the bounding-box diagonal).
 On a GPU everything runs on the device; --host evaluates the networks in torch on the CPU (small meshes and textures)."""
 import argparse
 import os
@@ -44,6 +47,9 @@ def main(argv=None):
     ap.add_argument('--chunk-faces', type=int, default=None)
     ap.add_argument('--fill', type=float, default=0.0, help='the value of the texels no face owns')
     ap.add_argument('--gamma', type=float, default=1.0, help='the albedo PNG stores albedo ^ (1 / gamma)')
+    ap.add_argument('--occlusion', type=int, default=None, metavar='K', help='also bake ambient occlusion and bent normals from K directions')
+    ap.add_argument('--occlusion-distance', type=float, default=float('inf'), metavar='D', help='the length of the occlusion rays')
+    ap.add_argument('--occlusion-bias', type=float, default=None, metavar='B', help='the offset of their origins along the normal')
     ap.add_argument('--host', action='store_true', help='run on the CPU (the numpy definition, the networks in torch)')
     args = ap.parse_args(argv)
 
@@ -67,7 +73,8 @@ def main(argv=None):
     print('%d faces in %d x %d texels: cells of %d x %d, %d rows per face, %.1f %% of the texels owned' % (
         atlas.F, atlas.T, atlas.T, atlas.c, atlas.c, atlas.K, 100.0 * atlas.F * atlas.K / atlas.T ** 2))
     net = load_model(args.conf, args.checkpoint, args.epoch, dev)
-    baked = mb.bake_materials(net, mesh, size=args.size, maps=tuple(args.maps), chunk_faces=args.chunk_faces, fill=args.fill)
+    baked = mb.bake_materials(net, mesh, size=args.size, maps=tuple(args.maps), chunk_faces=args.chunk_faces, fill=args.fill,
+                              occlusion=args.occlusion, occlusion_bias=args.occlusion_bias, occlusion_distance=args.occlusion_distance)
     files = mb.export_textured(args.out, mesh, baked, gamma=args.gamma)
     for what in sorted(files):
         print('%-8s %s' % (what, files[what]))

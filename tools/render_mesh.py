@@ -20,9 +20,10 @@ agree; ground-truth normals in camera space ('gt_normal_world' false) are rotate
 text table.  shadow/view_VV.npy is bool [L, H, W]: True where the light is visible from the surface point under the pixel going by
 the mesh (meshrender.mesh_light_visibility: binary occlusion, not the network's transmittance); off the mesh True.
 --textures: --mesh is a textured asset of tools/bake_materials.py (name.obj with name_albedo.png / name_normal.png /
-name_specular.npy beside it, whichever exist); each map is looked up at the first hits (meshbake.atlas_sample) and written as
-<map>/view_VV.npy (float32 [H, W, C], NaN off the mesh) and, for albedo and normal, .png.  The PNG maps are read back as the bytes they
-are (albedo u / 255, normal 2 u / 255 - 1): what another renderer would see.
+name_specular.npy / name_ao.png / name_bent.png beside it, whichever exist); each map is looked up at the first hits
+(meshbake.atlas_sample) and written as <map>/view_VV.npy (float32 [H, W, C], NaN off the mesh) and, for all but specular, .png.  The
+PNG maps are read back as the bytes they are (albedo and occlusion u / 255, normal and bent 2 u / 255 - 1): what another renderer
+would see.
 On a GPU everything runs on the device; --host takes the numpy definition (small meshes only: it is a brute force)."""
 import argparse
 import json
@@ -74,6 +75,10 @@ def read_textures(mesh_path, n_faces):
             maps[name] = decode(np.asarray(Image.open(base + '_%s.png' % name).convert('RGB')).astype(np.float32))
     if os.path.exists(base + '_specular.npy'):
         maps['specular'] = np.load(base + '_specular.npy').astype(np.float32)
+    if os.path.exists(base + '_ao.png'):                         # (bake_materials.py --occlusion)
+        maps['occlusion'] = (np.asarray(Image.open(base + '_ao.png').convert('L')).astype(np.float32) / np.float32(255.0))[..., None]
+    if os.path.exists(base + '_bent.png'):
+        maps['bent'] = np.asarray(Image.open(base + '_bent.png').convert('RGB')).astype(np.float32) * np.float32(2.0 / 255.0) - np.float32(1.0)
     if not maps:
         raise SystemExit('render_mesh: --textures, but no %s_albedo.png / _normal.png / _specular.npy' % base)
     sizes = set(m.shape[:2] for m in maps.values())
@@ -150,9 +155,10 @@ def main(argv=None):
         for key in (textures or ()):
             tex = out[key].to(torch.float32)
             np.save(os.path.join(args.out, 'tex_' + key, name + '.npy'), tex.cpu().numpy())
-            if key in ('albedo', 'normal'):
-                shown = torch.nan_to_num((tex + 1.0) / 2.0 if key == 'normal' else tex, nan=0.0) * mask[..., None]
-                save_png(os.path.join(args.out, 'tex_' + key, name + '.png'), im.to_img(shown).cpu().numpy())
+            if key in ('albedo', 'normal', 'occlusion', 'bent'):
+                shown = torch.nan_to_num((tex + 1.0) / 2.0 if key in ('normal', 'bent') else tex, nan=0.0) * mask[..., None]
+                shown = im.to_img(shown).cpu().numpy()
+                save_png(os.path.join(args.out, 'tex_' + key, name + '.png'), shown[..., 0] if shown.shape[-1] == 1 else shown)
         if args.gt_normal:
             gt = np.load(os.path.join(args.gt_normal, name + '.npy')).astype(np.float32)
             if not para.get('gt_normal_world', True):
