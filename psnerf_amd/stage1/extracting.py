@@ -203,7 +203,8 @@ def host_marching_cubes(grid, threshold):
         f0, fq = P[p[:, 0], p[:, 1], p[:, 2]], P[q[:, 0], q[:, 1], q[:, 2]]
         lo, hi = p[:, a].astype(np.float64), q[:, a].astype(np.float64)
         (x1, x2, f1, f2) = (hi, lo, fq, f0) if a == 0 else (lo, hi, f0, fq)
-        pos = (x2 - x1) * (thr - f1) / (f2 - f1) + x1
+        with np.errstate(invalid='ignore'):                                        # (infinite ends: inf / inf = NaN, as on the device)
+            pos = (x2 - x1) * (thr - f1) / (f2 - f1) + x1
         at = voff[sel] + (((vm[sel] & ((1 << a) - 1)) & 1) + ((vm[sel] & ((1 << a) - 1)) >> 1))
         out = p.astype(np.float64)
         out[:, a] = pos

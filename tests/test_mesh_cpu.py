@@ -188,6 +188,151 @@ def test_host_path_r64_against_the_reference_digests():
     assert vol * d['signed_volume'] > 0 and abs(vol - d['signed_volume']) < n_cells and abs(area - d['area']) < n_cells
 
 
+# ------------------------------------------------------------------------------------------------ the edge cases (tests/mesh_cases.py)
+def test_edge_cases_do_what_they_are_for():
+    """Every case of tests/mesh_cases.py has the property it exists for (so that the device tests cannot pass on cases that
+    degenerated): ties put vertices exactly on lattice points, ties alone drive a refinement, the non-finite field gives NaN vertex
+    rows on a closed surface, and the marching-cubes sizes give the intended numbers of 256-cell runs."""
+    from tests import mesh_cases as mc
+    from psnerf_amd.stage1.extracting import host_marching_cubes, iso_value
+    assert mc.THR_LOGIT_03 == iso_value(0.3) and mc.THR_LOGIT_03 != float(np.float32(mc.THR_LOGIT_03))
+    assert [((n + 1) ** 3 + 255) // 256 for n in mc.MC_SIZES] == [1, 2, 9, 16] and (mc.MC_SIZES[-1] + 1) ** 3 % 256 == 0
+    assert max(r << d for r, d in mc.MISE_PAIRS) == 48 and {r << d for r, d in mc.MISE_PAIRS} >= {12, 20, 48}
+    for n in mc.MC_SIZES[1:]:
+        v, f = host_marching_cubes(mc.field('ternary', n - 1), 0.0)
+        on = int(mc.on_lattice_point(v).sum())
+        print('ternary n=%d: %d of %d vertices exactly on lattice points' % (n, on, len(v)))
+        assert on > len(v) // 4 and mf.is_closed_oriented(f)
+        v, f = host_marching_cubes(mc.field('tie_checker', n - 1), mc.THR_TIE)
+        assert int(mc.on_lattice_point(v).sum()) > 0 and mf.is_closed_oriented(f)
+        v, f = host_marching_cubes(mc.field('tie_checker', n - 1), mc.THR_LOGIT_03)
+        assert int(mc.on_lattice_point(v).sum()) == 0 and len(f) > 0
+        v, f = host_marching_cubes(mc.field('nonfinite', n - 1), 0.0)
+        nan_rows = int(np.isnan(v).any(axis=1).sum())
+        print('nonfinite n=%d: %d NaN rows of %d vertices' % (n, nan_rows, len(v)))
+        assert 0 < nan_rows < len(v) and mf.is_closed_oriented(f) and len(f) > 0
+        fld = mc.field('nonfinite', n - 1)
+        assert np.isnan(fld).any() and np.isposinf(fld).any() and np.isneginf(fld).any() and (np.signbit(fld) & (fld == 0)).any()
+        assert (fld == np.float32(1e-40)).any() and (fld == np.float32(-1e-40)).any() and np.float32(1e-40) != 0
+    for n in mc.MC_SIZES:
+        assert len(host_marching_cubes(mc.field('all_tie375', n - 1), mc.THR_TIE)[1]) == 0
+        v, f = host_marching_cubes(mc.field('all_above', n - 1), 0.0)
+        assert len(f) == 2 * len(v) - 4 and mf.is_closed_oriented(f)
+    # ties alone drive a refinement: sparse_tie(t) at thr = t evaluates more points than the same field with the ties set to +1
+    for res0, depth in mc.MISE_PAIRS:
+        if res0 < 2:
+            continue
+        R = res0 << depth
+        for name, thr in (('sparse_tie0', mc.THR_ZERO), ('sparse_tie375', mc.THR_TIE)):
+            fld = mc.field(name, R)
+            assert (fld == np.float32(thr)).any() and set(np.unique(fld).tolist()) == {float(np.float32(thr)), 1.0}
+            rounds, _ = mc.lock_step(fld, res0, depth, thr)
+            plain, _ = mc.lock_step(np.ones_like(fld), res0, depth, thr)
+            n_tie, n_plain = sum(len(r['rows']) for r in rounds), sum(len(r['rows']) for r in plain)
+            assert n_plain == (res0 + 1) ** 3 and len(plain) == 1 and n_tie > n_plain and len(rounds) > 1, (res0, depth, name)
+    # resolution0 = 1 is paired with fields that do refine there
+    for cid, res0, depth, fname, tname in mc.mise_cases():
+        if res0 == 1:
+            rounds, _ = mc.lock_step(mc.field(fname, res0 << depth), res0, depth, mc.THRESHOLDS[tname])
+            assert len(rounds) > depth and rounds[0]['new'] == 19, cid
+
+
+def test_fill_cases_reach_the_paths_they_are_built_for():
+    """tests/mesh_cases.ffill_grid: what the z kernel starts from (after the x and y passes) has the constructed lines, and the
+    x / y runs are the holes the strided kernel meets."""
+    from tests import mesh_cases as mc
+    from psnerf_amd.stage1.extracting import host_ffill
+    assert mc.FFILL_SIZES == [1, 2, 63, 64, 129, 130]
+    for n in mc.FFILL_SIZES:
+        grid = mc.ffill_grid(n)
+        before_z = mc.ffill_before_z(grid)
+        known = ~np.isnan(before_z)
+        out = host_ffill(grid.copy())
+        if n >= 2:
+            assert not known[0, 0].any() and np.isnan(out[0, 0]).all()              # a first point that is a hole, never filled
+            assert known[0, 1].tolist() == [True] + [False] * (n - 1)               # known only at z = 0 ...
+            assert np.signbit(out[0, 1]).all() and (out[0, 1] == 0).all()           # ... and -0.0 travels down the whole line
+        if n >= 7:
+            assert np.nonzero(known[1, 0])[0].tolist() == [5] and np.isnan(out[1, 0, :5]).all() and np.isneginf(out[1, 0, 5:]).all()
+        if n >= 129:
+            for j, val in ((2, 1e-40), (3, -1e-40)):
+                assert known[0, j, :64].all() and not known[0, j, 64:128].any() and known[0, j, 128:].all()
+                assert (out[0, j, 63:128] == np.float32(val)).all() and np.float32(val) != 0
+        if n >= 38:
+            seen = set()
+            for c, (q, length) in enumerate((q, length) for q in range(7, 11) for length in range(9, 18)):
+                k = 1 + c
+                for line in (grid[0, :, k], grid[:, n - 1, k]):                      # a y run and an x run
+                    assert not np.isnan(line[q - 1]) and np.isnan(line[q:q + length]).all() and not np.isnan(line[q + length])
+                assert out[0, q:q + length, k].view(np.int32).tolist() == [int(grid[0, q - 1, k].view(np.int32))] * length
+                assert out[q:q + length, n - 1, k].view(np.int32).tolist() == [int(grid[q - 1, n - 1, k].view(np.int32))] * length
+                seen.add((q, length))
+            assert len(seen) == 36
+            vals = grid[~np.isnan(grid)]
+            assert (np.signbit(vals) & (vals == 0)).any() and np.isinf(vals).any() and ((vals != 0) & (np.abs(vals) < 1e-38)).any()
+
+
+def test_lock_step_driver_is_the_extractor_on_the_host():
+    """The round-by-round driver and Extractor3D's own host loop (query / update) evaluate the same points in the same rounds."""
+    from tests import mesh_cases as mc
+    from psnerf_amd.stage1.extracting import Extractor3D
+    for res0, depth, fname, threshold in ((3, 2, 'tie_checker', 0.3), (2, 3, 'ternary', 0.5), (6, 1, 'nonfinite', 0.5)):
+        fld = mc.field(fname, res0 << depth)
+        model = mf.LookupModel(fld.copy())
+        ex = Extractor3D(model, resolution0=res0, upsampling_steps=depth, threshold=threshold, points_batch_size=1000)
+        _, stats = ex.generate_mesh()
+        rounds, mise = mc.lock_step(fld, res0, depth, mc.THR_ZERO if threshold == 0.5 else mc.THR_LOGIT_03)
+        assert stats['n_rounds'] == len(rounds) and stats['n_points_evaluated'] == sum(len(r['rows']) for r in rounds)
+        assert np.array_equal(ex.last_known, mise.flags == 2) and int(model.seen.max()) == 1
+        assert ex.last_grid.tobytes() == mise.to_dense().tobytes()
+
+
+def _edge_golden():
+    return json.load(open(os.path.join(GOLDEN, 'mesh_edge_cases.json')))
+
+
+def _assert_mc_record(v, f, rec, what):
+    """A host mesh (lattice units) against a record of the reference's: counts exactly, the lattice edges where they are
+    defined, closed and oriented, area / signed volume within the gate of the R = 64 digests (triangles x unit cell: inside a
+    cell the derived table may choose other diagonals than the reference's)."""
+    from tests import mesh_cases as mc
+    assert (len(v), len(f)) == (rec['n_vertices'], rec['n_faces']), what
+    assert int(mc.on_lattice_point(v).sum()) == rec['n_on_lattice_points'], what
+    assert mf.is_closed_oriented(f), what
+    assert ('edges_sha256' in rec) == mc.edges_defined(v), what
+    if 'edges_sha256' in rec:
+        assert mf.edges_digest(v) == rec['edges_sha256'], what
+    area, vol = mf.area_volume(v, f)
+    gate = max(rec['n_faces'], 1)
+    assert vol * rec['signed_volume'] > 0 or (vol == 0 and rec['signed_volume'] == 0), what
+    assert abs(vol - rec['signed_volume']) < gate and abs(area - rec['area']) < gate, what
+
+
+def test_host_path_reproduces_the_reference_on_the_edge_cases():
+    """HostMISE round by round, to_dense and host_marching_cubes against what the reference's libmise / libmcubes recorded for
+    every finite case (tests/golden/mesh_edge_cases.json, tools/gen_golden_mesh.py): ties, thresholds that are no float32 value,
+    resolutions 2 .. 48 that are no powers of two, depth 1 and resolution0 1."""
+    from tests import mesh_cases as mc
+    from psnerf_amd.stage1.extracting import host_marching_cubes
+    gold = _edge_golden()
+    finite = [c for c in mc.mise_cases() if mc.is_finite_case(c[3])]
+    assert sorted(gold['mise']) == sorted(c[0] for c in finite)
+    for cid, res0, depth, fname, tname in finite:
+        rec, thr = gold['mise'][cid], mc.THRESHOLDS[tname]
+        rounds, mise = mc.lock_step(mc.field(fname, res0 << depth), res0, depth, thr)
+        assert [len(r['rows']) for r in rounds] == rec['rounds'], cid
+        assert mc.sha256(np.nonzero((mise.flags == 2).ravel())[0], '<i8') == rec['known_sha256'], cid
+        dense = mise.to_dense()
+        assert dense.dtype == np.float32 and mc.sha256(dense, '<f4') == rec['dense_sha256'], cid
+        v, f = host_marching_cubes(dense, thr)
+        _assert_mc_record(v, f, rec, cid)
+    finite = [c for c in mc.mc_cases() if mc.is_finite_case(c[2])]
+    assert sorted(gold['mc']) == sorted(c[0] for c in finite)
+    for cid, n, fname, tname in finite:
+        v, f = host_marching_cubes(mc.field(fname, n - 1), mc.THRESHOLDS[tname])
+        _assert_mc_record(v, f, gold['mc'][cid], cid)
+
+
 # ------------------------------------------------------------------------------------------------ Extractor3D on the CPU
 def test_extractor_without_upsampling():
     from psnerf_amd.stage1.extracting import Extractor3D, host_marching_cubes, to_world

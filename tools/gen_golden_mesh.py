@@ -10,8 +10,13 @@ are stored:
                       marching cubes; plus the marching cubes of a random +- grid (mesh_fields.checker) that visits every
                       ambiguous-face configuration
   mesh_mise_r64.json  resolution0 16, depth 2: digests only
+  mesh_edge_cases.json  the finite cases of tests/mesh_cases.py (ties, thresholds that are no float32 value, odd resolutions,
+                      depth 1, resolution0 1): per refinement case the points per round, digests of the known set and of the dense
+                      grid and the counts / area / signed volume of its marching cubes; per marching-cubes case the same counts;
+                      the lattice-edge digest only where no vertex sits on a lattice point.  The non-finite field is left out: the
+                      reference's behaviour there is not a contract
 
-    python tools/gen_golden_mesh.py /path/to/reference
+    python tools/gen_golden_mesh.py /path/to/reference [base] [edge]      (which files to write; default: all of them)
 """
 import hashlib
 import json
@@ -100,11 +105,65 @@ def cube_histogram(grid, thr=0.0):
     return np.bincount(cube.ravel(), minlength=256)
 
 
+def mc_record(vertices, faces):
+    """Counts, area and signed volume of a reference mesh (lattice units); the lattice-edge digest where it is defined."""
+    from tests import mesh_cases as mc, mesh_fields as mf
+    area, volume = mf.area_volume(vertices, faces)
+    rec = dict(n_vertices=int(len(vertices)), n_faces=int(len(faces)), area=area, signed_volume=volume,
+               n_on_lattice_points=int(mc.on_lattice_point(vertices).sum()))
+    if mc.edges_defined(vertices):   # (lattice_edges refuses a vertex on, or within 1e-9 of, a lattice point)
+        rec['edges_sha256'] = mf.edges_digest(vertices)
+    return rec
+
+
+def edge_cases():
+    """tests/golden/mesh_edge_cases.json from the reference's libraries on the finite cases of tests/mesh_cases.py."""
+    from tests import mesh_cases as mc
+    out = dict(mise={}, mc={})
+    for cid, res0, depth, fname, tname in mc.mise_cases():
+        if not mc.is_finite_case(fname):
+            continue
+        R = res0 << depth
+        r = reference_extract(mc.field(fname, R), res0, depth, mc.THRESHOLDS[tname])
+        rec = dict(rounds=r['rounds'], known_sha256=mc.sha256(np.sort(mc.linear(r['known'], R + 1)), '<i8'),
+                   dense_sha256=mc.sha256(r['dense'], '<f4'))
+        rec.update(mc_record(r['vertices'], r['faces']))
+        out['mise'][cid] = rec
+        print(cid, rec['rounds'], rec['n_vertices'], rec['n_faces'])
+    for cid, n, fname, tname in mc.mc_cases():
+        if not mc.is_finite_case(fname):
+            continue
+        v, f = reference_mc(mc.field(fname, n - 1), mc.THRESHOLDS[tname])
+        out['mc'][cid] = mc_record(v, f)
+        print(cid, out['mc'][cid]['n_vertices'], out['mc'][cid]['n_faces'], out['mc'][cid]['n_on_lattice_points'])
+    with open(os.path.join(GOLDEN, 'mesh_edge_cases.json'), 'w') as f:   # one case per line: a few kB
+        f.write('{\n')
+        for gi, group in enumerate(('mise', 'mc')):
+            f.write(' "%s": {\n' % group)
+            keys = list(out[group])
+            for i, k in enumerate(keys):
+                f.write('  "%s": %s%s\n' % (k, json.dumps(out[group][k], sort_keys=True, separators=(',', ':')), ',' if i + 1 < len(keys) else ''))
+            f.write(' }%s\n' % (',' if gi == 0 else ''))
+        f.write('}\n')
+
+
 def main():
-    ref = sys.argv[1] if len(sys.argv) > 1 else os.environ.get('PSNERF_REFERENCE')
-    assert ref and os.path.isdir(ref), 'usage: gen_golden_mesh.py /path/to/reference'
+    args = [a for a in sys.argv[1:] if a not in ('base', 'edge')]
+    which = [a for a in sys.argv[1:] if a in ('base', 'edge')] or ['base', 'edge']
+    ref = args[0] if args else os.environ.get('PSNERF_REFERENCE')
+    assert ref and os.path.isdir(ref), 'usage: gen_golden_mesh.py /path/to/reference [base] [edge]'
     tmp = build_reference(ref)
     try:
+        if 'edge' in which:
+            edge_cases()
+        if 'base' in which:
+            base_fixtures()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def base_fixtures():
+    if True:
         from tests import mesh_fields as mf
         from psnerf_amd.stage1.extracting import CORNERS
         # -- the 256 single-cell cases
@@ -141,8 +200,6 @@ def main():
         with open(os.path.join(GOLDEN, 'mesh_mise_r64.json'), 'w') as f:
             json.dump(dig, f, indent=1, sort_keys=True)
             f.write('\n')
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 if __name__ == '__main__':
