@@ -884,20 +884,24 @@ int psn_mc_emit(const float* grid, int n, double threshold, const unsigned char*
  *             whose bounding box overlaps more cells than this is kept in the oversize list instead of the cell lists.
  *   lists     int32 triangle ids.  The order within a cell's list and within the oversize list is not defined (atomics); the
  *             query's result does not depend on it.
+ *   PsnMeshIndex (host memory, device pointers): the mesh and its built grid in one value, what every query takes.  cell_start
+ *             [cells + 1] int32 = the exclusive scan of psn_tri_grid_count's counts with the total appended; list [n_entries] as
+ *             psn_tri_grid_fill wrote it (may be null when n_over = F: no cell has an entry); over_list: its first n_over entries
+ *             are the oversize triangles, 0 <= n_over <= F (may be null when n_over = 0).  A query refuses with PSN_E_ARG a null
+ *             index, null vertices, faces or cell_start, F out of range, n_over or a null list against these rules, a bad grid.
  *
  * psn_tri_grid_count: cell_count [cells] int32 (zeroed here) = per cell, the triangles whose bounding box overlaps it;
  *   over_list [F] receives the oversize triangles, n_over[0] (set here) their number.
  * psn_tri_grid_fill: cursor [cells] int32 = the exclusive scan of those counts (advanced here to the inclusive scan);
  *   list [n_entries], n_entries = their total (< 2^31).
- * psn_closest_point: cell_start [cells + 1] int32 = the exclusive scan with the total appended.  points float64 [Q, 3]; order =
- *   null or a permutation of 0 .. Q - 1 in which the points are worked on (sorted by home cell keeps a wave's lanes in
- *   neighbouring cells; outputs are written at the point's own row either way).  closest float64 [Q, 3], dist float64 [Q]
- *   (Euclidean, mesh units), tri int64 [Q]: the minimum over ALL triangles of the distance to the triangle as the closed
- *   convex hull of its corners, ties to the lowest triangle index -- bitwise reproducible.  The search walks shells of cells
- *   around the point's (clamped) home cell and stops by an exact bound (csrc/meshdist.hip), also for points outside the
- *   bounding box.  A point with a NaN coordinate gets NaN, NaN, -1.  n_tests: null, or an int64 counter to which the number
- *   of point-triangle tests is added.  Q = 0 is a no-op.
- * Errors: PSN_E_ARG for null pointers, F or Q out of range, a bad PsnTriGrid, n_entries >= 2^31; PSN_E_LAUNCH.
+ * psn_closest_point: points float64 [Q, 3]; order = null or a permutation of 0 .. Q - 1 in which the points are worked on (sorted
+ *   by home cell keeps a wave's lanes in neighbouring cells; outputs are written at the point's own row either way).  closest
+ *   float64 [Q, 3], dist float64 [Q] (Euclidean, mesh units), tri int64 [Q]: the minimum over ALL triangles of the distance to
+ *   the triangle as the closed convex hull of its corners, ties to the lowest triangle index -- bitwise reproducible.  The search
+ *   walks shells of cells around the point's (clamped) home cell and stops by an exact bound (csrc/meshdist.hip), also for points
+ *   outside the bounding box.  A point with a NaN coordinate gets NaN, NaN, -1.  n_tests: null, or an int64 counter to which the
+ *   number of point-triangle tests is added.  Q = 0 is a no-op.
+ * Errors: PSN_E_ARG for null pointers, Q out of range, a bad PsnTriGrid or PsnMeshIndex, n_entries >= 2^31; PSN_E_LAUNCH.
  * ---------------------------------------------------------------------- */
 #define PSN_TRI_GRID_MAX_CELLS_PER_AXIS 256
 #define PSN_TRI_GRID_MAX_FACES 2147483646LL
@@ -908,18 +912,22 @@ typedef struct {
     int n[3];
     int max_span;
 } PsnTriGrid;
+typedef struct {
+    PsnTriGrid grid;
+    const double* vertices; const int64_t* faces; int64_t n_faces;
+    const int* cell_start; const int* list; const int* over_list; int64_t n_over;
+} PsnMeshIndex;
 int psn_tri_grid_count(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, int* cell_count,
                        int* over_list, long long* n_over, void* stream);
 int psn_tri_grid_fill(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, int* cursor,
                       int64_t n_entries, int* list, void* stream);
-int psn_closest_point(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
-                      const int* list, const int* over_list, int64_t n_over, const double* points, const int64_t* order,
-                      int64_t n_points, double* closest, double* dist, int64_t* tri, long long* n_tests, void* stream);
+int psn_closest_point(const PsnMeshIndex* index, const double* points, const int64_t* order, int64_t n_points, double* closest,
+                      double* dist, int64_t* tri, long long* n_tests, void* stream);
 
 /* ------------------------------------------------------------------------
  * Ray casting against the mesh, over the same index (csrc/meshray.hip; the float64 numpy definition is
  * psnerf_amd/meshdist.py:host_ray_cast).  The reference has no such query: its depth, normal and shadow maps all come from marching
- * the occupancy network.  grid, vertices, faces, cell_start, list, over_list, n_over: as psn_closest_point takes them.
+ * the occupancy network.  index: the PsnMeshIndex (above).
  *
  * psn_ray_cast: origins / directions float64 [Q, 3] (directions need not be unit vectors: t is the parameter of o + t d); order =
  *   null or a permutation of 0 .. Q - 1 in which the rays are worked on (outputs are written at the ray's own row either way).
@@ -930,20 +938,19 @@ int psn_closest_point(const PsnTriGrid* grid, const double* vertices, const int6
  *   first accepted triangle; t, tri and bary receive the values of a miss.  A triangle of zero area or seen edge-on is never hit; a
  *   ray with a non-finite component or a zero direction misses.  n_tests: null, or an int64 counter to which the number of
  *   ray-triangle tests is added.  Q = 0 is a no-op.
- * Errors: PSN_E_ARG for null pointers, F or Q out of range, a bad PsnTriGrid, an unknown mode, t_min > t_max; PSN_E_LAUNCH.
+ * Errors: PSN_E_ARG for null pointers, a bad PsnMeshIndex, Q out of range, an unknown mode, t_min > t_max; PSN_E_LAUNCH.
  * ---------------------------------------------------------------------- */
 #define PSN_RAY_FIRST_HIT 0
 #define PSN_RAY_ANY_HIT 1
-int psn_ray_cast(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
-                 const int* list, const int* over_list, int64_t n_over, const double* origins, const double* directions,
-                 const int64_t* order, int64_t n_rays, double t_min, double t_max, int mode, double* t, int64_t* tri, double* bary,
-                 unsigned char* hit, long long* n_tests, void* stream);
+int psn_ray_cast(const PsnMeshIndex* index, const double* origins, const double* directions, const int64_t* order, int64_t n_rays,
+                 double t_min, double t_max, int mode, double* t, int64_t* tri, double* bary, unsigned char* hit, long long* n_tests,
+                 void* stream);
 
 /* ------------------------------------------------------------------------
  * Occlusion of surface rows by the mesh, over the same index (csrc/meshocclude.hip; the float64 numpy definition is
  * psnerf_amd/meshocclude.py:host_occlusion_rows): per row (a point and a normal) the K rays of a direction table are formed in
  * registers and walked through the grid by psn_ray_cast's own any-hit walk (csrc/meshray.h), so no ray is ever written to memory.
- * The reference has no such query.  grid, vertices, faces, cell_start, list, over_list, n_over: as psn_closest_point takes them.
+ * The reference has no such query.  index: the PsnMeshIndex (above).
  *
  * psn_occlusion_rows: points / normals float64 [R, 3], table float64 [K, 3], 1 <= K <= PSN_OCC_MAX_DIRS.  A row whose point or normal
  *   has a non-finite component, or whose normal is zero, casts nothing: hits = -1, visible = 0, ao = NaN, bent = 0, words = 0.
@@ -959,21 +966,20 @@ int psn_ray_cast(const PsnTriGrid* grid, const double* vertices, const int64_t* 
  *   k / 32 is set iff direction k was cast and not blocked.  All arithmetic is float64 without contraction in the order written,
  *   so every output is bitwise reproducible and equal to the definition's.  n_tests: null, or an int64 counter to which the
  *   number of ray-triangle tests is added.  R = 0 is a no-op.
- * Errors: PSN_E_ARG for null pointers, F, R or K out of range, a bad PsnTriGrid, an unknown mode, a bias that is not finite,
+ * Errors: PSN_E_ARG for null pointers, a bad PsnMeshIndex, R or K out of range, an unknown mode, a bias that is not finite,
  *   t_max < 0 or NaN; PSN_E_LAUNCH.
  * ---------------------------------------------------------------------- */
 #define PSN_OCC_LOCAL 0
 #define PSN_OCC_WORLD 1
 #define PSN_OCC_MAX_DIRS 1024
-int psn_occlusion_rows(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
-                       const int* list, const int* over_list, int64_t n_over, const double* points, const double* normals, int64_t n_rows,
-                       const double* table, int n_dirs, int mode, double bias, double t_max, int* hits, int* visible, double* ao,
-                       double* bent, int* words, long long* n_tests, void* stream);
+int psn_occlusion_rows(const PsnMeshIndex* index, const double* points, const double* normals, int64_t n_rows, const double* table,
+                       int n_dirs, int mode, double bias, double t_max, int* hits, int* visible, double* ao, double* bent, int* words,
+                       long long* n_tests, void* stream);
 
 /* ------------------------------------------------------------------------
  * Crossing counts of an axis-parallel line with the mesh, over the same index (csrc/meshinside.hip; the float64 numpy definition is
- * psnerf_amd/meshdist.py:host_crossings): the inside test behind volume IoU.  The reference has no such query.  grid, vertices,
- * faces, cell_start, list, over_list, n_over: as psn_closest_point takes them.
+ * psnerf_amd/meshdist.py:host_crossings): the inside test behind volume IoU.  The reference has no such query.  index: the
+ * PsnMeshIndex (above).
  *
  * psn_mesh_crossings: points float64 [Q, 3]; order = null or a permutation of 0 .. Q - 1 in which the points are worked on (sorted
  *   by column, then by cell along the axis; outputs are written at the point's own row either way).  axis = 0, 1 or 2: the line
@@ -990,12 +996,11 @@ int psn_occlusion_rows(const PsnTriGrid* grid, const double* vertices, const int
  *   above and on do not change.  Zero-area and edge-on triangles are never counted; a point with a non-finite coordinate, or
  *   outside the bounding box in kx or ky, gets zeros.  n_tests: null, or an int64 counter to which the number of line-triangle
  *   tests is added (at most Q F).  Q = 0 is a no-op.
- * Errors: PSN_E_ARG for null pointers, an axis outside 0 .. 2, F or Q out of range, a bad PsnTriGrid; PSN_E_LAUNCH.
+ * Errors: PSN_E_ARG for null pointers, an axis outside 0 .. 2, a bad PsnMeshIndex, Q out of range; PSN_E_LAUNCH.
  * ---------------------------------------------------------------------- */
 #define PSN_CROSSINGS_MAX_POINTS 137438953408LL
-int psn_mesh_crossings(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
-                       const int* list, const int* over_list, int64_t n_over, const double* points, const int64_t* order,
-                       int64_t n_points, int axis, int* above, int* below, int* on, long long* n_tests, void* stream);
+int psn_mesh_crossings(const PsnMeshIndex* index, const double* points, const int64_t* order, int64_t n_points, int axis,
+                       int* above, int* below, int* on, long long* n_tests, void* stream);
 
 /* ------------------------------------------------------------------------
  * Mesh clean-up: connected components of a triangle mesh, per-component statistics and compaction (csrc/meshclean.hip; the numpy

@@ -225,12 +225,7 @@ __global__ __launch_bounds__(256) void closest_point_kernel(PsnTriGrid g, const 
             tri[q] = -1;
         }
     }
-    if (n_tests != nullptr) {   // one atomic per wave (every lane reaches this point)
-        unsigned long long s = tests;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-        if (md_lane() == 0 && s > 0) atomicAdd(n_tests, s);
-    }
+    md_add_tests(n_tests, tests);   // one atomic per wave (every lane reaches this point)
 }
 
 }  // namespace psn
@@ -276,26 +271,21 @@ extern "C" int psn_tri_grid_fill(const PsnTriGrid* grid, const double* vertices,
     return PSN_OK;
 }
 
-// The query.  cell_start [cells + 1]: exclusive scan of the counts with the total appended; list / over_list / n_over as built
-// above.  points [n_points, 3]; order: null, or a permutation of 0 .. n_points - 1 in which the points are taken (sorted by home
-// cell: neighbouring lanes then walk neighbouring cells); outputs are written at the point's own row whatever the order.
-// closest [n_points, 3], dist [n_points], tri [n_points] (a point with a NaN coordinate: NaN, NaN, -1).  n_tests: null, or one
-// counter to which the number of point-triangle tests is ADDED.
-extern "C" int psn_closest_point(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
-                                 const int* list, const int* over_list, int64_t n_over, const double* points, const int64_t* order,
-                                 int64_t n_points, double* closest, double* dist, int64_t* tri, long long* n_tests, void* stream) {
+// The query.  index: the grid and lists built above (PsnMeshIndex, include/psnerf_hip.h).  points [n_points, 3]; order: null, or a
+// permutation of 0 .. n_points - 1 in which the points are taken (sorted by home cell: neighbouring lanes then walk neighbouring
+// cells); outputs are written at the point's own row whatever the order.  closest [n_points, 3], dist [n_points], tri [n_points] (a
+// point with a NaN coordinate: NaN, NaN, -1).  n_tests: null, or one counter to which the number of point-triangle tests is ADDED.
+extern "C" int psn_closest_point(const PsnMeshIndex* index, const double* points, const int64_t* order, int64_t n_points, double* closest,
+                                 double* dist, int64_t* tri, long long* n_tests, void* stream) {
     using namespace psn;
-    if (int rc = md_check_grid(grid, "closest_point")) return rc;
-    PSN_CHECK_ARG(vertices && faces && cell_start, "closest_point: null pointer");
-    PSN_CHECK_ARG(n_faces >= 1 && n_faces <= PSN_TRI_GRID_MAX_FACES, "closest_point: n_faces=%lld (1 .. %lld)", (long long)n_faces,
-                  (long long)PSN_TRI_GRID_MAX_FACES);
-    PSN_CHECK_ARG(n_over >= 0 && n_over <= n_faces && (n_over == 0 || over_list), "closest_point: n_over=%lld / null oversize list", (long long)n_over);
-    PSN_CHECK_ARG(n_over == n_faces || list, "closest_point: null cell list");
+    if (int rc = md_check_index(index, "closest_point")) return rc;
     PSN_CHECK_ARG(n_points >= 0, "closest_point: n_points=%lld", (long long)n_points);
     if (n_points == 0) return PSN_OK;
     PSN_CHECK_ARG(points && closest && dist && tri, "closest_point: null point / output pointer");
-    hipLaunchKernelGGL(closest_point_kernel, dim3(md_blocks(n_points)), dim3(256), 0, (hipStream_t)stream, *grid, vertices, faces, cell_start, list,
-                       over_list, n_over, points, order, n_points, closest, dist, tri, reinterpret_cast<unsigned long long*>(n_tests));
+    // (the index expanded: with the struct by value this kernel's unchanged search loop measured 1.5 % slower at 1 M points)
+    hipLaunchKernelGGL(closest_point_kernel, dim3(md_blocks(n_points)), dim3(256), 0, (hipStream_t)stream, index->grid, index->vertices,
+                       index->faces, index->cell_start, index->list, index->over_list, index->n_over, points, order, n_points, closest, dist, tri,
+                       reinterpret_cast<unsigned long long*>(n_tests));
     PSN_CHECK_LAUNCH("closest_point");
     return PSN_OK;
 }

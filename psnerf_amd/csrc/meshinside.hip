@@ -94,12 +94,13 @@ __device__ __forceinline__ void mi_count_tri(const double (&p)[3], const MdTri& 
 
 // One thread per point, points taken in the caller's order.  The walk, the once-only rule and the block shape: the head of this file.
 template <int AXIS>
-__global__ __launch_bounds__(64) void mesh_crossings_kernel(PsnTriGrid g, const double* __restrict__ vertices, const int64_t* __restrict__ faces,
-                                                            const int* __restrict__ cell_start, const int* __restrict__ list,
-                                                            const int* __restrict__ over_list, int64_t n_over, const double* __restrict__ points,
-                                                            const int64_t* __restrict__ order, int64_t n_points, int* __restrict__ above_out,
-                                                            int* __restrict__ below_out, int* __restrict__ on_out,
-                                                            unsigned long long* __restrict__ n_tests) {
+__global__ __launch_bounds__(64) void mesh_crossings_kernel(PsnMeshIndex ix, const double* __restrict__ points, const int64_t* __restrict__ order,
+                                                            int64_t n_points, int* __restrict__ above_out, int* __restrict__ below_out,
+                                                            int* __restrict__ on_out, unsigned long long* __restrict__ n_tests) {
+    const PsnTriGrid& g = ix.grid;
+    const double* __restrict__ vertices = ix.vertices; const int64_t* __restrict__ faces = ix.faces;
+    const int* __restrict__ cell_start = ix.cell_start; const int* __restrict__ list = ix.list;
+    const int* __restrict__ over_list = ix.over_list; const int64_t n_over = ix.n_over;
     constexpr int KX = (AXIS + 1) % 3, KY = (AXIS + 2) % 3, KZ = AXIS;
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     unsigned int tests = 0;
@@ -142,48 +143,28 @@ __global__ __launch_bounds__(64) void mesh_crossings_kernel(PsnTriGrid g, const 
         if (below_out != nullptr) below_out[q] = below;
         if (on_out != nullptr) on_out[q] = on;
     }
-    if (n_tests != nullptr) {   // one atomic per wave (every lane reaches this point)
-        unsigned long long s = tests;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-        if (md_lane() == 0 && s > 0) atomicAdd(n_tests, s);
-    }
+    md_add_tests(n_tests, tests);   // one atomic per wave (every lane reaches this point)
 }
 
 }  // namespace psn
 
-// The query.  grid / cell_start / list / over_list / n_over: the index as psn_closest_point takes it.  points [n_points, 3]; order:
-// null, or a permutation of 0 .. n_points - 1 in which the points are taken (sorted by column, then by cell along the axis);
-// outputs are written at the point's own row whatever the order.  above [n_points]; below, on [n_points] or null (without below the
-// walk starts at the point's own cell; above and on do not change).  n_tests: null, or one counter to which the number of
-// line-triangle tests is ADDED.
-extern "C" int psn_mesh_crossings(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
-                                  const int* list, const int* over_list, int64_t n_over, const double* points, const int64_t* order,
-                                  int64_t n_points, int axis, int* above, int* below, int* on, long long* n_tests, void* stream) {
+// The query.  points [n_points, 3]; order: null, or a permutation of 0 .. n_points - 1 in which the points are taken (sorted by
+// column, then by cell along the axis); outputs are written at the point's own row whatever the order.  above [n_points]; below, on
+// [n_points] or null (without below the walk starts at the point's own cell; above and on do not change).  n_tests: null, or one
+// counter to which the number of line-triangle tests is ADDED.
+extern "C" int psn_mesh_crossings(const PsnMeshIndex* index, const double* points, const int64_t* order, int64_t n_points, int axis, int* above,
+                                  int* below, int* on, long long* n_tests, void* stream) {
     using namespace psn;
-    if (int rc = md_check_grid(grid, "mesh_crossings")) return rc;
-    PSN_CHECK_ARG(vertices && faces && cell_start, "mesh_crossings: null pointer");
-    PSN_CHECK_ARG(n_faces >= 1 && n_faces <= PSN_TRI_GRID_MAX_FACES, "mesh_crossings: n_faces=%lld (1 .. %lld)", (long long)n_faces,
-                  (long long)PSN_TRI_GRID_MAX_FACES);
-    PSN_CHECK_ARG(n_over >= 0 && n_over <= n_faces && (n_over == 0 || over_list), "mesh_crossings: n_over=%lld / null oversize list",
-                  (long long)n_over);
-    PSN_CHECK_ARG(n_over == n_faces || list, "mesh_crossings: null cell list");
+    if (int rc = md_check_index(index, "mesh_crossings")) return rc;
     PSN_CHECK_ARG(n_points >= 0 && n_points <= PSN_CROSSINGS_MAX_POINTS, "mesh_crossings: n_points=%lld (0 .. %lld)", (long long)n_points,
                   (long long)PSN_CROSSINGS_MAX_POINTS);
     PSN_CHECK_ARG(axis >= 0 && axis <= 2, "mesh_crossings: axis=%d (0 .. 2)", axis);
     if (n_points == 0) return PSN_OK;
     PSN_CHECK_ARG(points && above, "mesh_crossings: null point / output pointer");
     const dim3 blocks((unsigned)((n_points + 63) / 64)), threads(64);
-    auto n = reinterpret_cast<unsigned long long*>(n_tests);
-    if (axis == 0)
-        hipLaunchKernelGGL(mesh_crossings_kernel<0>, blocks, threads, 0, (hipStream_t)stream, *grid, vertices, faces, cell_start, list, over_list, n_over,
-                           points, order, n_points, above, below, on, n);
-    else if (axis == 1)
-        hipLaunchKernelGGL(mesh_crossings_kernel<1>, blocks, threads, 0, (hipStream_t)stream, *grid, vertices, faces, cell_start, list, over_list, n_over,
-                           points, order, n_points, above, below, on, n);
-    else
-        hipLaunchKernelGGL(mesh_crossings_kernel<2>, blocks, threads, 0, (hipStream_t)stream, *grid, vertices, faces, cell_start, list, over_list, n_over,
-                           points, order, n_points, above, below, on, n);
+    const auto kernel = axis == 0 ? mesh_crossings_kernel<0> : (axis == 1 ? mesh_crossings_kernel<1> : mesh_crossings_kernel<2>);
+    hipLaunchKernelGGL(kernel, blocks, threads, 0, (hipStream_t)stream, *index, points, order, n_points, above, below, on,
+                       reinterpret_cast<unsigned long long*>(n_tests));
     PSN_CHECK_LAUNCH("mesh_crossings");
     return PSN_OK;
 }

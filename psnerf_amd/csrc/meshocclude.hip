@@ -18,13 +18,11 @@
 namespace psn {
 
 template <bool WORLD>
-__global__ __launch_bounds__(256) void occlusion_rows_kernel(PsnTriGrid g, const double* __restrict__ vertices, const int64_t* __restrict__ faces,
-                                                             const int* __restrict__ cell_start, const int* __restrict__ list,
-                                                             const int* __restrict__ over_list, int64_t n_over, const double* __restrict__ points,
-                                                             const double* __restrict__ normals, int64_t n_rows, const double* __restrict__ table,
-                                                             int K, double bias, double t_max, int* __restrict__ hits_out,
-                                                             int* __restrict__ visible_out, double* __restrict__ ao_out, double* __restrict__ bent_out,
-                                                             int* __restrict__ words_out, unsigned long long* __restrict__ n_tests) {
+__global__ __launch_bounds__(256) void occlusion_rows_kernel(PsnMeshIndex ix, const double* __restrict__ points, const double* __restrict__ normals,
+                                                             int64_t n_rows, const double* __restrict__ table, int K, double bias, double t_max,
+                                                             int* __restrict__ hits_out, int* __restrict__ visible_out, double* __restrict__ ao_out,
+                                                             double* __restrict__ bent_out, int* __restrict__ words_out,
+                                                             unsigned long long* __restrict__ n_tests) {
     extern __shared__ double tab[];   // [K, 3]
     for (int e = threadIdx.x; e < 3 * K; e += 256) tab[e] = table[e];
     __syncthreads();
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(256) void occlusion_rows_kernel(PsnTriGrid g, const
                     MrBest best;
                     MrRay r;
                     if (mr_valid(o0, o1, o2, d0, d1, d2))
-                        mr_cast<true>(g, vertices, faces, cell_start, list, over_list, n_over, o0, o1, o2, d0, d1, d2, 0.0, t_max, r, best, tests);
+                        mr_cast<true>(ix, o0, o1, o2, d0, d1, d2, 0.0, t_max, r, best, tests);
                     if (best.found) {
                         ++hits;
                     } else {
@@ -94,26 +92,18 @@ __global__ __launch_bounds__(256) void occlusion_rows_kernel(PsnTriGrid g, const
             bent_out[3 * i + 2] = ok ? m2 / len : 0.0;
         }
     }
-    mr_add_tests(n_tests, tests);   // one atomic per wave (every lane reaches this point)
+    md_add_tests(n_tests, tests);   // one atomic per wave (every lane reaches this point)
 }
 
 }  // namespace psn
 
-// The query.  grid / cell_start / list / over_list / n_over: the index as psn_ray_cast takes it.  points, normals [n_rows, 3]; table
-// [n_dirs, 3]; outputs per row: hits, visible int32, ao float64, bent float64 [3], words int32 [(n_dirs + 31) / 32] or null.
-// n_tests: null, or one counter to which the number of ray-triangle tests is ADDED.
-extern "C" int psn_occlusion_rows(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
-                                  const int* list, const int* over_list, int64_t n_over, const double* points, const double* normals,
-                                  int64_t n_rows, const double* table, int n_dirs, int mode, double bias, double t_max, int* hits, int* visible,
-                                  double* ao, double* bent, int* words, long long* n_tests, void* stream) {
+// The query.  points, normals [n_rows, 3]; table [n_dirs, 3]; outputs per row: hits, visible int32, ao float64, bent float64 [3],
+// words int32 [(n_dirs + 31) / 32] or null.  n_tests: null, or one counter to which the number of ray-triangle tests is ADDED.
+extern "C" int psn_occlusion_rows(const PsnMeshIndex* index, const double* points, const double* normals, int64_t n_rows, const double* table,
+                                  int n_dirs, int mode, double bias, double t_max, int* hits, int* visible, double* ao, double* bent, int* words,
+                                  long long* n_tests, void* stream) {
     using namespace psn;
-    if (int rc = md_check_grid(grid, "occlusion_rows")) return rc;
-    PSN_CHECK_ARG(vertices && faces && cell_start, "occlusion_rows: null pointer");
-    PSN_CHECK_ARG(n_faces >= 1 && n_faces <= PSN_TRI_GRID_MAX_FACES, "occlusion_rows: n_faces=%lld (1 .. %lld)", (long long)n_faces,
-                  (long long)PSN_TRI_GRID_MAX_FACES);
-    PSN_CHECK_ARG(n_over >= 0 && n_over <= n_faces && (n_over == 0 || over_list), "occlusion_rows: n_over=%lld / null oversize list",
-                  (long long)n_over);
-    PSN_CHECK_ARG(n_over == n_faces || list, "occlusion_rows: null cell list");
+    if (int rc = md_check_index(index, "occlusion_rows")) return rc;
     PSN_CHECK_ARG(n_rows >= 0 && n_rows <= 2147483647LL * 256, "occlusion_rows: n_rows=%lld", (long long)n_rows);
     PSN_CHECK_ARG(n_dirs >= 1 && n_dirs <= PSN_OCC_MAX_DIRS, "occlusion_rows: n_dirs=%d (1 .. %d)", n_dirs, PSN_OCC_MAX_DIRS);
     PSN_CHECK_ARG(mode == PSN_OCC_LOCAL || mode == PSN_OCC_WORLD, "occlusion_rows: mode=%d", mode);
@@ -124,14 +114,9 @@ extern "C" int psn_occlusion_rows(const PsnTriGrid* grid, const double* vertices
     PSN_CHECK_ARG(points && normals && hits && visible && ao && bent, "occlusion_rows: null row / output pointer");
     const dim3 blocks(md_blocks(n_rows)), threads(256);
     const size_t lds = (size_t)n_dirs * 3 * sizeof(double);
-    if (mode == PSN_OCC_WORLD)
-        hipLaunchKernelGGL(occlusion_rows_kernel<true>, blocks, threads, lds, (hipStream_t)stream, *grid, vertices, faces, cell_start, list, over_list,
-                           n_over, points, normals, n_rows, table, n_dirs, bias, t_max, hits, visible, ao, bent, words,
-                           reinterpret_cast<unsigned long long*>(n_tests));
-    else
-        hipLaunchKernelGGL(occlusion_rows_kernel<false>, blocks, threads, lds, (hipStream_t)stream, *grid, vertices, faces, cell_start, list, over_list,
-                           n_over, points, normals, n_rows, table, n_dirs, bias, t_max, hits, visible, ao, bent, words,
-                           reinterpret_cast<unsigned long long*>(n_tests));
+    hipLaunchKernelGGL(mode == PSN_OCC_WORLD ? occlusion_rows_kernel<true> : occlusion_rows_kernel<false>, blocks, threads, lds, (hipStream_t)stream,
+                       *index, points, normals, n_rows, table, n_dirs, bias, t_max, hits, visible, ao, bent, words,
+                       reinterpret_cast<unsigned long long*>(n_tests));
     PSN_CHECK_LAUNCH("occlusion_rows");
     return PSN_OK;
 }

@@ -52,10 +52,12 @@ __device__ __forceinline__ bool mr_valid(double o0, double o1, double o2, double
 // minimum of (t, triangle id) over the accepted triangles in ``best``; ANY: returns at the first accepted triangle.  ``tests`` is
 // advanced by the number of ray-triangle tests.
 template <bool ANY>
-__device__ __forceinline__ void mr_cast(const PsnTriGrid& g, const double* __restrict__ vertices, const int64_t* __restrict__ faces,
-                                        const int* __restrict__ cell_start, const int* __restrict__ list, const int* __restrict__ over_list,
-                                        int64_t n_over, double o0, double o1, double o2, double d0, double d1, double d2, double t_min, double t_max,
-                                        MrRay& r, MrBest& best, unsigned int& tests) {
+__device__ __forceinline__ void mr_cast(const PsnMeshIndex& ix, double o0, double o1, double o2, double d0, double d1, double d2, double t_min,
+                                        double t_max, MrRay& r, MrBest& best, unsigned int& tests) {
+    const PsnTriGrid& g = ix.grid;
+    const double* __restrict__ vertices = ix.vertices; const int64_t* __restrict__ faces = ix.faces;
+    const int* __restrict__ cell_start = ix.cell_start; const int* __restrict__ list = ix.list;
+    const int* __restrict__ over_list = ix.over_list; const int64_t n_over = ix.n_over;
     int kz = 0;
     double big = fabs(d0);
     if (fabs(d1) > big) { kz = 1; big = fabs(d1); }
@@ -121,15 +123,6 @@ __device__ __forceinline__ void mr_cast(const PsnTriGrid& g, const double* __res
             }
         }
     }
-}
-
-// the sum of a per-lane count over the wave, added to the counter once (every lane of the wave must call this)
-__device__ __forceinline__ void mr_add_tests(unsigned long long* __restrict__ n_tests, unsigned int tests) {
-    if (n_tests == nullptr) return;
-    unsigned long long s = tests;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if (md_lane() == 0 && s > 0) atomicAdd(n_tests, s);
 }
 
 }  // namespace psn

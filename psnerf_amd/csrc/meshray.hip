@@ -50,13 +50,11 @@ namespace psn {
 // One thread per ray, rays taken in the caller's order (sorted by the cell where they enter the box, or pixels in small tiles, so
 // that the lanes of a wave walk neighbouring cells).  The walk and its argument: the head of this file.
 template <bool ANY>
-__global__ __launch_bounds__(256) void ray_cast_kernel(PsnTriGrid g, const double* __restrict__ vertices, const int64_t* __restrict__ faces,
-                                                       const int* __restrict__ cell_start, const int* __restrict__ list,
-                                                       const int* __restrict__ over_list, int64_t n_over, const double* __restrict__ origins,
-                                                       const double* __restrict__ directions, const int64_t* __restrict__ order, int64_t n_rays,
-                                                       double t_min, double t_max, double* __restrict__ t_out, int64_t* __restrict__ tri_out,
-                                                       double* __restrict__ bary_out, unsigned char* __restrict__ hit_out,
-                                                       unsigned long long* __restrict__ n_tests) {
+__global__ __launch_bounds__(256) void ray_cast_kernel(PsnMeshIndex ix, const double* __restrict__ origins, const double* __restrict__ directions,
+                                                       const int64_t* __restrict__ order, int64_t n_rays, double t_min, double t_max,
+                                                       double* __restrict__ t_out, int64_t* __restrict__ tri_out, double* __restrict__ bary_out,
+                                                       unsigned char* __restrict__ hit_out, unsigned long long* __restrict__ n_tests) {
+    const double* __restrict__ vertices = ix.vertices; const int64_t* __restrict__ faces = ix.faces;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     unsigned int tests = 0;
     if (i < n_rays) {
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(256) void ray_cast_kernel(PsnTriGrid g, const doubl
         MrBest best;
         MrRay r;
         if (mr_valid(o0, o1, o2, d0, d1, d2))
-            mr_cast<ANY>(g, vertices, faces, cell_start, list, over_list, n_over, o0, o1, o2, d0, d1, d2, t_min, t_max, r, best, tests);
+            mr_cast<ANY>(ix, o0, o1, o2, d0, d1, d2, t_min, t_max, r, best, tests);
         const double nan = __builtin_nan("");
         if (!ANY && best.id != 0x7fffffff) {
             double t, U, V, W, det;
@@ -81,39 +79,28 @@ __global__ __launch_bounds__(256) void ray_cast_kernel(PsnTriGrid g, const doubl
         }
         hit_out[q] = best.found ? 1 : 0;
     }
-    mr_add_tests(n_tests, tests);   // one atomic per wave (every lane reaches this point)
+    md_add_tests(n_tests, tests);   // one atomic per wave (every lane reaches this point)
 }
 
 }  // namespace psn
 
-// The query.  grid / cell_start / list / over_list / n_over: the index as psn_closest_point takes it.  origins, directions
-// [n_rays, 3]; order: null, or a permutation of 0 .. n_rays - 1 in which the rays are taken; outputs are written at the ray's own
-// row whatever the order.  mode PSN_RAY_FIRST_HIT: t [n_rays] (inf on a miss), tri [n_rays] (-1), bary [n_rays, 3] or null (NaN),
-// hit [n_rays] bytes.  mode PSN_RAY_ANY_HIT: hit only; t, tri and bary receive the values of a miss.  n_tests: null, or one counter
-// to which the number of ray-triangle tests is ADDED.
-extern "C" int psn_ray_cast(const PsnTriGrid* grid, const double* vertices, const int64_t* faces, int64_t n_faces, const int* cell_start,
-                            const int* list, const int* over_list, int64_t n_over, const double* origins, const double* directions,
-                            const int64_t* order, int64_t n_rays, double t_min, double t_max, int mode, double* t, int64_t* tri, double* bary,
-                            unsigned char* hit, long long* n_tests, void* stream) {
+// The query.  origins, directions [n_rays, 3]; order: null, or a permutation of 0 .. n_rays - 1 in which the rays are taken; outputs
+// are written at the ray's own row whatever the order.  mode PSN_RAY_FIRST_HIT: t [n_rays] (inf on a miss), tri [n_rays] (-1), bary
+// [n_rays, 3] or null (NaN), hit [n_rays] bytes.  mode PSN_RAY_ANY_HIT: hit only; t, tri and bary receive the values of a miss.
+// n_tests: null, or one counter to which the number of ray-triangle tests is ADDED.
+extern "C" int psn_ray_cast(const PsnMeshIndex* index, const double* origins, const double* directions, const int64_t* order, int64_t n_rays,
+                            double t_min, double t_max, int mode, double* t, int64_t* tri, double* bary, unsigned char* hit, long long* n_tests,
+                            void* stream) {
     using namespace psn;
-    if (int rc = md_check_grid(grid, "ray_cast")) return rc;
-    PSN_CHECK_ARG(vertices && faces && cell_start, "ray_cast: null pointer");
-    PSN_CHECK_ARG(n_faces >= 1 && n_faces <= PSN_TRI_GRID_MAX_FACES, "ray_cast: n_faces=%lld (1 .. %lld)", (long long)n_faces,
-                  (long long)PSN_TRI_GRID_MAX_FACES);
-    PSN_CHECK_ARG(n_over >= 0 && n_over <= n_faces && (n_over == 0 || over_list), "ray_cast: n_over=%lld / null oversize list", (long long)n_over);
-    PSN_CHECK_ARG(n_over == n_faces || list, "ray_cast: null cell list");
+    if (int rc = md_check_index(index, "ray_cast")) return rc;
     PSN_CHECK_ARG(n_rays >= 0, "ray_cast: n_rays=%lld", (long long)n_rays);
     PSN_CHECK_ARG(mode == PSN_RAY_FIRST_HIT || mode == PSN_RAY_ANY_HIT, "ray_cast: mode=%d", mode);
     PSN_CHECK_ARG(t_min <= t_max, "ray_cast: t_min=%g > t_max=%g (or a NaN)", t_min, t_max);
     if (n_rays == 0) return PSN_OK;
     PSN_CHECK_ARG(origins && directions && t && tri && hit, "ray_cast: null ray / output pointer");
     const dim3 blocks(md_blocks(n_rays)), threads(256);
-    if (mode == PSN_RAY_ANY_HIT)
-        hipLaunchKernelGGL(ray_cast_kernel<true>, blocks, threads, 0, (hipStream_t)stream, *grid, vertices, faces, cell_start, list, over_list, n_over,
-                           origins, directions, order, n_rays, t_min, t_max, t, tri, bary, hit, reinterpret_cast<unsigned long long*>(n_tests));
-    else
-        hipLaunchKernelGGL(ray_cast_kernel<false>, blocks, threads, 0, (hipStream_t)stream, *grid, vertices, faces, cell_start, list, over_list, n_over,
-                           origins, directions, order, n_rays, t_min, t_max, t, tri, bary, hit, reinterpret_cast<unsigned long long*>(n_tests));
+    hipLaunchKernelGGL(mode == PSN_RAY_ANY_HIT ? ray_cast_kernel<true> : ray_cast_kernel<false>, blocks, threads, 0, (hipStream_t)stream, *index,
+                       origins, directions, order, n_rays, t_min, t_max, t, tri, bary, hit, reinterpret_cast<unsigned long long*>(n_tests));
     PSN_CHECK_LAUNCH("ray_cast");
     return PSN_OK;
 }

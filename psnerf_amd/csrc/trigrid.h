@@ -1,6 +1,7 @@
 // The uniform grid of triangle lists (PsnTriGrid) as its builder and its queries see it: csrc/meshdist.hip builds it and asks
 // for the closest point, csrc/meshray.hip casts rays through it, csrc/meshinside.hip counts a line's crossings in it.  All must map
-// a coordinate to a cell, and a triangle to its range of cells, in exactly one way, so both mappings live here.
+// a coordinate to a cell, and a triangle to its range of cells, in exactly one way, so both mappings live here; so do the one check of
+// the index the queries take (PsnMeshIndex) and the per-wave counter reduction they share.
 #pragma once
 #include "common.h"
 
@@ -39,6 +40,15 @@ __device__ __forceinline__ int64_t md_range(const PsnTriGrid& g, const MdTri& t,
     return (int64_t)(c1[0] - c0[0] + 1) * (c1[1] - c0[1] + 1) * (c1[2] - c0[2] + 1);
 }
 
+// the sum of a per-lane count over the wave, added to the counter once (every lane of the wave must call this)
+__device__ __forceinline__ void md_add_tests(unsigned long long* __restrict__ n_tests, unsigned int tests) {
+    if (n_tests == nullptr) return;
+    unsigned long long s = tests;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if (md_lane() == 0 && s > 0) atomicAdd(n_tests, s);
+}
+
 static inline int md_check_grid(const PsnTriGrid* g, const char* what) {
     PSN_CHECK_ARG(g != nullptr, "%s: null grid descriptor", what);
     PSN_CHECK_ARG(g->cell > 0.0 && g->cell < __builtin_inf(), "%s: cell size %g", what, g->cell);
@@ -49,6 +59,18 @@ static inline int md_check_grid(const PsnTriGrid* g, const char* what) {
                       g->lo[a], g->hi[a], a);
     }
     PSN_CHECK_ARG(g->max_span >= 1, "%s: max_span=%d", what, g->max_span);
+    return PSN_OK;
+}
+// the PsnMeshIndex of a query, as include/psnerf_hip.h states it
+static inline int md_check_index(const PsnMeshIndex* ix, const char* what) {
+    PSN_CHECK_ARG(ix != nullptr, "%s: null index", what);
+    if (int rc = md_check_grid(&ix->grid, what)) return rc;
+    PSN_CHECK_ARG(ix->vertices && ix->faces && ix->cell_start, "%s: null pointer", what);
+    PSN_CHECK_ARG(ix->n_faces >= 1 && ix->n_faces <= PSN_TRI_GRID_MAX_FACES, "%s: n_faces=%lld (1 .. %lld)", what, (long long)ix->n_faces,
+                  (long long)PSN_TRI_GRID_MAX_FACES);
+    PSN_CHECK_ARG(ix->n_over >= 0 && ix->n_over <= ix->n_faces && (ix->n_over == 0 || ix->over_list), "%s: n_over=%lld / null oversize list", what,
+                  (long long)ix->n_over);
+    PSN_CHECK_ARG(ix->n_over == ix->n_faces || ix->list, "%s: null cell list", what);
     return PSN_OK;
 }
 static inline unsigned md_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }

@@ -1587,49 +1587,57 @@ def tri_grid_fill(grid, vertices, faces, cursor, n_entries):
     return lst
 
 
-def closest_point(grid, vertices, faces, cell_start, lst, over_list, n_over, points, order=None, n_tests=None):
+def mesh_index(grid, vertices, faces, cell_start, lst, over_list, n_over):
+    """The built index as the four queries below take it (PsnMeshIndex): the grid, the mesh, cell_start int32 [cells + 1], the cell
+    lists and the first n_over entries of over_list.  Everything about it is checked here, once; the object keeps the tensors whose
+    addresses it holds (``tensors``)."""
+    ix = PsnMeshIndex()  # noqa: F821
+    ix.grid, ix.n_faces, ix.n_over = grid, faces.shape[0], int(n_over)
+    ix.vertices, ix.faces = _mesh_ptrs(vertices, faces)
+    ix.cell_start, ix.list, ix.over_list = (_tptr(t, name, torch.int32) for name, t in (('cell_start', cell_start), ('list', lst),
+                                                                                       ('over_list', over_list)))
+    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
+    ix.tensors = (vertices, faces, cell_start, lst, over_list)
+    return ix
+
+
+def closest_point(index, points, order=None, n_tests=None):
     """psn_closest_point: points float64 [Q, 3] -> (closest float64 [Q, 3], distance float64 [Q], triangle id int64 [Q]) over the whole
     mesh; order = the permutation in which the points are worked on (or None); n_tests (int64 [1]) accumulates the number of
     point-triangle tests."""
-    vp, fp = _mesh_ptrs(vertices, faces)
     if points.dim() != 2 or points.shape[1] != 3:
         raise RuntimeError('closest_point: points [Q, 3] expected, got %s' % (tuple(points.shape),))
-    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
     q = points.shape[0]
     assert order is None or order.numel() == q
-    dev = vertices.device
+    dev = points.device
     closest = torch.empty(q, 3, dtype=torch.float64, device=dev)
     dist = torch.empty(q, dtype=torch.float64, device=dev)
     tri = torch.empty(q, dtype=torch.int64, device=dev)
     if q == 0:
         return closest, dist, tri
     with _Prof('closest_point', q):
-        _check(_lib.psn_closest_point(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cell_start, 'cell_start', torch.int32),
-                                      _tptr(lst, 'list', torch.int32), _tptr(over_list, 'over_list', torch.int32), int(n_over),
-                                      _tptr(points, 'points', torch.float64), None if order is None else _tptr(order, 'order', torch.int64), q,
+        _check(_lib.psn_closest_point(ctypes.byref(index), _tptr(points, 'points', torch.float64),
+                                      None if order is None else _tptr(order, 'order', torch.int64), q,
                                       closest.data_ptr(), dist.data_ptr(), tri.data_ptr(),
                                       None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'closest_point')
     return closest, dist, tri
 
 
 # --------------------------------------------------------------------------- ray casting (csrc/meshray.hip)
-def ray_cast(grid, vertices, faces, cell_start, lst, over_list, n_over, origins, directions, t_min=0.0, t_max=float('inf'), order=None,
-             any_hit=False, n_tests=None, want_bary=True):
+def ray_cast(index, origins, directions, t_min=0.0, t_max=float('inf'), order=None, any_hit=False, n_tests=None, want_bary=True):
     """psn_ray_cast: origins / directions float64 [Q, 3] -> (t float64 [Q], triangle id int64 [Q], barycentrics float64 [Q, 3] or None,
     hit uint8 [Q]): the first hit with t_min <= t <= t_max over the whole mesh (a miss: inf, -1, NaN, 0), or with ``any_hit`` only
     ``hit``.  order = the permutation in which the rays are worked on (or None); n_tests (int64 [1]) accumulates the number of
     ray-triangle tests."""
-    vp, fp = _mesh_ptrs(vertices, faces)
     for name, x in (('origins', origins), ('directions', directions)):
         _tptr(x, 'ray_cast: %s' % name, torch.float64)
         if x.dim() != 2 or x.shape[1] != 3:
             raise RuntimeError('ray_cast: %s [Q, 3] expected, got %s' % (name, tuple(x.shape)))
     if origins.shape != directions.shape:
         raise RuntimeError('ray_cast: %d origins and %d directions' % (origins.shape[0], directions.shape[0]))
-    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
     q = origins.shape[0]
     assert order is None or order.numel() == q
-    dev = vertices.device
+    dev = origins.device
     t = torch.empty(q, dtype=torch.float64, device=dev)
     tri = torch.empty(q, dtype=torch.int64, device=dev)
     bary = torch.empty(q, 3, dtype=torch.float64, device=dev) if want_bary else None
@@ -1637,30 +1645,26 @@ def ray_cast(grid, vertices, faces, cell_start, lst, over_list, n_over, origins,
     if q == 0:
         return t, tri, bary, hit
     with _Prof('ray_cast_any' if any_hit else 'ray_cast', q):
-        _check(_lib.psn_ray_cast(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cell_start, 'cell_start', torch.int32),
-                                 _tptr(lst, 'list', torch.int32), _tptr(over_list, 'over_list', torch.int32), int(n_over),
-                                 origins.data_ptr(), directions.data_ptr(), None if order is None else _tptr(order, 'order', torch.int64), q,
-                                 float(t_min), float(t_max), RAY_ANY_HIT if any_hit else RAY_FIRST_HIT, t.data_ptr(), tri.data_ptr(),  # noqa: F821
+        _check(_lib.psn_ray_cast(ctypes.byref(index), origins.data_ptr(), directions.data_ptr(),
+                                 None if order is None else _tptr(order, 'order', torch.int64), q, float(t_min), float(t_max),
+                                 RAY_ANY_HIT if any_hit else RAY_FIRST_HIT, t.data_ptr(), tri.data_ptr(),  # noqa: F821
                                  None if bary is None else bary.data_ptr(), hit.data_ptr(),
                                  None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'ray_cast')
     return t, tri, bary, hit
 
 
 # --------------------------------------------------------------------------- occlusion of rows (csrc/meshocclude.hip)
-def occlusion_rows(grid, vertices, faces, cell_start, lst, over_list, n_over, points, normals, table, local=True, bias=0.0, t_max=float('inf'),
-                   bits=False, n_tests=None, out=None):
+def occlusion_rows(index, points, normals, table, local=True, bias=0.0, t_max=float('inf'), bits=False, n_tests=None, out=None):
     """psn_occlusion_rows: points / normals float64 [R, 3], table float64 [K, 3] -> (hits int32 [R], visible int32 [R], ao float64 [R],
     bent float64 [R, 3], words int32 [R, ceil(K / 32)] or None): per row the K rays of the table (about the normal with ``local``, as
     given and only where they face the normal without) any-hit against the whole mesh.  out: the five outputs to write into (words
     None without ``bits``); n_tests (int64 [1]) accumulates the number of ray-triangle tests."""
-    vp, fp = _mesh_ptrs(vertices, faces)
     for name, x in (('points', points), ('normals', normals), ('table', table)):
         _tptr(x, 'occlusion_rows: %s' % name, torch.float64)
         if x.dim() != 2 or x.shape[1] != 3:
             raise RuntimeError('occlusion_rows: %s [R, 3] expected, got %s' % (name, tuple(x.shape)))
     if points.shape != normals.shape:
         raise RuntimeError('occlusion_rows: %d points and %d normals' % (points.shape[0], normals.shape[0]))
-    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
     r, k = points.shape[0], table.shape[0]
     n_words = (k + 31) // 32
     given = (None,) * 5 if out is None else out
@@ -1670,9 +1674,7 @@ def occlusion_rows(grid, vertices, faces, cell_start, lst, over_list, n_over, po
     bent = _out(given[3], (r, 3), points, 'occlusion_rows: bent', torch.float64)
     words = _out(given[4], (r, n_words), points, 'occlusion_rows: words', torch.int32) if bits else None
     with _Prof('occlusion_rows', r * k):
-        _check(_lib.psn_occlusion_rows(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cell_start, 'cell_start', torch.int32),
-                                       _tptr(lst, 'list', torch.int32), _tptr(over_list, 'over_list', torch.int32), int(n_over),
-                                       _eptr(points, table), _eptr(normals, table), r, _eptr(table, vertices), k,
+        _check(_lib.psn_occlusion_rows(ctypes.byref(index), _eptr(points, table), _eptr(normals, table), r, _eptr(table, points), k,
                                        OCC_LOCAL if local else OCC_WORLD, float(bias), float(t_max),  # noqa: F821
                                        _eptr(hits, table), _eptr(visible, table), _eptr(ao, table), _eptr(bent, table),
                                        None if words is None else _eptr(words, table),
@@ -1681,26 +1683,22 @@ def occlusion_rows(grid, vertices, faces, cell_start, lst, over_list, n_over, po
 
 
 # --------------------------------------------------------------------------- crossing counts (csrc/meshinside.hip)
-def mesh_crossings(grid, vertices, faces, cell_start, lst, over_list, n_over, points, axis=2, order=None, want_below=True, want_on=True,
-                   n_tests=None):
+def mesh_crossings(index, points, axis=2, order=None, want_below=True, want_on=True, n_tests=None):
     """psn_mesh_crossings: points float64 [Q, 3] -> (above int32 [Q], below int32 [Q] or None, on int32 [Q] or None): the triangles of
     the whole mesh that the line through each point along ``axis`` crosses above, below and exactly at the point.  order = the
     permutation in which the points are worked on (or None); n_tests (int64 [1]) accumulates the number of line-triangle tests."""
-    vp, fp = _mesh_ptrs(vertices, faces)
     _tptr(points, 'mesh_crossings: points', torch.float64)
     if points.dim() != 2 or points.shape[1] != 3:
         raise RuntimeError('mesh_crossings: points [Q, 3] expected, got %s' % (tuple(points.shape),))
-    assert cell_start.numel() == grid.n[0] * grid.n[1] * grid.n[2] + 1 and 0 <= n_over <= over_list.numel()
     q = points.shape[0]
     assert order is None or order.numel() == q
-    dev = vertices.device
+    dev = points.device
     above = torch.empty(q, dtype=torch.int32, device=dev)
     below = torch.empty(q, dtype=torch.int32, device=dev) if want_below else None
     on = torch.empty(q, dtype=torch.int32, device=dev) if want_on else None
     with _Prof('mesh_crossings', q):
-        _check(_lib.psn_mesh_crossings(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cell_start, 'cell_start', torch.int32),
-                                       _tptr(lst, 'list', torch.int32), _tptr(over_list, 'over_list', torch.int32), int(n_over),
-                                       points.data_ptr(), None if order is None else _tptr(order, 'order', torch.int64), q, int(axis),
+        _check(_lib.psn_mesh_crossings(ctypes.byref(index), points.data_ptr(),
+                                       None if order is None else _tptr(order, 'order', torch.int64), q, int(axis),
                                        above.data_ptr(), None if below is None else below.data_ptr(), None if on is None else on.data_ptr(),
                                        None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'mesh_crossings')
     return above, below, on

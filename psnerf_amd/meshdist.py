@@ -338,9 +338,10 @@ class MeshIndex(object):
     number of queries.  vertices float64 [V, 3] / faces int64 [F, 3]: device tensors, or numpy arrays / CPU tensors that are moved
     to ``device`` once.  Cell edge = max(mean triangle edge, largest box extent / CELLS_PER_AXIS); triangles that span more than
     MAX_SPAN cells (a few long slivers of a scan) are kept in a short list that every query tests directly, so they neither fail
-    nor inflate the cell lists.  Two host reads while building: (bounding box, mean edge, index range) and the list totals."""
+    nor inflate the cell lists; ``cell`` and ``max_span`` override the two.  Two host reads while building: (bounding box, mean edge,
+    index range) and the list totals.  ``index`` is the built index as the hip.* queries take it."""
 
-    def __init__(self, vertices, faces, device=None, name='mesh', profile=False):
+    def __init__(self, vertices, faces, device=None, name='mesh', profile=False, cell=None, max_span=MAX_SPAN):
         from . import hip
         self.vertices, self.faces, _ = device_mesh(vertices, faces, None, device)
         device = self.vertices.device
@@ -357,12 +358,13 @@ class MeshIndex(object):
         if not all(np.isfinite(lo + hi)):
             raise ValueError('%s: a vertex coordinate is not finite' % name)
         extent = [hi[i] - lo[i] for i in range(3)]
-        cell = max(mean_edge if np.isfinite(mean_edge) else 0.0, max(extent) / CELLS_PER_AXIS)
+        if cell is None:
+            cell = max(mean_edge if np.isfinite(mean_edge) else 0.0, max(extent) / CELLS_PER_AXIS)
         if not cell > 0.0:
             cell = 1.0   # every vertex in one point
         n = [int(min(CELLS_PER_AXIS, max(1, np.ceil(extent[i] / cell)))) for i in range(3)]
         self.lo, self.hi, self.cell, self.n = lo, hi, cell, n
-        self.grid = hip.tri_grid(lo, hi, cell, n, MAX_SPAN)
+        self.grid = hip.tri_grid(lo, hi, cell, n, max_span)
         self.build_events = [] if profile else None   # (phase, start event, end event) of the build (tools/bench_chamfer.py)
         counts = torch.zeros(2, dtype=torch.int64, device=device)
         with self._phase('count'):
@@ -377,9 +379,10 @@ class MeshIndex(object):
             self.cell_start = torch.zeros(cell_count.numel() + 1, dtype=torch.int32, device=device)
             self.cell_start[1:] = incl
             cursor = self.cell_start[:-1].clone()
-        with self._phase('fill'):
-            self.list = hip.tri_grid_fill(self.grid, v, f, cursor, n_entries)
+        with self._phase('fill'):   # (no entries: every triangle is oversize, and the list is never read)
+            self.list = hip.tri_grid_fill(self.grid, v, f, cursor, n_entries) if n_entries else torch.zeros(1, dtype=torch.int32, device=device)
         self.over_list, self.n_over, self.n_entries = over_list[:n_over].clone(), n_over, n_entries
+        self.index = hip.mesh_index(self.grid, v, f, self.cell_start, self.list, self.over_list, n_over)
 
     def _phase(self, name):
         return Phase(self.build_events, name)
@@ -407,8 +410,7 @@ class MeshIndex(object):
             raise RuntimeError('MeshIndex.closest_point: points must be a device tensor (host arrays: host_closest_point)')
         points = points.to(torch.float64).reshape(-1, 3).contiguous()
         order = self.home_order(points) if points.shape[0] > 64 else None   # (one wave: nothing to order)
-        return hip.closest_point(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over, points,
-                                 order=order, n_tests=n_tests)
+        return hip.closest_point(self.index, points, order=order, n_tests=n_tests)
 
     def entry_order(self, origins, directions, t_min=0.0):
         """The permutation that sorts the rays by the cell in which they enter the bounding box (the cell of the origin at t_min when
@@ -433,8 +435,7 @@ class MeshIndex(object):
         origins = origins.to(torch.float64).reshape(-1, 3).contiguous()
         directions = directions.to(torch.float64).reshape(-1, 3).contiguous()
         order = self.entry_order(origins, directions, t_min) if sort and origins.shape[0] > 64 else None   # (one wave: nothing to order)
-        t, tri, bary, hit = hip.ray_cast(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over,
-                                         origins, directions, t_min, t_max, order=order, any_hit=any_hit, n_tests=n_tests)
+        t, tri, bary, hit = hip.ray_cast(self.index, origins, directions, t_min, t_max, order=order, any_hit=any_hit, n_tests=n_tests)
         return t, tri, bary, hit.bool()
 
     def crossings(self, points, axis=2, below=True, n_tests=None, sort=True):
@@ -451,8 +452,7 @@ class MeshIndex(object):
         points = points.to(torch.float64).reshape(-1, 3).contiguous()
         axes = ((axis + 1) % 3, (axis + 2) % 3, axis)
         order = self.home_order(points, axes) if sort and points.shape[0] > 64 else None   # (one wave: nothing to order)
-        return hip.mesh_crossings(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over, points,
-                                  axis=axis, order=order, want_below=below, n_tests=n_tests)
+        return hip.mesh_crossings(self.index, points, axis=axis, order=order, want_below=below, n_tests=n_tests)
 
     def contains(self, points, axis=2, vote=False):
         """Is each of points [Q, 3] inside the mesh -> bool [Q]: the parity of the crossings above the point along ``axis``.  Exact
@@ -475,8 +475,7 @@ class MeshIndex(object):
         if not torch.is_tensor(table):
             table = torch.from_numpy(np.ascontiguousarray(np.asarray(table, dtype=np.float64)))
         table = table.to(device=points.device, dtype=torch.float64).contiguous()
-        return hip.occlusion_rows(self.grid, self.vertices, self.faces, self.cell_start, self.list, self.over_list, self.n_over, points, normals,
-                                  table, local=local, bias=bias, t_max=t_max, bits=bits, n_tests=n_tests, out=out)
+        return hip.occlusion_rows(self.index, points, normals, table, local=local, bias=bias, t_max=t_max, bits=bits, n_tests=n_tests, out=out)
 
     def face_areas_cumulative(self):
         return torch.cumsum(face_areas(self.vertices, self.faces), dim=0)

@@ -267,14 +267,26 @@ def test_argument_validation_of_the_mesh_distance_entries_needs_no_gpu():
     assert rc == -1 and b'n_entries' in lib.psn_last_error()
     rc = lib.psn_tri_grid_fill(ctypes.byref(g), dummy, dummy, 5, None, 10, dummy, None)
     assert rc == -1 and b'null pointer' in lib.psn_last_error()
-    args = (dummy, dummy, 5, dummy, dummy, dummy)
-    rc = lib.psn_closest_point(ctypes.byref(g), *args, 6, dummy, None, 3, dummy, dummy, dummy, None, None)
+    assert ctypes.sizeof(hip.PsnMeshIndex) == 128
+
+    def index(grid=g, n_over=0):
+        ix = hip.PsnMeshIndex()
+        ix.grid, ix.vertices, ix.faces, ix.n_faces, ix.cell_start, ix.list, ix.over_list, ix.n_over = grid, 64, 64, 5, 64, 64, 64, n_over
+        return ctypes.byref(ix)
+    rc = lib.psn_closest_point(index(n_over=6), dummy, None, 3, dummy, dummy, dummy, None, None)
     assert rc == -1 and b'n_over' in lib.psn_last_error()
-    rc = lib.psn_closest_point(ctypes.byref(g), *args, 0, None, None, 3, dummy, dummy, dummy, None, None)
+    rc = lib.psn_closest_point(index(), None, None, 3, dummy, dummy, dummy, None, None)
     assert rc == -1 and b'null point' in lib.psn_last_error()
-    rc = lib.psn_closest_point(ctypes.byref(g), *args, 0, dummy, None, -1, dummy, dummy, dummy, None, None)
+    rc = lib.psn_closest_point(index(), dummy, None, -1, dummy, dummy, dummy, None, None)
     assert rc == -1 and b'n_points' in lib.psn_last_error()
-    assert lib.psn_closest_point(ctypes.byref(g), *args, 0, None, None, 0, None, None, None, None, None) == 0   # Q = 0: a no-op
+    assert lib.psn_closest_point(index(), None, None, 0, None, None, None, None, None) == 0   # Q = 0: a no-op
+    # the four queries after the index, with otherwise valid arguments: a null index and (below) a bad grid are the first thing refused
+    queries = ((lib.psn_closest_point, (dummy, None, 3, dummy, dummy, dummy, None, None)),
+               (lib.psn_ray_cast, (dummy, dummy, None, 3, 0.0, 1.0, hip.RAY_FIRST_HIT, dummy, dummy, dummy, dummy, None, None)),
+               (lib.psn_mesh_crossings, (dummy, None, 3, 2, dummy, dummy, dummy, None, None)),
+               (lib.psn_occlusion_rows, (dummy, dummy, 3, dummy, 4, hip.OCC_LOCAL, 0.0, 1.0, dummy, dummy, dummy, dummy, dummy, None, None)))
+    for fn, rest in queries:
+        assert fn(None, *rest) == -1 and b'null' in lib.psn_last_error(), lib.psn_last_error()
     for bad, word in ((dict(cell=0.0), b'cell size'), (dict(cell=float('nan')), b'cell size'), (dict(n=[4, 0, 4]), b'cells on axis 1'),
                       (dict(n=[4, 4, 257]), b'cells on axis 2'), (dict(lo=[0, 2, 0]), b'bounding box'),
                       (dict(hi=[1, float('inf'), 1]), b'bounding box'), (dict(max_span=0), b'max_span')):
@@ -282,12 +294,14 @@ def test_argument_validation_of_the_mesh_distance_entries_needs_no_gpu():
         kw.update(bad)
         b = hip.tri_grid(**kw)
         for fn, rest in ((lib.psn_tri_grid_count, (dummy, dummy, 1, dummy, dummy, dummy, None)),
-                         (lib.psn_tri_grid_fill, (dummy, dummy, 1, dummy, 1, dummy, None)),
-                         (lib.psn_closest_point, args + (0, dummy, None, 3, dummy, dummy, dummy, None, None))):
+                         (lib.psn_tri_grid_fill, (dummy, dummy, 1, dummy, 1, dummy, None))):
             rc = fn(ctypes.byref(b), *rest)
+            assert rc == -1 and word in lib.psn_last_error(), (bad, lib.psn_last_error())
+        for fn, rest in queries:
+            rc = fn(index(grid=b), *rest)
             assert rc == -1 and word in lib.psn_last_error(), (bad, lib.psn_last_error())
     # the wrappers refuse host tensors: there is no host fall-back behind them
     import torch
     with pytest.raises(RuntimeError, match='HIP device tensor'):
-        hip.closest_point(g, torch.zeros(3, 3, dtype=torch.float64), torch.zeros(1, 3, dtype=torch.int64), torch.zeros(65, dtype=torch.int32),
-                          torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.int32), 0, torch.zeros(2, 3, dtype=torch.float64))
+        hip.mesh_index(g, torch.zeros(3, 3, dtype=torch.float64), torch.zeros(1, 3, dtype=torch.int64), torch.zeros(65, dtype=torch.int32),
+                       torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.int32), 0)

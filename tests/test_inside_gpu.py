@@ -97,8 +97,7 @@ def test_device_against_the_definition(cuda, name):
             assert half[1] is None and torch.equal(half[0], out[0]) and torch.equal(half[2], out[2]), what + ': below=False changes above / on'
             # a second run on a rebuilt index; the order of the work: a random permutation, and none
             assert equal(out, again.crossings(pd.clone(), axis)), what + ': two runs differ'
-            raw = lambda order: hip.mesh_crossings(index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list,
-                                                   index.n_over, pd, axis=axis, order=order)
+            raw = lambda order: hip.mesh_crossings(index.index, pd, axis=axis, order=order)
             assert equal(out, raw(None)) and equal(out, raw(torch.randperm(len(p), generator=g).to(cuda))), what + ': the order changes the result'
             if sname == 'uniform, box + 10 %':
                 assert torch.equal(index.contains(pd, axis), out[0] % 2 == 1)
@@ -134,8 +133,7 @@ def test_c_abi_errors(cuda):
     v, f = rc.icosphere(2)
     index = md.MeshIndex(v, f, device=cuda)
     p = torch.zeros(10, 3, dtype=torch.float64, device=cuda)
-    count = lambda p, **kw: hip.mesh_crossings(index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over,
-                                               p, **kw)
+    count = lambda p, **kw: hip.mesh_crossings(index.index, p, **kw)
     above, below, on = count(p)
     assert above.tolist() == [1] * 10 and below.tolist() == [1] * 10 and on.tolist() == [0] * 10
     wide = torch.ones(10, 6, dtype=torch.float64, device=cuda)
@@ -151,13 +149,19 @@ def test_c_abi_errors(cuda):
     assert above.shape == (0,) and below.shape == (0,) and on.shape == (0,) and above.is_cuda and above.dtype == torch.int32
     # the C ABI itself: null pointers, axis 3, Q = 0
     out = torch.full((10,), -7, dtype=torch.int32, device=cuda)
-    args = lambda **kw: [kw.get(k, d) for k, d in (('grid', ctypes.byref(index.grid)), ('vertices', index.vertices.data_ptr()),
-                                                   ('faces', index.faces.data_ptr()), ('n_faces', len(f)), ('cell_start', index.cell_start.data_ptr()),
-                                                   ('list', index.list.data_ptr()), ('over_list', None), ('n_over', 0), ('points', p.data_ptr()),
-                                                   ('order', None), ('n_points', 10), ('axis', 2), ('above', out.data_ptr()), ('below', None),
-                                                   ('on', None), ('n_tests', None), ('stream', None))]
-    call = lambda **kw: hip._lib.psn_mesh_crossings(*args(**kw))
-    for kw in ({'grid': None}, {'vertices': None}, {'faces': None}, {'cell_start': None}, {'list': None}, {'points': None}, {'above': None},
+    def struct(**fields):                                        # the index with no oversize list, and one field changed in the copy
+        ix = hip.PsnMeshIndex.from_buffer_copy(index.index)
+        for k, value in dict({'over_list': None, 'n_over': 0}, **fields).items():
+            setattr(ix, k, value)
+        return ctypes.byref(ix)
+
+    def call(**kw):
+        ix = struct(**{k: kw.pop(k) for k in list(kw) if k in dict(hip.PsnMeshIndex._fields_)})
+        return hip._lib.psn_mesh_crossings(*[kw.get(k, d) for k, d in (('index', ix), ('points', p.data_ptr()), ('order', None), ('n_points', 10),
+                                                                        ('axis', 2), ('above', out.data_ptr()), ('below', None), ('on', None),
+                                                                        ('n_tests', None), ('stream', None))])
+    assert index.index.n_faces == len(f)
+    for kw in ({'index': None}, {'vertices': None}, {'faces': None}, {'cell_start': None}, {'list': None}, {'points': None}, {'above': None},
                {'axis': 3}, {'axis': -1}, {'n_points': -1}, {'n_faces': 0}, {'n_over': 1}):
         assert call(**kw) == hip.E_ARG, kw                       # noqa: F821 (from the header)
         assert b'mesh_crossings' in hip._lib.psn_last_error()

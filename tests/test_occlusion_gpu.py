@@ -7,6 +7,7 @@ walks them with the function psn_ray_cast instantiates, which loses no triangle 
 are integers and the bent normal is a sum in index order.  So hits, visible and words are compared exactly and ao and bent bit for
 bit.  A mismatch is a finding about the order of operations or the walk, not a tolerance to widen.  Outputs land in guarded buffers
 (NaN / a sentinel), so a row the kernel skips shows."""
+import collections
 import ctypes
 
 import numpy as np
@@ -43,19 +44,10 @@ def guards(R, K, cuda, bits=True):
 def index_of(c, name, cuda):
     """The MeshIndex of a case; for the all-oversize case the same mesh under a grid of small cells with max_span = 1, built by the
     index's own two passes, so that every face lands in the oversize list and the cell lists are empty."""
-    from psnerf_amd import hip
-    index = md.MeshIndex(c['v'], c['f'], device=cuda)
     if 'every face oversize' not in name:
-        return index
-    cell = oc.ALL_OVERSIZE_CELL
-    index.cell, index.n = cell, [int(np.ceil((index.hi[a] - index.lo[a]) / cell)) for a in range(3)]
-    index.grid = hip.tri_grid(index.lo, index.hi, cell, index.n, 1)
-    counts = torch.zeros(1, dtype=torch.int64, device=cuda)
-    cell_count, over_list = hip.tri_grid_count(index.grid, index.vertices, index.faces, counts)
-    assert int(cell_count.sum()) == 0 and int(counts.item()) == len(c['f'])
-    index.cell_start = torch.zeros(cell_count.numel() + 1, dtype=torch.int32, device=cuda)
-    index.list = torch.zeros(1, dtype=torch.int32, device=cuda)              # (never read: every list is empty)
-    index.over_list, index.n_over, index.n_entries = over_list.clone(), len(c['f']), 0
+        return md.MeshIndex(c['v'], c['f'], device=cuda)
+    index = md.MeshIndex(c['v'], c['f'], device=cuda, cell=oc.ALL_OVERSIZE_CELL, max_span=1)
+    assert index.n_entries == 0 and int(index.cell_start.sum()) == 0 and index.n_over == len(index.over_list) == len(c['f'])
     return index
 
 
@@ -114,8 +106,7 @@ def test_against_materialised_rays(cuda, name):
     n_rays = torch.zeros(1, dtype=torch.int64, device=cuda)
     hits = index.occlusion(dev(c['points'], cuda), dev(c['normals'], cuda), dev(c['table'], cuda), local=c['local'], bias=c['bias'], t_max=c['t_max'],
                            n_tests=n_fused)[0].cpu().numpy()
-    hip.ray_cast(index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over, od, dd, 0.0, c['t_max'],
-                 any_hit=True, n_tests=n_rays)
+    hip.ray_cast(index.index, od, dd, 0.0, c['t_max'], any_hit=True, n_tests=n_rays)
     print('%s: %d rays, %d blocked; tests: fused %d, materialised %d' % (name, int(keep.sum()), int(blocked.sum()), n_fused.item(), n_rays.item()))
     assert np.array_equal(hits[~c['dead']], blocked.reshape(R, K).sum(axis=1)[~c['dead']])
     assert 0 < int(n_fused.item()) <= int(n_rays.item())
@@ -166,8 +157,7 @@ def test_c_abi_errors(cuda):
     p = torch.zeros(10, 3, dtype=torch.float64, device=cuda)
     n = torch.ones(10, 3, dtype=torch.float64, device=cuda)
     table = lambda K: dev(mo.hemisphere_table(K) if K else np.zeros((0, 3)), cuda)
-    call = lambda p, n, t, **kw: hip.occlusion_rows(index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over,
-                                                    p, n, t, **kw)
+    call = lambda p, n, t, **kw: hip.occlusion_rows(index.index, p, n, t, **kw)
     assert bool((call(p, n, table(1024))[0] == 1024).all())                  # rows at the centre of the sphere: everything is blocked
     wide = torch.ones(10, 6, dtype=torch.float64, device=cuda)
     for bad in (lambda: call(p, n, table(0)), lambda: call(p, n, table(1025)), lambda: call(p.cpu(), n, table(4)), lambda: call(p, n.float(), table(4)),
@@ -181,15 +171,22 @@ def test_c_abi_errors(cuda):
     # null pointers and a bad mode, which the wrapper cannot produce: the entry point itself
     out = guards(10, 4, cuda)
     t4 = table(4)
-    args = [ctypes.byref(index.grid), index.vertices.data_ptr(), index.faces.data_ptr(), index.faces.shape[0], index.cell_start.data_ptr(),
-            index.list.data_ptr(), index.over_list.data_ptr() or index.vertices.data_ptr(), index.n_over, p.data_ptr(), n.data_ptr(), 10, t4.data_ptr(),
-            4, hip.OCC_LOCAL, 0.0, float('inf'), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), None, None]
-    assert hip._lib.psn_occlusion_rows(*args) == 0
+    args = collections.OrderedDict([('index', ctypes.byref(index.index)), ('points', p.data_ptr()), ('normals', n.data_ptr()), ('n_rows', 10),
+                                    ('table', t4.data_ptr()), ('n_dirs', 4), ('mode', hip.OCC_LOCAL), ('bias', 0.0), ('t_max', float('inf')),
+                                    ('hits', out[0].data_ptr()), ('visible', out[1].data_ptr()), ('ao', out[2].data_ptr()),
+                                    ('bent', out[3].data_ptr()), ('words', out[4].data_ptr()), ('n_tests', None), ('stream', None)])
+    assert hip._lib.psn_occlusion_rows(*args.values()) == 0
     torch.cuda.synchronize()
     assert bool((out[0] == 4).all())
-    for at, value in ((0, None), (1, None), (2, None), (4, None), (8, None), (9, None), (11, None), (16, None), (17, None), (18, None), (19, None),
-                      (13, 2), (13, -1), (12, 0), (12, 1025), (10, -1)):
-        broken = list(args)
-        broken[at] = value
-        assert hip._lib.psn_occlusion_rows(*broken) == hip.E_ARG, 'argument %d = %r' % (at, value)
+    for key, value in (('index', None), ('vertices', None), ('faces', None), ('cell_start', None), ('points', None), ('normals', None),
+                       ('table', None), ('hits', None), ('visible', None), ('ao', None), ('bent', None), ('mode', 2), ('mode', -1), ('n_dirs', 0),
+                       ('n_dirs', 1025), ('n_rows', -1)):
+        broken = collections.OrderedDict(args)
+        if key in broken:
+            broken[key] = value
+        else:                                                            # a field of the index: one changed in a copy of the struct
+            ix = hip.PsnMeshIndex.from_buffer_copy(index.index)
+            setattr(ix, key, value)
+            broken['index'] = ctypes.byref(ix)
+        assert hip._lib.psn_occlusion_rows(*broken.values()) == hip.E_ARG, '%s = %r' % (key, value)
         assert b'occlusion_rows' in hip._lib.psn_last_error()

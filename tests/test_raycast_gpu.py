@@ -79,8 +79,7 @@ def test_device_against_the_definition(cuda, name):
         out = index.ray_cast(od, dd, t_min, t_max, n_tests=n_tests)
         assert same(out, again.ray_cast(od.clone(), dd.clone(), t_min, t_max)), what + ': two runs differ'
         # the order of the work changes nothing: a random permutation, and none
-        raw = lambda order: hip.ray_cast(index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over,
-                                         od, dd, t_min, t_max, order=order)
+        raw = lambda order: hip.ray_cast(index.index, od, dd, t_min, t_max, order=order)
         plain = raw(None)
         assert same(plain, raw(torch.randperm(len(o), generator=g).to(cuda))), what + ': the order changes the result'
         assert same(out[:3], plain[:3]) and torch.equal(out[3], plain[3].bool())
@@ -187,8 +186,7 @@ def test_c_abi_errors(cuda):
     index = md.MeshIndex(v, f, device=cuda)
     o = torch.zeros(10, 3, dtype=torch.float64, device=cuda)
     d = torch.ones(10, 3, dtype=torch.float64, device=cuda)
-    cast = lambda o, d, t_min=0.0, t_max=1.0: hip.ray_cast(index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list,
-                                                           index.n_over, o, d, t_min, t_max)
+    cast = lambda o, d, t_min=0.0, t_max=1.0: hip.ray_cast(index.index, o, d, t_min, t_max)
     assert bool(cast(o, d, 0.0, 3.0)[3].all())
     wide = torch.ones(10, 6, dtype=torch.float64, device=cuda)
     for bad in (lambda: cast(o.cpu(), d), lambda: cast(o, d.float()), lambda: cast(o, d, 2.0, 1.0), lambda: cast(o, d, float('nan'), 1.0),

@@ -41,8 +41,7 @@ def one_pass(md, meshes, n, seed, events, sort=True, counters=None):
         if sort:
             return index.closest_point(p, n_tests=n_tests)[1]
         from psnerf_amd import hip   # the same kernel on the points as they come: the binding below MeshIndex
-        return hip.closest_point(index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over, p,
-                                 order=None, n_tests=n_tests)[1]
+        return hip.closest_point(index.index, p, order=None, n_tests=n_tests)[1]
     with Phase(events, 'query'):
         d01 = query(idx[1], pts[0], None if counters is None else counters[1:2])
         d10 = query(idx[0], pts[1], None if counters is None else counters[0:1])

@@ -57,9 +57,8 @@ def main():
         n = args.points
         points = torch.from_numpy(lo + np.random.RandomState(0).random_sample((n, 3)) * (hi - lo)).to(dev)
         counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        raw = lambda axis, order, below, n_tests=None: hip.mesh_crossings(
-            index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over, points, axis=axis, order=order,
-            want_below=below, want_on=below, n_tests=n_tests)
+        raw = lambda axis, order, below, n_tests=None: hip.mesh_crossings(index.index, points, axis=axis, order=order, want_below=below,
+                                                                          want_on=below, n_tests=n_tests)
         kernel = {}
         for axis in (2, 0):
             order = index.home_order(points, ((axis + 1) % 3, (axis + 2) % 3, axis))

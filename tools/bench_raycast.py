@@ -65,9 +65,8 @@ def main():
     with ops.strict():
         v, f = extracted_mesh(net, dev, 64, 3)
         index = md.MeshIndex(v, f)
-        raw = lambda o, d, t_min, t_max, order, any_hit, n_tests=None: hip.ray_cast(
-            index.grid, index.vertices, index.faces, index.cell_start, index.list, index.over_list, index.n_over, o, d, t_min, t_max, order=order,
-            any_hit=any_hit, n_tests=n_tests)
+        raw = lambda o, d, t_min, t_max, order, any_hit, n_tests=None: hip.ray_cast(index.index, o, d, t_min, t_max, order=order, any_hit=any_hit,
+                                                                                    n_tests=n_tests)
         counter = torch.zeros(1, dtype=torch.int64, device=dev)
 
         # ---- primary rays: one view
