@@ -1093,6 +1093,61 @@ int psn_vc_face_flags(const double* vertices, const int64_t* faces, int64_t n_fa
                       unsigned char* flipped, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Mesh connectivity and smoothing: the edge table of a triangle mesh, vertex rings, per-vertex corner runs, vertex normals over
+ * them, the lambda | mu (Taubin) smoothing step and the area / volume sums (csrc/meshtopo.hip; the numpy definitions, which these
+ * kernels repeat operation for operation in float64, are psnerf_amd/meshtopo.py:host_* and psnerf_amd/meshsmooth.py:host_smooth).
+ * The reference has none of it.  The stable sorts and the head-flag scan between the kernels are the caller's (torch).
+ *   vertices float64 [V, 3];  faces int64 [F, 3];  0 <= V <= PSN_CC_MAX_VERTICES, 0 <= F <= PSN_CC_MAX_FACES.  A face with an index
+ *   outside 0 .. V - 1 is SKIPPED and PSN_TOPO_E_INDEX is set in status (int32 [1] on the device, zeroed by the caller, who reads it
+ *   with the counters and raises).  A face with a repeated index is degenerate: legal, and it contributes no half-edge.
+ *
+ * psn_topo_edge_keys: keys int64 [3 F]; half-edge h = 3 f + k of a non-degenerate face runs from a = f[k] to b = f[(k + 1) % 3] and
+ *   has the key min(a, b) V + max(a, b); the three keys of a degenerate or skipped face are INT64_MAX, which sorts last.
+ * psn_topo_edges: sorted_keys / order int64 [3 F] = the caller's STABLE sort of those keys and its permutation; rank_incl int64
+ *   [3 F] = the inclusive scan of the head flags (a position is a head when its key is not INT64_MAX and differs from its
+ *   predecessor's), n_edges = E its total.  -> edges int64 [E, 2] = (lo, hi) ascending by key; count int32 [E] = the half-edges of
+ *   the run; forward int32 [E] = those with a < b; halfedge_edge int64 [3 F] = the rank of each half-edge's edge, -1 for INT64_MAX;
+ *   vertex_used bytes [V] = 1 for every vertex of an edge, vertex_open bytes [V] = 1 for every vertex of an edge with count != 2
+ *   (both zeroed here); counters int64 [4] (zeroed here) = edges with count == 1, with count > 2, with count == 2 and
+ *   forward != 1, and degenerate (or skipped) faces.  Integer counters only: ballot + popcount per wave, one atomic per workgroup.
+ * psn_topo_ring_keys: edges int64 [E, 2] -> keys int64 [2 E]: lo V + hi and hi V + lo.  Sorted, key / V owns the run and key % V is
+ *   the neighbour: every neighbour once, ascending.
+ * psn_topo_corner_keys: keys int64 [3 F], corner-major: keys[k F + f] = f[k] (V for a skipped face: behind every run).  The caller's
+ *   stable sort gives every vertex its (corner, face) pairs in ascending (k, f); degenerate faces stay in the runs.
+ * psn_topo_runs: sorted_keys int64 [n] ascending -> start int64 [V + 1], start[x] = the first position whose key / div is >= x (n where
+ *   there is none; a key / div above V counts as V); rem int64 [n] (or null) = key % div, -1 for such a key.
+ * psn_topo_vertex_normals: corner_start int64 [V + 1] and corner int64 [3 F] (values k F + f) from the two calls above -> normals
+ *   float64 [V, 3]: from +0.0, per corner of the run in order, += (b - a) x (c - a) of its face (PSN_TOPO_WEIGHT_AREA) or that
+ *   divided by its length sqrt((nx nx + ny ny) + nz nz), nothing for a face without length (PSN_TOPO_WEIGHT_UNIFORM); then divided by
+ *   the sum's length formed the same way, zero where that is not > 0.
+ * psn_topo_smooth_step: ring_start int64 [V + 1], ring int64 [n_ring] -> out [V, 3] (must not be x): per vertex with a non-empty
+ *   ring of n neighbours and pinned[v] == 0 (pinned bytes [V], or null: none), per axis acc = +0.0, acc += x[w] in ring order,
+ *   m = acc / n, out = x + s (m - x); every other vertex keeps its bits.
+ * psn_topo_measures: out float64 [2] = the sum of 0.5 |(b - a) x (c - a)| and of (a . (b x c)) / 6 over the faces.  partial float64
+ *   [2 PSN_TOPO_MEASURE_BLOCKS]: workspace; a fixed grid of per-workgroup sums and a fixed-order second step, so two calls give the
+ *   same bits; the order of the sums is not numpy's (within F 2^-53 relative of the sum of the terms' absolute values).
+ * Errors: PSN_E_ARG for null pointers and bad arguments; PSN_E_UNSUPPORTED for sizes beyond the limits; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_TOPO_E_INDEX 1
+#define PSN_TOPO_WEIGHT_AREA 0
+#define PSN_TOPO_WEIGHT_UNIFORM 1
+#define PSN_TOPO_MEASURE_BLOCKS 1024
+int psn_topo_edge_keys(const int64_t* faces, int64_t n_faces, int64_t n_vertices, int64_t* keys, int* status, void* stream);
+int psn_topo_edges(const int64_t* sorted_keys, const int64_t* order, const int64_t* rank_incl, const int64_t* faces, int64_t n_faces,
+                   int64_t n_vertices, int64_t n_edges, int64_t* edges, int* count, int* forward, int64_t* halfedge_edge,
+                   unsigned char* vertex_used, unsigned char* vertex_open, long long* counters, void* stream);
+int psn_topo_ring_keys(const int64_t* edges, int64_t n_edges, int64_t n_vertices, int64_t* keys, void* stream);
+int psn_topo_corner_keys(const int64_t* faces, int64_t n_faces, int64_t n_vertices, int64_t* keys, int* status, void* stream);
+int psn_topo_runs(const int64_t* sorted_keys, int64_t n_keys, int64_t div, int64_t n_vertices, int64_t* start, int64_t* rem,
+                  void* stream);
+int psn_topo_vertex_normals(const double* vertices, const int64_t* faces, int64_t n_faces, int64_t n_vertices,
+                            const int64_t* corner_start, const int64_t* corner, int weight, double* normals, void* stream);
+int psn_topo_smooth_step(const double* x, int64_t n_vertices, const int64_t* ring_start, const int64_t* ring, int64_t n_ring,
+                         const unsigned char* pinned, double s, double* out, void* stream);
+int psn_topo_measures(const double* vertices, const int64_t* faces, int64_t n_faces, int64_t n_vertices, double* partial, double* out,
+                      void* stream);
+
+/* ------------------------------------------------------------------------
  * Image evaluation: what the reference's evaluation.py computes per image pair and per view (csrc/imgmetrics.hip; the float64
  * numpy definition is psnerf_amd/imgmetrics.py:host_*).  float64 arithmetic, no floating-point atomics: each call writes one row
  * of partial sums per tile / chunk into ``partial`` (psn_img_workspace doubles; every row written on every call) and a second,

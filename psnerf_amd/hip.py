@@ -1836,6 +1836,142 @@ def vc_face_flags(vertices, faces, g, positions, face_keep):
     return vertex_keep, flipped
 
 
+# --------------------------------------------------------------------------- mesh connectivity and smoothing (csrc/meshtopo.hip)
+def _faces_ptr(faces, what, stand_in):
+    """Device pointer of faces int64 [F, 3]; F may be 0 (``stand_in``: see _eptr)."""
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError('%s: faces [F, 3] expected, got %s' % (what, tuple(faces.shape)))
+    _tptr(faces, 'faces', torch.int64)
+    return _eptr(faces, stand_in)
+
+
+def topo_edge_keys(faces, n_vertices, status, out=None):
+    """psn_topo_edge_keys: faces int64 [F, 3] -> keys int64 [3 F], min(a, b) V + max(a, b) per half-edge h = 3 f + k, INT64_MAX for a
+    degenerate or skipped face.  status (int32 [1] on the device, zeroed by the caller) collects TOPO_E_* bits."""
+    fp = _faces_ptr(faces, 'topo_edge_keys', status)
+    n_f = faces.shape[0]
+    assert status.numel() == 1
+    keys = _out(out, (3 * n_f,), faces, 'topo_edge_keys', torch.int64)
+    with _Prof('topo_edge_keys', 48 * n_f):
+        _check(_lib.psn_topo_edge_keys(fp, n_f, int(n_vertices), _eptr(keys, status), _tptr(status, 'status', torch.int32), _stream()),
+               'topo_edge_keys')
+    return keys
+
+
+def topo_edges(sorted_keys, order, rank_incl, faces, n_vertices, n_edges, out=None):
+    """psn_topo_edges: the stable sort of the half-edge keys, its permutation and the inclusive head-flag scan -> (edges int64 [E, 2],
+    count int32 [E], forward int32 [E], halfedge_edge int64 [3 F], vertex_used uint8 [V], vertex_open uint8 [V], counters int64 [4]:
+    boundary, non-manifold, inconsistent edges and degenerate faces).  ``out``: a tuple of the seven, or None."""
+    n_f, n_v, n_e = faces.shape[0], int(n_vertices), int(n_edges)
+    assert sorted_keys.numel() == order.numel() == rank_incl.numel() == 3 * n_f
+    for t, name in ((sorted_keys, 'sorted_keys'), (order, 'order'), (rank_incl, 'rank_incl')):
+        _tptr(t, name, torch.int64)
+    out = (None,) * 7 if out is None else out
+    edges = _out(out[0], (n_e, 2), faces, 'topo_edges: edges', torch.int64)
+    count = _out(out[1], (n_e,), faces, 'topo_edges: count', torch.int32)
+    forward = _out(out[2], (n_e,), faces, 'topo_edges: forward', torch.int32)
+    halfedge_edge = _out(out[3], (3 * n_f,), faces, 'topo_edges: halfedge_edge', torch.int64)
+    used = _out(out[4], (n_v,), faces, 'topo_edges: vertex_used', torch.uint8)
+    is_open = _out(out[5], (n_v,), faces, 'topo_edges: vertex_open', torch.uint8)
+    counters = _out(out[6], (4,), faces, 'topo_edges: counters', torch.int64)
+    fp = _faces_ptr(faces, 'topo_edges', counters)
+    with _Prof('topo_edges', 3 * n_f * (8 + 8 + 8 + 16 + 8) + n_e * 24 + 2 * n_v):
+        _check(_lib.psn_topo_edges(_eptr(sorted_keys, counters), _eptr(order, counters), _eptr(rank_incl, counters), fp, n_f, n_v, n_e,
+                                   _eptr(edges, counters), _eptr(count, counters), _eptr(forward, counters), _eptr(halfedge_edge, counters),
+                                   _eptr(used, counters), _eptr(is_open, counters), counters.data_ptr(), _stream()), 'topo_edges')
+    return edges, count, forward, halfedge_edge, used, is_open, counters
+
+
+def topo_ring_keys(edges, n_vertices):
+    """psn_topo_ring_keys: edges int64 [E, 2] -> keys int64 [2 E], the directed pairs lo V + hi and hi V + lo."""
+    if edges.dim() != 2 or edges.shape[1] != 2:
+        raise RuntimeError('topo_ring_keys: edges [E, 2] expected, got %s' % (tuple(edges.shape),))
+    _tptr(edges, 'edges', torch.int64)
+    n_e = edges.shape[0]
+    keys = torch.empty(2 * n_e, dtype=torch.int64, device=edges.device)
+    if n_e:
+        with _Prof('topo_ring_keys', 32 * n_e):
+            _check(_lib.psn_topo_ring_keys(edges.data_ptr(), n_e, int(n_vertices), keys.data_ptr(), _stream()), 'topo_ring_keys')
+    return keys
+
+
+def topo_corner_keys(faces, n_vertices, status):
+    """psn_topo_corner_keys: faces int64 [F, 3] -> keys int64 [3 F], corner-major: keys[k F + f] = f[k] (V for a skipped face)."""
+    fp = _faces_ptr(faces, 'topo_corner_keys', status)
+    n_f = faces.shape[0]
+    assert status.numel() == 1
+    keys = torch.empty(3 * n_f, dtype=torch.int64, device=faces.device)
+    with _Prof('topo_corner_keys', 48 * n_f):
+        _check(_lib.psn_topo_corner_keys(fp, n_f, int(n_vertices), _eptr(keys, status), _tptr(status, 'status', torch.int32), _stream()),
+               'topo_corner_keys')
+    return keys
+
+
+def topo_runs(sorted_keys, div, n_vertices, want_rem=False, out=None):
+    """psn_topo_runs: ascending keys int64 [n] -> (start int64 [V + 1]: the first position whose key // div is >= x, rem int64 [n] =
+    key % div or None).  ``out``: a tuple (start, rem or None), or None."""
+    n, n_v = sorted_keys.numel(), int(n_vertices)
+    _tptr(sorted_keys, 'sorted_keys', torch.int64)
+    out = (None, None) if out is None else out
+    start = _out(out[0], (n_v + 1,), sorted_keys, 'topo_runs: start', torch.int64)
+    rem = _out(out[1], (n,), sorted_keys, 'topo_runs: rem', torch.int64) if want_rem else None
+    with _Prof('topo_runs', (8 + (8 if want_rem else 0)) * n + 8 * (n_v + 1)):
+        _check(_lib.psn_topo_runs(_eptr(sorted_keys, start), n, int(div), n_v, start.data_ptr(), None if rem is None else _eptr(rem, start),
+                                  _stream()), 'topo_runs')
+    return start, rem
+
+
+TOPO_WEIGHTS = {'area': TOPO_WEIGHT_AREA, 'uniform': TOPO_WEIGHT_UNIFORM}  # noqa: F821
+
+
+def topo_vertex_normals(vertices, faces, corner_start, corner, weight='area', out=None):
+    """psn_topo_vertex_normals -> normals float64 [V, 3]: per vertex the normalised sum over its corner run (in the run's order, from
+    +0.0) of its faces' cross products ('area') or unit normals ('uniform')."""
+    if weight not in TOPO_WEIGHTS:
+        raise ValueError("vertex normals: weight=%r ('area' or 'uniform')" % (weight,))
+    _mesh_ptrs(vertices, faces)
+    n_v, n_f = vertices.shape[0], faces.shape[0]
+    assert corner_start.numel() == n_v + 1 and corner.numel() == 3 * n_f
+    normals = _out(out, (n_v, 3), vertices, 'topo_vertex_normals', torch.float64)
+    _tptr(corner, 'corner', torch.int64)
+    if n_v:
+        with _Prof('topo_vertex_normals', n_v * (16 + 24) + 3 * n_f * (8 + 24 + 72)):
+            _check(_lib.psn_topo_vertex_normals(vertices.data_ptr(), _eptr(faces, vertices), n_f, n_v, _tptr(corner_start, 'corner_start', torch.int64),
+                                                _eptr(corner, vertices), TOPO_WEIGHTS[weight], normals.data_ptr(), _stream()),
+                   'topo_vertex_normals')
+    return normals
+
+
+def topo_smooth_step(x, ring_start, ring, pinned, s, out=None):
+    """psn_topo_smooth_step: x float64 [V, 3] -> out [V, 3] = x + s (ring mean - x) per vertex with a non-empty ring that is not pinned
+    (pinned uint8 [V] or None); the other vertices keep their bits."""
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise RuntimeError('topo_smooth_step: x [V, 3] expected, got %s' % (tuple(x.shape),))
+    _tptr(x, 'x', torch.float64)
+    n_v, n_r = x.shape[0], ring.numel()
+    assert ring_start.numel() == n_v + 1 and (pinned is None or pinned.numel() == n_v)
+    out = _out(out, (n_v, 3), x, 'topo_smooth_step', torch.float64)
+    if n_v:
+        _tptr(ring, 'ring', torch.int64)
+        with _Prof('topo_smooth_step', n_v * (16 + 1 + 48) + n_r * 32):
+            _check(_lib.psn_topo_smooth_step(x.data_ptr(), n_v, _tptr(ring_start, 'ring_start', torch.int64), _eptr(ring, x), n_r,
+                                             None if pinned is None else _tptr(pinned, 'pinned', torch.uint8), float(s), out.data_ptr(),
+                                             _stream()), 'topo_smooth_step')
+    return out
+
+
+def topo_measures(vertices, faces, out=None):
+    """psn_topo_measures -> float64 [2] on the device: area and signed volume (fixed summation order; no atomics)."""
+    _mesh_ptrs(vertices, faces)
+    n_v, n_f = vertices.shape[0], faces.shape[0]
+    out = _out(out, (2,), vertices, 'topo_measures', torch.float64)
+    partial = torch.empty(2 * TOPO_MEASURE_BLOCKS, dtype=torch.float64, device=vertices.device)  # noqa: F821
+    with _Prof('topo_measures', 96 * n_f):
+        _check(_lib.psn_topo_measures(_eptr(vertices, partial), _eptr(faces, partial), n_f, n_v, partial.data_ptr(), out.data_ptr(), _stream()),
+               'topo_measures')
+    return out
+
+
 # --------------------------------------------------------------------------- image evaluation (csrc/imgmetrics.hip)
 IMG_TYPES = {torch.float32: IMG_F32, torch.uint8: IMG_U8}  # noqa: F821
 

@@ -49,7 +49,7 @@ def _inside_open(mesh, points, vote):
     return inside >= (2 if vote else 1), line_open
 
 
-def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False):
+def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False, report=False):
     """Compare the mesh ``pred`` with the ground truth ``gt`` (anything with ``.vertices`` and ``.faces``) -> dict.  Device tensors, or
     ``device='cuda'``, take the device path; otherwise the numpy host path.  ``rng``: np.random.RandomState (default: the global
     np.random).
@@ -73,7 +73,9 @@ def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=10000
       volume_pred, volume_gt                 count / iou_points x the box's volume
       open_pred, open_gt (n_open_*)          the share (count) of the points whose line along axis 2 crosses the mesh an odd number
                                              of times: 0 for a closed surface
-    ``raw``: the samples, their faces, distances and closest triangles, and the IoU points with the two inside masks."""
+    ``raw``: the samples, their faces, distances and closest triangles, and the IoU points with the two inside masks.
+    ``report``: also pred_topology and gt_topology, the connectivity reports of the two meshes (meshtopo.mesh_report: edge classes,
+    Euler characteristic, is_watertight, is_oriented, area, volume), which say WHY a line is not closed; nothing else changes."""
     pred_m, gt_m = _prepare(pred, device, 'pred'), _prepare(gt, device, 'gt')
     pred_pts, pred_face = pred_m.sample_surface(num_samples, rng)
     gt_pts, gt_face = gt_m.sample_surface(num_samples, rng)
@@ -121,4 +123,8 @@ def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=10000
         out['open_pred'], out['open_gt'] = out['n_open_pred'] / n_iou, out['n_open_gt'] / n_iou
         raw.update({'iou_pts': points, 'inside_pred': in_pred, 'inside_gt': in_gt})
     out['raw'] = raw
+    if report:
+        from . import meshtopo
+        for key, m in (('pred_topology', pred_m), ('gt_topology', gt_m)):
+            out[key] = meshtopo.mesh_report((m.vertices, m.faces))
     return out

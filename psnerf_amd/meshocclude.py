@@ -168,15 +168,19 @@ def area_weighted_normals(vertices, faces):
 
 def vertex_occlusion(mesh, vertex_normals=None, table=None, K=64, local=True, bias=None, t_max=float('inf'), bits=False, device=None):
     """occlusion_rows at the vertices of ``mesh`` (a Mesh, a (vertices, faces[, normals]) tuple, a MeshIndex): the rows are the
-    vertices with ``vertex_normals`` (default: the mesh's own, else area-weighted face normals, formed on the host).  A mesh on the
-    device, or ``device='cuda'``, takes the kernel."""
+    vertices with ``vertex_normals`` (default: the mesh's own, else area-weighted face normals: area_weighted_normals on the host path,
+    meshtopo's vertex-normal kernel, which gives the same bits, on the device).  A mesh on the device, or ``device='cuda'``, takes the
+    kernels."""
     if isinstance(mesh, (md.MeshIndex, md._HostMesh)):
         index, vn = mesh, vertex_normals
     else:
         v, f, own = mesh_parts(mesh)
         vn = own if vertex_normals is None else vertex_normals
         index = md._prepare((v, f), device, 'mesh')
-    if vn is None:
+    if vn is None and isinstance(index, md.MeshIndex):      # on the device: the same bits without the copy-back (the index checked the faces)
+        from . import meshtopo
+        vn = meshtopo._device_vertex_normals(index.vertices, index.faces, 'area', check=False)
+    elif vn is None:
         vn = area_weighted_normals(index.vertices, index.faces)
     if isinstance(index, md.MeshIndex):
         vn = torch.as_tensor(to_numpy(vn) if not (torch.is_tensor(vn) and vn.is_cuda) else vn).to(index.vertices.device)

@@ -95,8 +95,8 @@ def get_surface_dist(src_mesh, tgt_mesh, num_samples=10000, rng=None, device=Non
     return f(src_mesh, tgt_mesh, num_samples, rng=rng, device=device)
 
 
-def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False):
+def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False, report=False):
     """Accuracy / completeness, F-score, normal consistency and volume IoU of a mesh against the ground truth -> dict:
     psnerf_amd.mesheval (the reference reports the Chamfer distance only)."""
     from .mesheval import evaluate_mesh as f
-    return f(pred, gt, num_samples, thresholds=thresholds, iou_points=iou_points, rng=rng, device=device, vote=vote)
+    return f(pred, gt, num_samples, thresholds=thresholds, iou_points=iou_points, rng=rng, device=device, vote=vote, report=report)

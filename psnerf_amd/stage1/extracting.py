@@ -26,6 +26,10 @@ Clean-up (not in the reference; opt-in): ``Extractor3D(..., keep_components=K, m
 Simplification (the lineage's ``simplify_nfaces``, which UNISURF and the reference dropped with its native library; opt-in):
   ``Extractor3D(..., simplify_nfaces=N)`` reduces the mesh to at most N faces by quadric vertex clustering (psnerf_amd/meshsimplify.py;
   on the device csrc/meshsimplify.hip), after the clean-up and before the copy-back and the normals.  None (the default) = off.
+Smoothing (not in the reference; opt-in): ``Extractor3D(..., smooth_iterations=N, smooth_lambda=0.5, smooth_mu=-0.53)`` runs N
+  lambda | mu pairs of Taubin's filter over the vertex rings (psnerf_amd/meshsmooth.py; on the device csrc/meshtopo.hip), with the rim
+  and non-manifold seams pinned, after the clean-up and before the simplification, so that the quadrics see the smoothed face planes.
+  None (the default) = off: no launch, tensor or byte of the extraction changes.
 Carving (the reference's ``mask_loader``, extracting.py:120-127, with the project's projection; opt-in): ``Extractor3D(..., carve=hull)``
   with a ``psnerf_amd.hull.VisualHull`` sets the dense grid to -30 where a lattice point lies in no image, or where some image that
   contains it shows background in its dilated mask: after to_dense (and in the upsampling_steps = 0 branch), before ``clip``.  On the
@@ -238,7 +242,7 @@ class Extractor3D(object):
 
     def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0, device=None, resolution0=16,
                  upsampling_steps=3, with_normals=False, padding=0.4, refine_max_faces=10000, keep_components=None,
-                 min_component_faces=0, simplify_nfaces=None, carve=None):
+                 min_component_faces=0, simplify_nfaces=None, carve=None, smooth_iterations=None, smooth_lambda=0.5, smooth_mu=-0.53):
         if device is None and isinstance(model, torch.nn.Module):
             device = next(model.parameters()).device   # (the reference leaves the model where it is; so do we, and follow it)
         self.model = model.to(device) if (model is not None and hasattr(model, 'to')) else model
@@ -256,6 +260,11 @@ class Extractor3D(object):
         self.min_component_faces = min_component_faces
         # simplification (meshsimplify.py): quadric vertex clustering to at most this many faces, after the clean-up; None = off
         self.simplify_nfaces = simplify_nfaces
+        # smoothing (meshsmooth.py): this many lambda | mu pairs (mu = None: plain Laplacian steps) with the rim and non-manifold seams
+        # pinned, after the clean-up and before the simplification; None = off
+        self.smooth_iterations = smooth_iterations
+        self.smooth_lambda = smooth_lambda
+        self.smooth_mu = smooth_mu
         # carving (hull.py): a VisualHull whose dilated masks carve the dense grid before marching cubes; None = off
         self.carve = carve
         self.last_grid = None   # the dense value grid of the last generate_* call (device tensor or numpy array)
@@ -354,6 +363,14 @@ class Extractor3D(object):
                     v, f, _, report = meshclean._device_clean(v, f, None, self.keep_components, self.min_component_faces, 'faces')
                 torch.cuda.synchronize(occ_hat.device)
                 t0 += self._clean_stats(stats_dict, report, time.time() - t1)   # ('time (marching cubes)' stays what it was)
+            if self.smooth_iterations is not None:   # on the device tensors, between the clean-up and the simplification
+                from .. import meshsmooth
+                torch.cuda.synchronize(occ_hat.device)
+                t1 = time.time()
+                with Phase(self.phase_events, 'smooth'):
+                    v, report = meshsmooth._device_smooth(v, f, self.smooth_iterations, self.smooth_lambda, self.smooth_mu)
+                torch.cuda.synchronize(occ_hat.device)
+                t0 += self._smooth_stats(stats_dict, report, time.time() - t1)
             if self.simplify_nfaces is not None:   # likewise on the device tensors, after the clean-up
                 from .. import meshsimplify
                 torch.cuda.synchronize(occ_hat.device)
@@ -376,6 +393,11 @@ class Extractor3D(object):
                 t1 = time.time()
                 vertices, faces, _, report = meshclean.host_clean(vertices, faces, None, self.keep_components, self.min_component_faces)
                 self._clean_stats(stats_dict, report, time.time() - t1)
+            if self.smooth_iterations is not None:
+                from .. import meshsmooth
+                t1 = time.time()
+                vertices, report = meshsmooth.host_smooth(vertices, faces, self.smooth_iterations, self.smooth_lambda, self.smooth_mu)
+                self._smooth_stats(stats_dict, report, time.time() - t1)
             if self.simplify_nfaces is not None:
                 from .. import meshsimplify
                 t1 = time.time()
@@ -399,6 +421,14 @@ class Extractor3D(object):
     def _simplify_stats(stats_dict, report, n_faces_from, seconds):
         stats_dict['n_faces_simplified_from'], stats_dict['simplify_resolution'] = int(n_faces_from), report['resolution']
         stats_dict['time (simplify)'] = seconds
+        return seconds
+
+    @staticmethod
+    def _smooth_stats(stats_dict, report, seconds):
+        stats_dict['smooth_iterations'], stats_dict['n_vertices_pinned'] = report['iterations'], report['n_pinned']
+        stats_dict['smooth_max_displacement'], stats_dict['smooth_volume_ratio'] = report['max_displacement'], (
+            report['volume_after'] / report['volume_before'] if report['volume_before'] != 0.0 else float('nan'))
+        stats_dict['time (smooth)'] = seconds
         return seconds
 
     def estimate_normals(self, vertices, c=None):

@@ -3,13 +3,15 @@
 distance thresholds, normal consistency and volume IoU (psnerf_amd/mesheval.py).
 
     python tools/evaluate_mesh.py PRED GT [--samples 10000] [--thresholds T [T ...]] [--iou-points 100000] [--seed S] [--vote]
-                                  [--device cuda|cpu] [--json]
+                                  [--device cuda|cpu] [--json] [--topology]
 
 Meshes: .obj / .ply (psnerf_amd.meshdist.load_mesh).  --thresholds are distances in mesh units (default: 0.5 %, 1 % and 2 % of the
 diagonal of GT's bounding box).  --iou-points 0 skips the volume block; --vote takes the majority of the three axes' inside tests,
 for scans with holes.  On a GPU (--device cuda, the default where one is present) the meshes are uploaded once and sampling, the
 distance queries and the inside tests run on the device; otherwise the numpy host path.  --seed makes the samples reproducible.
---json prints the result as one JSON object instead of the table."""
+--json prints the result as one JSON object instead of the table.  --topology adds the connectivity report of each mesh
+(psnerf_amd/meshtopo.py: boundary, non-manifold and inconsistently wound edges, Euler characteristic, area, signed volume), which says
+why a line is not closed."""
 import argparse
 import json
 import os
@@ -33,13 +35,15 @@ def main(argv=None):
     parser.add_argument('--vote', action='store_true')
     parser.add_argument('--device', type=str, default=None, choices=('cuda', 'cpu'))
     parser.add_argument('--json', action='store_true')
+    parser.add_argument('--topology', action='store_true')
     args = parser.parse_args(argv)
     from psnerf_amd.meshdist import load_mesh
     from psnerf_amd.mesheval import evaluate_mesh
     device = args.device if args.device is not None else ('cuda' if torch.cuda.is_available() else 'cpu')
     rng = np.random.RandomState(args.seed) if args.seed is not None else None
     result = evaluate_mesh(load_mesh(args.pred), load_mesh(args.gt), num_samples=args.samples, thresholds=args.thresholds,
-                           iou_points=args.iou_points, rng=rng, device='cuda' if device == 'cuda' else None, vote=args.vote)
+                           iou_points=args.iou_points, rng=rng, device='cuda' if device == 'cuda' else None, vote=args.vote,
+                           report=args.topology)
     del result['raw']
     if args.json:
         print(json.dumps(result))
@@ -53,6 +57,10 @@ def main(argv=None):
     if result['iou_points'] > 0:
         print('Volume IoU         %.4f     (volume pred %.6g, gt %.6g; lines not closed: pred %.2f %%, gt %.2f %%)' % (
             result['iou'], result['volume_pred'], result['volume_gt'], 100.0 * result['open_pred'], 100.0 * result['open_gt']))
+    if args.topology:
+        from psnerf_amd.meshtopo import report_line
+        for name in ('pred', 'gt'):
+            print('%-4s topology      %s' % (name, report_line(result[name + '_topology'])))
     return result
 
 
