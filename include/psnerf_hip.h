@@ -879,8 +879,11 @@ int psn_mc_emit(const float* grid, int n, double threshold, const unsigned char*
  *             1 <= F <= PSN_TRI_GRID_MAX_FACES.  Zero-area and duplicated triangles are allowed and take part with their true
  *             distance (segment / point); no NaN arises from them.
  *   PsnTriGrid (host memory): lo / hi = the exact minimum / maximum of the vertices per axis (mesh units); cell = edge of the
- *             cubic cells (> 0, mesh units); n[a] = cells per axis, 1 .. PSN_TRI_GRID_MAX_CELLS_PER_AXIS, with
- *             lo[a] + n[a] cell >= hi[a]; cell (i, j, k) has the linear index (i n[1] + j) n[2] + k.  max_span >= 1: a triangle
+ *             cubic cells (> 0, mesh units); n[a] = cells per axis, 1 .. PSN_TRI_GRID_MAX_CELLS_PER_AXIS, as a rule with
+ *             lo[a] + n[a] cell >= hi[a].  A grid may stop short of hi (a small cell with n at its limit): a coordinate beyond
+ *             lo[a] + n[a] cell belongs to the last cell n[a] - 1, for the builder and for every query alike, so the results
+ *             are the same and only the last cell's lists grow (tests/test_trigrid_gpu.py builds such a grid).  Cell (i, j, k)
+ *             has the linear index (i n[1] + j) n[2] + k.  max_span >= 1: a triangle
  *             whose bounding box overlaps more cells than this is kept in the oversize list instead of the cell lists.
  *   lists     int32 triangle ids.  The order within a cell's list and within the oversize list is not defined (atomics); the
  *             query's result does not depend on it.

@@ -1561,26 +1561,28 @@ def _mesh_ptrs(vertices, faces):
     return _tptr(vertices, 'vertices', torch.float64), _tptr(faces, 'faces', torch.int64)
 
 
-def tri_grid_count(grid, vertices, faces, n_over):
+def tri_grid_count(grid, vertices, faces, n_over, out=None):
     """Index build, first pass (psn_tri_grid_count) -> (cell_count int32 [cells], over_list int32 [F]); n_over (int64 [1] on the
-    device) receives the length of the oversize list."""
+    device) receives the length of the oversize list.  ``out``: the two, preallocated (cell_count is zeroed by the call whatever it
+    held; of over_list only the first n_over entries are written)."""
     vp, fp = _mesh_ptrs(vertices, faces)
     cells = grid.n[0] * grid.n[1] * grid.n[2]
     assert n_over.numel() == 1
-    cell_count = torch.empty(cells, dtype=torch.int32, device=vertices.device)
-    over_list = torch.empty(faces.shape[0], dtype=torch.int32, device=vertices.device)
+    o = out if out is not None else (None, None)
+    cell_count = _out(o[0], (cells,), vertices, 'tri_grid_count: cell_count', torch.int32)
+    over_list = _out(o[1], (faces.shape[0],), vertices, 'tri_grid_count: over_list', torch.int32)
     with _Prof('tri_grid_count', 96 * faces.shape[0]):
         _check(_lib.psn_tri_grid_count(ctypes.byref(grid), vp, fp, faces.shape[0], cell_count.data_ptr(), over_list.data_ptr(),
                                        _tptr(n_over, 'n_over', torch.int64), _stream()), 'tri_grid_count')
     return cell_count, over_list
 
 
-def tri_grid_fill(grid, vertices, faces, cursor, n_entries):
+def tri_grid_fill(grid, vertices, faces, cursor, n_entries, out=None):
     """Index build, second pass (psn_tri_grid_fill): cursor (int32 [cells], the exclusive scan of the counts; advanced in place) ->
-    list int32 [n_entries]."""
+    list int32 [n_entries]; ``out``: the list, preallocated."""
     vp, fp = _mesh_ptrs(vertices, faces)
     assert cursor.numel() == grid.n[0] * grid.n[1] * grid.n[2]
-    lst = torch.empty(int(n_entries), dtype=torch.int32, device=vertices.device)
+    lst = _out(out, (int(n_entries),), vertices, 'tri_grid_fill: list', torch.int32)
     with _Prof('tri_grid_fill', 96 * faces.shape[0]):
         _check(_lib.psn_tri_grid_fill(ctypes.byref(grid), vp, fp, faces.shape[0], _tptr(cursor, 'cursor', torch.int32), int(n_entries),
                                       lst.data_ptr(), _stream()), 'tri_grid_fill')

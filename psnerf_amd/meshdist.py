@@ -328,9 +328,65 @@ def host_sample_surface(vertices, faces, count, rng=None, return_cumulative=Fals
     return (points, face_index, area_cum) if return_cumulative else (points, face_index)
 
 
+def host_tri_grid(vertices, faces, lo, hi, cell, n, max_span):
+    """The triangle grid (PsnTriGrid with its lists) that csrc/meshdist.hip builds, as plain float64 numpy: the definition of the
+    index every device query walks, operation for operation as csrc/trigrid.h (md_cell, md_range) -> dict(c0 int64 [F, 3],
+    c1 int64 [F, 3]: each triangle's first and last cell per axis; span int64 [F]: the cells of that range; over int64: the ids of
+    the oversize triangles (span > max_span), ascending; cell_count int64 [cells]; cell_start int64 [cells + 1]: the exclusive scan
+    of the counts with the total appended; list int64 [n_entries]: per cell the ids of the triangles whose range holds it and that
+    are not oversize, ascending within the cell).  The linear index of cell (x, y, z) is (x n[1] + y) n[2] + z.  ``hi`` is part of
+    the descriptor and of no formula here: a coordinate beyond lo + n cell clamps into the last cell."""
+    v, f, _ = host_mesh(vertices, faces)
+    n = [int(k) for k in n]
+    inv = 1.0 / float(cell)
+    corners = v[f]                                               # [F, 3 corners, 3 axes]
+    c0 = np.zeros((f.shape[0], 3), dtype=np.int64)
+    c1 = np.zeros((f.shape[0], 3), dtype=np.int64)
+    for a in range(3):
+        for out, x in ((c0, corners[:, :, a].min(axis=1)), (c1, corners[:, :, a].max(axis=1))):
+            with np.errstate(invalid='ignore'):
+                t = np.floor((x - float(lo[a])) * inv)
+                t = np.where(t >= 0.0, t, 0.0)                   # (a t that is not >= 0, a NaN among them, goes to 0)
+                out[:, a] = np.where(t > float(n[a] - 1), float(n[a] - 1), t).astype(np.int64)
+    extent = c1 - c0 + 1
+    span = extent[:, 0] * extent[:, 1] * extent[:, 2]
+    is_over = span > int(max_span)
+    cells = n[0] * n[1] * n[2]
+    entries = []                                                 # per listed triangle: its cells, then its id as often
+    for t in np.nonzero(~is_over)[0]:
+        x, y, z = np.meshgrid(*[np.arange(c0[t, a], c1[t, a] + 1) for a in range(3)], indexing='ij')
+        entries.append(np.stack([((x * n[1] + y) * n[2] + z).ravel(), np.full(x.size, t, dtype=np.int64)]))
+    entries = np.concatenate(entries, axis=1) if entries else np.zeros((2, 0), dtype=np.int64)
+    order = np.lexsort((entries[1], entries[0]))                 # by cell, then by id
+    cell_count = np.bincount(entries[0], minlength=cells).astype(np.int64)
+    cell_start = np.concatenate([[0], np.cumsum(cell_count)]).astype(np.int64)
+    return dict(c0=c0, c1=c1, span=span, over=np.nonzero(is_over)[0].astype(np.int64), cell_count=cell_count, cell_start=cell_start,
+                list=entries[1][order])
+
+
 # ------------------------------------------------------------------------------------------------ device path
 MAX_SPAN = 256      # a triangle whose bounding box overlaps more cells than this goes to the oversize list
 CELLS_PER_AXIS = 192   # at most 192^3 = 7.1 M cells: a 28 MB table of list starts
+
+
+def grid_shape(lo, hi, mean_edge, cell=None):
+    """The grid MeshIndex lays over the bounding box [lo, hi] of a mesh with the mean triangle edge ``mean_edge`` -> (cell, n): cell =
+    max(mean edge, largest extent / CELLS_PER_AXIS) unless the caller gives one, 1 where that is not positive (every vertex in one
+    point); n[a] = ceil(extent[a] / cell) within 1 .. CELLS_PER_AXIS.  A given cell so small that an axis would need more than
+    CELLS_PER_AXIS cells leaves a truncated grid, lo[a] + n[a] cell < hi[a]: the last cell of that axis then holds everything
+    beyond it (``grid_truncated``)."""
+    extent = [hi[i] - lo[i] for i in range(3)]
+    if cell is None:
+        cell = max(mean_edge if np.isfinite(mean_edge) else 0.0, max(extent) / CELLS_PER_AXIS)
+    if not cell > 0.0:
+        cell = 1.0   # every vertex in one point
+    n = [int(min(CELLS_PER_AXIS, max(1, np.ceil(extent[i] / cell)))) for i in range(3)]
+    return cell, n
+
+
+def grid_truncated(lo, hi, cell, n):
+    """Does the grid stop short of the bounding box on some axis (lo + n cell < hi, in the grid's own rounding)?"""
+    return any(lo[i] + n[i] * cell < hi[i] for i in range(3))
 
 
 class MeshIndex(object):
@@ -357,12 +413,7 @@ class MeshIndex(object):
             raise ValueError('%s: a face refers to vertex %d of %d' % (name, f_max if f_max >= v.shape[0] else f_min, v.shape[0]))
         if not all(np.isfinite(lo + hi)):
             raise ValueError('%s: a vertex coordinate is not finite' % name)
-        extent = [hi[i] - lo[i] for i in range(3)]
-        if cell is None:
-            cell = max(mean_edge if np.isfinite(mean_edge) else 0.0, max(extent) / CELLS_PER_AXIS)
-        if not cell > 0.0:
-            cell = 1.0   # every vertex in one point
-        n = [int(min(CELLS_PER_AXIS, max(1, np.ceil(extent[i] / cell)))) for i in range(3)]
+        cell, n = grid_shape(lo, hi, mean_edge, cell)
         self.lo, self.hi, self.cell, self.n = lo, hi, cell, n
         self.grid = hip.tri_grid(lo, hi, cell, n, max_span)
         self.build_events = [] if profile else None   # (phase, start event, end event) of the build (tools/bench_chamfer.py)

@@ -34,13 +34,14 @@ def diagonal(v):
     return float(np.linalg.norm(v.max(0) - v.min(0)))
 
 
-def check_against_host(cuda, v, f, queries, what):
-    """MeshIndex.closest_point against host_closest_point; two device runs bit-identical.  Returns the device distances."""
+def check_against_host(cuda, v, f, queries, what, **grid):
+    """MeshIndex.closest_point against host_closest_point; two device runs bit-identical.  Returns the device distances.
+    ``grid``: MeshIndex's ``cell`` / ``max_span``, for a grid other than the default one."""
     diag = diagonal(v)
-    index = md.MeshIndex(v, f, device=cuda)
+    index = md.MeshIndex(v, f, device=cuda, **grid)
     pts = torch.from_numpy(queries).to(cuda)
     closest, dist, tri = index.closest_point(pts)
-    c2, d2, t2 = md.MeshIndex(v, f, device=cuda).closest_point(pts.clone())
+    c2, d2, t2 = md.MeshIndex(v, f, device=cuda, **grid).closest_point(pts.clone())
     assert torch.equal(closest, c2) and torch.equal(dist, d2) and torch.equal(tri, t2), what + ': two runs differ'
     closest, dist, tri = closest.cpu().numpy(), dist.cpu().numpy(), tri.cpu().numpy()
     assert tri.dtype == np.int64 and tri.min() >= 0 and tri.max() < len(f)
