@@ -1304,6 +1304,39 @@ int psn_hull_points(const void* points, int point_type, int64_t n_points, const 
 int psn_hull_grid(float* grid, int n, const double* axis, const double* views, int V, const unsigned char* masks, int H, int W, float value,
                   unsigned long long* count, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Mesh registration, trimmed point-to-plane ICP: the device steps of one iteration that are not a mesh query (csrc/meshalign.hip; the
+ * numpy definition, which is THE definition and states every operation order, is psnerf_amd/meshalign.py: host_transform, host_dist,
+ * host_sums).  float64 arithmetic in the definition's order; no floating-point atomics.  0 <= n <= PSN_ALIGN_MAX_ROWS.
+ *
+ * psn_align_transform: points double [n, 3] -> out [n, 3] = s (R x) + t, row i of R x = (R[i,0] x0 + R[i,1] x1) + R[i,2] x2, then the
+ *   product with s, then the sum with t[i]: bit for bit the definition.  rotation (9, row-major) and translation (3) are HOST tables.
+ * psn_align_dist: dist [n] = sqrt((dx dx + dy dy) + dz dz) with (dx, dy, dz) = Y - P, bit for bit: the distances whose order statistic
+ *   is the trim's max_dist.
+ * psn_align_sums: rows P, Y double [n, 3], tri int64 [n] and the mesh (vertices double [V, 3], faces int64 [F, 3]) whose triangle
+ *   normals are meant; rotation = null, or a HOST table of 9 doubles applied to the unit normal.  Per row: N = normalise(e1 x e2) of
+ *   triangle tri (rotated); the row is skipped as (1) no triangle / not finite when tri is outside 0 .. F - 1, a coordinate of P or Y
+ *   is not finite or the face names a vertex outside 0 .. V - 1, else as (2) zero normal when |e1 x e2| is not > 0, else as (3) beyond
+ *   max_dist unless |Y - P| <= max_dist (closed: a tie is kept).  For the used rows, with J = [P x N (3), N (3), P . N] and
+ *   r = N . (Y - P): sums [PSN_ALIGN_SUMS] = the upper triangle of sum J J^T row by row (28), sum J r (7), sum r r, sum |Y - P|^2;
+ *   counts int64 [PSN_ALIGN_COUNTS] = used, then the three skip counts in the order above; the counts are exact.  Each workgroup
+ *   writes one partial row per PSN_ALIGN_CHUNK rows into ``partial`` (psn_align_workspace 8-byte words; every row on every call) and
+ *   a second, fixed-order step adds them: two calls on the same input give the same bits.
+ * psn_align_workspace: the 8-byte words ``partial`` must hold for n rows; -1 on a bad argument.
+ * Errors: PSN_E_ARG for null pointers, n out of range, V or F < 1, a max_dist that is negative or NaN; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_ALIGN_MAX_ROWS 1073741824
+#define PSN_ALIGN_CHUNK 1024
+#define PSN_ALIGN_SUMS 37
+#define PSN_ALIGN_COUNTS 4
+int64_t psn_align_workspace(int64_t n);
+int psn_align_transform(const double* points, int64_t n, double scale, const double* rotation, const double* translation, double* out,
+                        void* stream);
+int psn_align_dist(const double* P, const double* Y, int64_t n, double* dist, void* stream);
+int psn_align_sums(const double* P, const double* Y, const int64_t* tri, int64_t n, const double* vertices, int64_t n_vertices,
+                   const int64_t* faces, int64_t n_faces, const double* rotation, double max_dist, double* partial, double* sums,
+                   int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

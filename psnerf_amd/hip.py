@@ -2309,3 +2309,75 @@ def hull_grid(grid, axis, views, masks, value=-30.0):
         _check(_lib.psn_hull_grid(gp, n, ap, _hull_views('hull_grid', views, V, masks.device), V, mp, H, W, float(value), count.data_ptr(),
                                   _stream()), 'hull_grid')
     return count
+
+
+# --------------------------------------------------------------------------- mesh registration (csrc/meshalign.hip)
+def _host_table(what, name, values, count):
+    """A host table of ``count`` doubles (a rotation, a translation) as the C ABI takes it."""
+    flat = [float(x) for row in values for x in (row if hasattr(row, '__len__') else (row,))]
+    if len(flat) != count:
+        raise RuntimeError('%s: %s: %d numbers expected, got %d' % (what, name, count, len(flat)))
+    return (ctypes.c_double * count)(*flat)
+
+
+def _align_rows(what, n, dev, **tensors):
+    for name, t in tensors.items():
+        _tptr(t, '%s: %s' % (what, name), torch.float64)
+        if tuple(t.shape) != (n, 3) or t.device != dev:
+            raise RuntimeError('%s: %s [%d, 3] on one device expected, got %s' % (what, name, n, tuple(t.shape)))
+
+
+def align_transform(points, scale, rotation, translation, out=None):
+    """psn_align_transform: points float64 [n, 3] -> scale (rotation x) + translation, float64 [n, 3], bit for bit
+    meshalign.host_transform.  rotation [3, 3] and translation [3] are host values."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError('align_transform: points [n, 3] expected')
+    n = int(points.shape[0])
+    _align_rows('align_transform', n, points.device, points=points)
+    out = _out(out, (n, 3), points, 'align_transform: out', torch.float64)
+    R, t = _host_table('align_transform', 'rotation', rotation, 9), _host_table('align_transform', 'translation', translation, 3)
+    if n:
+        with _Prof('align_transform', 48 * n):
+            _check(_lib.psn_align_transform(points.data_ptr(), n, float(scale), R, t, out.data_ptr(), _stream()), 'align_transform')
+    return out
+
+
+def align_dist(P, Y, out=None):
+    """psn_align_dist: P, Y float64 [n, 3] -> |Y - P| float64 [n], bit for bit meshalign.host_dist."""
+    if not isinstance(P, torch.Tensor) or P.dim() != 2:
+        raise RuntimeError('align_dist: P [n, 3] expected')
+    n = int(P.shape[0])
+    _align_rows('align_dist', n, P.device, P=P, Y=Y)
+    out = _out(out, (n,), P, 'align_dist: out', torch.float64)
+    if n:
+        with _Prof('align_dist', 56 * n):
+            _check(_lib.psn_align_dist(P.data_ptr(), Y.data_ptr(), n, out.data_ptr(), _stream()), 'align_dist')
+    return out
+
+
+def align_sums(P, Y, tri, vertices, faces, max_dist, rotation=None, out=None):
+    """psn_align_sums: rows P, Y float64 [n, 3], tri int64 [n], the mesh whose triangle normals are meant, max_dist (a host value),
+    rotation = None or a host [3, 3] applied to the normals -> (sums float64 [ALIGN_SUMS], counts int64 [ALIGN_COUNTS], partial rows);
+    ``out``: (sums, counts), preallocated."""
+    if not isinstance(P, torch.Tensor) or P.dim() != 2:
+        raise RuntimeError('align_sums: P [n, 3] expected')
+    n, dev = int(P.shape[0]), P.device
+    _align_rows('align_sums', n, dev, P=P, Y=Y)
+    _tptr(tri, 'align_sums: tri', torch.int64)
+    if tuple(tri.shape) != (n,) or tri.device != dev:
+        raise RuntimeError('align_sums: tri [%d] on the rows\' device expected, got %s' % (n, tuple(tri.shape)))
+    vp, fp = _mesh_ptrs(vertices, faces)
+    if vertices.device != dev or faces.device != dev:
+        raise RuntimeError('align_sums: the mesh must be on the rows\' device')
+    words = int(_lib.psn_align_workspace(n))
+    if words < 0:
+        raise RuntimeError('psn_align_workspace(%d) refused' % n)
+    partial = torch.empty(words, dtype=torch.float64, device=dev)
+    o = out if out is not None else (None, None)
+    sums = _out(o[0], (ALIGN_SUMS,), P, 'align_sums: sums', torch.float64)  # noqa: F821
+    counts = _out(o[1], (ALIGN_COUNTS,), P, 'align_sums: counts', torch.int64)  # noqa: F821
+    R = None if rotation is None else _host_table('align_sums', 'rotation', rotation, 9)
+    with _Prof('align_sums', 64 * n):
+        _check(_lib.psn_align_sums(_eptr(P, partial), _eptr(Y, partial), _eptr(tri, partial), n, vp, vertices.shape[0], fp, faces.shape[0], R,
+                                   float(max_dist), partial.data_ptr(), sums.data_ptr(), counts.data_ptr(), _stream()), 'align_sums')
+    return sums, counts, partial

@@ -49,7 +49,15 @@ def _inside_open(mesh, points, vote):
     return inside >= (2 if vote else 1), line_open
 
 
-def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False, report=False):
+def _rng_copy(rng):
+    """A RandomState in the state of ``rng`` (None: of the global np.random), which itself is left untouched."""
+    copy = np.random.RandomState()
+    copy.set_state((np.random if rng is None else rng).get_state())
+    return copy
+
+
+def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False, report=False,
+                  align=None, align_options=None):
     """Compare the mesh ``pred`` with the ground truth ``gt`` (anything with ``.vertices`` and ``.faces``) -> dict.  Device tensors, or
     ``device='cuda'``, take the device path; otherwise the numpy host path.  ``rng``: np.random.RandomState (default: the global
     np.random).
@@ -75,8 +83,21 @@ def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=10000
                                              of times: 0 for a closed surface
     ``raw``: the samples, their faces, distances and closest triangles, and the IoU points with the two inside masks.
     ``report``: also pred_topology and gt_topology, the connectivity reports of the two meshes (meshtopo.mesh_report: edge classes,
-    Euler characteristic, is_watertight, is_oriented, area, volume), which say WHY a line is not closed; nothing else changes."""
+    Euler characteristic, is_watertight, is_oriented, area, volume), which say WHY a line is not closed; nothing else changes.
+    ``align``: None (default: the meshes are taken to be in one frame, and every output is what it was without the argument), or
+    'rigid' / 'similarity': ``pred`` is first registered to ``gt`` (meshalign.align_mesh on the same path, with its defaults unless
+    ``align_options``, a dict of its keyword arguments, says otherwise) and everything above is computed for the moved prediction;
+    ``alignment`` then holds the registration's result without its history (matrix, scale, rotation, translation, rms, used,
+    iterations, converged, mode).  The registration draws its samples from a COPY of the rng's state, so the evaluation's own draws
+    are those of the call without ``align``."""
     pred_m, gt_m = _prepare(pred, device, 'pred'), _prepare(gt, device, 'gt')
+    alignment = None
+    if align is not None:
+        from . import meshalign
+        if align not in ('rigid', 'similarity'):
+            raise ValueError('evaluate_mesh: align=%r (None, \'rigid\' or \'similarity\')' % (align,))
+        alignment = meshalign.align_mesh(pred_m, gt_m, mode=align, rng=_rng_copy(rng), **dict(align_options or {}))
+        pred_m = meshalign.moved(pred_m, alignment['matrix'])
     pred_pts, pred_face = pred_m.sample_surface(num_samples, rng)
     gt_pts, gt_face = gt_m.sample_surface(num_samples, rng)
     _, pred_gt_dist, pred_gt_tri = gt_m.closest_point(pred_pts)
@@ -123,6 +144,8 @@ def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=10000
         out['open_pred'], out['open_gt'] = out['n_open_pred'] / n_iou, out['n_open_gt'] / n_iou
         raw.update({'iou_pts': points, 'inside_pred': in_pred, 'inside_gt': in_gt})
     out['raw'] = raw
+    if alignment is not None:
+        out['alignment'] = {k: v for k, v in alignment.items() if k != 'history'}
     if report:
         from . import meshtopo
         for key, m in (('pred_topology', pred_m), ('gt_topology', gt_m)):

@@ -95,8 +95,11 @@ def get_surface_dist(src_mesh, tgt_mesh, num_samples=10000, rng=None, device=Non
     return f(src_mesh, tgt_mesh, num_samples, rng=rng, device=device)
 
 
-def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False, report=False):
+def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False, report=False,
+                  align=None, align_options=None):
     """Accuracy / completeness, F-score, normal consistency and volume IoU of a mesh against the ground truth -> dict:
-    psnerf_amd.mesheval (the reference reports the Chamfer distance only)."""
+    psnerf_amd.mesheval (the reference reports the Chamfer distance only).  ``align``: 'rigid' or 'similarity' registers ``pred`` to
+    ``gt`` first (psnerf_amd.meshalign)."""
     from .mesheval import evaluate_mesh as f
-    return f(pred, gt, num_samples, thresholds=thresholds, iou_points=iou_points, rng=rng, device=device, vote=vote, report=report)
+    return f(pred, gt, num_samples, thresholds=thresholds, iou_points=iou_points, rng=rng, device=device, vote=vote, report=report, align=align,
+             align_options=align_options)

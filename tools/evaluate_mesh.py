@@ -3,7 +3,7 @@
 distance thresholds, normal consistency and volume IoU (psnerf_amd/mesheval.py).
 
     python tools/evaluate_mesh.py PRED GT [--samples 10000] [--thresholds T [T ...]] [--iou-points 100000] [--seed S] [--vote]
-                                  [--device cuda|cpu] [--json] [--topology]
+                                  [--device cuda|cpu] [--json] [--topology] [--align rigid|similarity]
 
 Meshes: .obj / .ply (psnerf_amd.meshdist.load_mesh).  --thresholds are distances in mesh units (default: 0.5 %, 1 % and 2 % of the
 diagonal of GT's bounding box).  --iou-points 0 skips the volume block; --vote takes the majority of the three axes' inside tests,
@@ -11,7 +11,8 @@ for scans with holes.  On a GPU (--device cuda, the default where one is present
 distance queries and the inside tests run on the device; otherwise the numpy host path.  --seed makes the samples reproducible.
 --json prints the result as one JSON object instead of the table.  --topology adds the connectivity report of each mesh
 (psnerf_amd/meshtopo.py: boundary, non-manifold and inconsistently wound edges, Euler characteristic, area, signed volume), which says
-why a line is not closed."""
+why a line is not closed.  --align MODE (off when absent) first registers PRED to GT by trimmed point-to-plane ICP
+(psnerf_amd/meshalign.py), for a prediction in another frame or unit, and adds the transform to the output."""
 import argparse
 import json
 import os
@@ -36,6 +37,7 @@ def main(argv=None):
     parser.add_argument('--device', type=str, default=None, choices=('cuda', 'cpu'))
     parser.add_argument('--json', action='store_true')
     parser.add_argument('--topology', action='store_true')
+    parser.add_argument('--align', type=str, default=None, choices=('rigid', 'similarity'))
     args = parser.parse_args(argv)
     from psnerf_amd.meshdist import load_mesh
     from psnerf_amd.mesheval import evaluate_mesh
@@ -43,11 +45,17 @@ def main(argv=None):
     rng = np.random.RandomState(args.seed) if args.seed is not None else None
     result = evaluate_mesh(load_mesh(args.pred), load_mesh(args.gt), num_samples=args.samples, thresholds=args.thresholds,
                            iou_points=args.iou_points, rng=rng, device='cuda' if device == 'cuda' else None, vote=args.vote,
-                           report=args.topology)
+                           report=args.topology, align=args.align)
     del result['raw']
+    if 'alignment' in result:
+        result['alignment'] = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in result['alignment'].items()}
     if args.json:
         print(json.dumps(result))
         return result
+    if 'alignment' in result:
+        a = result['alignment']
+        print('Aligned (%s)%s scale %.9g, rms %.6g over %d rows, %d iterations, %s' % (a['mode'], ' ' * (9 - len(a['mode'])), a['scale'], a['rms'],
+              a['used'], a['iterations'], 'converged' if a['converged'] else 'NOT converged'))
     print('Chamfer distance   %.6g   (accuracy %.6g, completeness %.6g)' % (result['chamfer'], result['accuracy'], result['completeness']))
     print('squared            %.6g   (accuracy %.6g, completeness %.6g)' % (result['chamfer2'], result['accuracy2'], result['completeness2']))
     for t in result['thresholds']:
