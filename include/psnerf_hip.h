@@ -980,6 +980,51 @@ int psn_occlusion_rows(const PsnMeshIndex* index, const double* points, const do
                        long long* n_tests, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The views projected onto surface rows, over the same index (csrc/meshproject.hip; the float64 numpy definition is
+ * psnerf_amd/meshproject.py:host_project_rows): per row (a point and a normal) which of V cameras see it, and the weighted sums of
+ * what their images show there.  The segment to a camera is formed in registers and walked by psn_ray_cast's own any-hit walk
+ * (csrc/meshray.h), so no ray and no per-(row, view) value is ever written to memory.  The reference has no such query.
+ * index: the PsnMeshIndex (above).
+ *
+ * psn_project_rows: points / normals float64 [R, 3]; views float64 [V, 16], 1 <= V <= PSN_PROJECT_MAX_VIEWS, one row per view:
+ *   R row-major (9, camera to world), o (3), K00, K02, K12, 0 (the table of psn_hull_points); images [V, H, W, C], PSN_IMG_U8 (a byte
+ *   u is the double u / 255.0) or PSN_IMG_F32 (widened exactly), 1 <= H, W <= PSN_PROJECT_MAX_EXTENT, 1 <= C <=
+ *   PSN_PROJECT_MAX_CHANNELS -- or images null and C = 0: visibility only, sum / sum_sq / best_value are not touched and may be
+ *   null; masks uint8 [V, H, W] (non-zero = set) or null.
+ *   A row whose point or normal has a non-finite component, or whose normal is zero, sees nothing: n_seen = 0, best_view = -1, every
+ *   sum, weight and word 0.  Otherwise the views are taken in ascending order, and view v SEES the row iff
+ *     1. d = p - o, x_c = (d0 R[0, c] + d1 R[1, c]) + d2 R[2, c], x_2 > 0, u = K02 + K00 (x_0 / x_2), v = K12 + K00 (x_1 / x_2);
+ *     2. 0 <= u <= W - 1 and 0 <= v <= H - 1 (a NaN is outside); x0 = floor u, x1 = min(x0 + 1, W - 1), fx = u - x0, likewise y;
+ *     3. e = o - p, c = ((n0 e0 + n1 e1) + n2 e2) / sqrt((e0 e0 + e1 e1) + e2 e2) > cos_min;
+ *     4. with masks, the four pixels (y0 | y1, x0 | x1) of view v are all non-zero;
+ *     5. psn_ray_cast in mode PSN_RAY_ANY_HIT with t in [0, 1] reports no hit for (q, o - q), q = p + bias n (the products, then
+ *        the sums).
+ *   Its sample per channel is val = (1 - fy)((1 - fx) t00 + fx t10) + fy ((1 - fx) t01 + fx t11); with
+ *   PSN_PROJECT_FRAME_CAMERA_NORMAL (C = 3) val becomes w_i = (R[i, 0] val0 + R[i, 1] (-val1)) + R[i, 2] (-val2).  Its weight is
+ *   w = c (PSN_PROJECT_WEIGHT_COSINE) or 1 (PSN_PROJECT_WEIGHT_UNIFORM).  In view order: sum[ch] += w val[ch];
+ *   sum_sq[ch] += w (val[ch] val[ch]); weight += w; n_seen += 1; best_view = the seeing view of the largest w (a tie: the lowest),
+ *   best_value = its val; bit v % 32 of word v / 32 is set.
+ *   Outputs: sum, sum_sq, best_value float64 [R, C]; weight float64 [R]; n_seen, best_view int32 [R]; words int32 [R, (V + 31) / 32]
+ *   or null.  All arithmetic is float64 without contraction in the order written and a row's views accumulate in one thread, so
+ *   every output is bitwise reproducible and equal to the definition's.  n_tests: null, or an int64 counter to which the number of
+ *   ray-triangle tests is added.  R = 0 is a no-op.
+ * Errors: PSN_E_ARG for null pointers, a bad PsnMeshIndex, R, V, H, W or C out of range, C = 0 with images or C > 0 without, an
+ *   unknown image type, weight mode or frame mode, PSN_PROJECT_FRAME_CAMERA_NORMAL with C != 3, a bias or cos_min that is not
+ *   finite; PSN_E_LAUNCH.
+ * ---------------------------------------------------------------------- */
+#define PSN_PROJECT_MAX_VIEWS 256
+#define PSN_PROJECT_MAX_EXTENT 32768
+#define PSN_PROJECT_MAX_CHANNELS 4
+#define PSN_PROJECT_WEIGHT_COSINE 0
+#define PSN_PROJECT_WEIGHT_UNIFORM 1
+#define PSN_PROJECT_FRAME_RAW 0
+#define PSN_PROJECT_FRAME_CAMERA_NORMAL 1
+int psn_project_rows(const PsnMeshIndex* index, const double* points, const double* normals, int64_t n_rows, const double* views,
+                     int n_views, const void* images, int image_type, int H, int W, int C, const unsigned char* masks, double bias,
+                     double cos_min, int weight_mode, int frame_mode, double* sum, double* sum_sq, double* weight, int* n_seen,
+                     int* best_view, double* best_value, int* words, long long* n_tests, void* stream);
+
+/* ------------------------------------------------------------------------
  * Crossing counts of an axis-parallel line with the mesh, over the same index (csrc/meshinside.hip; the float64 numpy definition is
  * psnerf_amd/meshdist.py:host_crossings): the inside test behind volume IoU.  The reference has no such query.  index: the
  * PsnMeshIndex (above).

@@ -1684,6 +1684,62 @@ def occlusion_rows(index, points, normals, table, local=True, bias=0.0, t_max=fl
     return hits, visible, ao, bent, words
 
 
+# --------------------------------------------------------------------------- the views on surface rows (csrc/meshproject.hip)
+def project_rows(index, points, normals, views, images, hw=None, masks=None, bias=0.0, cos_min=0.0, uniform=False, camera_normal=False,
+                 bits=False, n_tests=None, out=None):
+    """psn_project_rows: points / normals float64 [R, 3], views float64 [V, 16] (hull._views), images uint8 or float32 [V, H, W, C] (or
+    None with ``hw`` = (H, W): visibility only, C = 0), masks uint8 [V, H, W] or None -> (sum [R, C], sum_sq [R, C], weight [R], n_seen
+    int32 [R], best_view int32 [R], best_value [R, C], words int32 [R, ceil(V / 32)] or None); the three [R, C] outputs are None with
+    C = 0.  out: the seven outputs to write into (None where none is made); n_tests (int64 [1]) accumulates the ray-triangle tests."""
+    for name, x in (('points', points), ('normals', normals)):
+        _tptr(x, 'project_rows: %s' % name, torch.float64)
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise RuntimeError('project_rows: %s [R, 3] expected, got %s' % (name, tuple(x.shape)))
+    if points.shape != normals.shape or normals.device != points.device:
+        raise RuntimeError('project_rows: %d points and %d normals (on one device)' % (points.shape[0], normals.shape[0]))
+    _tptr(views, 'project_rows: views', torch.float64)
+    if views.dim() != 2 or views.shape[1] != 16 or views.device != points.device:
+        raise RuntimeError('project_rows: views [V, 16] on the rows\' device expected, got %s' % (tuple(views.shape),))
+    r, v = int(points.shape[0]), int(views.shape[0])
+    if images is None:
+        if hw is None:
+            raise RuntimeError('project_rows: without images, hw = (H, W) is required')
+        H, W, C, ip, ty = int(hw[0]), int(hw[1]), 0, None, IMG_F32  # noqa: F821
+    else:
+        ip = _tptr(images, 'project_rows: images', tuple(IMG_TYPES))
+        if images.dim() != 4 or images.shape[0] != v or images.device != points.device or images.numel() == 0:
+            raise RuntimeError('project_rows: images [%d, H, W, C] on the rows\' device expected, got %s' % (v, tuple(images.shape)))
+        H, W, C, ty = int(images.shape[1]), int(images.shape[2]), int(images.shape[3]), IMG_TYPES[images.dtype]
+        if hw is not None and (int(hw[0]), int(hw[1])) != (H, W):
+            raise RuntimeError('project_rows: hw = %r, the images are %d x %d' % (tuple(hw), H, W))
+    mp = None
+    if masks is not None:
+        mp = _tptr(masks, 'project_rows: masks', torch.uint8)
+        if tuple(masks.shape) != (v, H, W) or masks.device != points.device:
+            raise RuntimeError('project_rows: masks [%d, %d, %d] on the rows\' device expected, got %s' % (v, H, W, tuple(masks.shape)))
+    n_words = (v + 31) // 32
+    given = (None,) * 7 if out is None else out
+    if C == 0 and any(given[i] is not None for i in (0, 1, 5)):
+        raise RuntimeError('project_rows: out holds sum / sum_sq / best_value buffers, but there are no images')
+    total = _out(given[0], (r, C), points, 'project_rows: sum', torch.float64) if C else None
+    total_sq = _out(given[1], (r, C), points, 'project_rows: sum_sq', torch.float64) if C else None
+    weight = _out(given[2], (r,), points, 'project_rows: weight', torch.float64)
+    n_seen = _out(given[3], (r,), points, 'project_rows: n_seen', torch.int32)
+    best_view = _out(given[4], (r,), points, 'project_rows: best_view', torch.int32)
+    best_value = _out(given[5], (r, C), points, 'project_rows: best_value', torch.float64) if C else None
+    words = _out(given[6], (r, n_words), points, 'project_rows: words', torch.int32) if bits else None
+    opt = lambda t: None if t is None else _eptr(t, views)
+    with _Prof('project_rows', r * v):
+        _check(_lib.psn_project_rows(ctypes.byref(index), _eptr(points, views), _eptr(normals, views), r, _eptr(views, points), v, ip, ty, H, W, C,
+                                     mp, float(bias), float(cos_min),
+                                     PROJECT_WEIGHT_UNIFORM if uniform else PROJECT_WEIGHT_COSINE,  # noqa: F821
+                                     PROJECT_FRAME_CAMERA_NORMAL if camera_normal else PROJECT_FRAME_RAW,  # noqa: F821
+                                     opt(total), opt(total_sq), _eptr(weight, views), _eptr(n_seen, views), _eptr(best_view, views),
+                                     opt(best_value), opt(words),
+                                     None if n_tests is None else _tptr(n_tests, 'n_tests', torch.int64), _stream()), 'project_rows')
+    return total, total_sq, weight, n_seen, best_view, best_value, words
+
+
 # --------------------------------------------------------------------------- crossing counts (csrc/meshinside.hip)
 def mesh_crossings(index, points, axis=2, order=None, want_below=True, want_on=True, n_tests=None):
     """psn_mesh_crossings: points float64 [Q, 3] -> (above int32 [Q], below int32 [Q] or None, on int32 [Q] or None): the triangles of

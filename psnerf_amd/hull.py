@@ -143,8 +143,9 @@ def _host_points(points):
     return p.astype(np.float64)
 
 
-def _project(p, view):
-    """The definition's arithmetic for float64 points [Q, 3] and one row of the view table -> (floor(u + 0.5), floor(v + 0.5), front)."""
+def _project_uv(p, view):
+    """The definition's arithmetic for float64 points [Q, 3] and one row of the view table, up to the image-plane position
+    -> (u, v, front).  The one statement of the projection: ``_project`` below and meshproject.host_project_rows both go through it."""
     R, o, fx, cx, cy = view[0:9].reshape(3, 3), view[9:12], view[12], view[13], view[14]
     with np.errstate(all='ignore'):
         d0, d1, d2 = p[:, 0] - o[0], p[:, 1] - o[1], p[:, 2] - o[2]
@@ -153,7 +154,14 @@ def _project(p, view):
         x2 = (d0 * R[0, 2] + d1 * R[1, 2]) + d2 * R[2, 2]
         u = cx + fx * (x0 / x2)
         v = cy + fx * (x1 / x2)
-        return np.floor(u + 0.5), np.floor(v + 0.5), x2 > 0
+        return u, v, x2 > 0
+
+
+def _project(p, view):
+    """_project_uv rounded to the nearest pixel centre -> (floor(u + 0.5), floor(v + 0.5), front)."""
+    u, v, front = _project_uv(p, view)
+    with np.errstate(all='ignore'):
+        return np.floor(u + 0.5), np.floor(v + 0.5), front
 
 
 def host_project(points, camera_mat, world_mat, hw=None, scale_mat=None):
@@ -320,21 +328,8 @@ class VisualHull(object):
     def from_params(cls, params_json, mask_dir, views=None, footprint=None, device=None):
         """The dataset's params.json ('K', 'pose_c2w' in OpenGL axes, 'n_view'), read as tools/render_mesh.py reads it, and
         mask_dir/view_VV.png (imgmetrics.load_image).  ``views``: view numbers from 1 (default: all)."""
-        import os
-        from .imgmetrics import load_image
-        with open(params_json) as f:
-            para = json.load(f)
-        K = np.array(para['K']).astype(np.float32)
-        pose = np.array(para['pose_c2w']).astype(np.float32).copy()
-        pose[:, :3, 1:3] *= -1.0                                          # OpenGL -> OpenCV, stage1/dataloading/dataset.py:56
-        views = list(views) if views else list(range(1, int(para.get('n_view', len(pose))) + 1))
-        masks = []
-        for vi in views:
-            if not 1 <= vi <= len(pose):
-                raise ValueError('VisualHull.from_params: view %d of %d' % (vi, len(pose)))
-            m = load_image(os.path.join(mask_dir, 'view_%02d.png' % vi))
-            masks.append((m.reshape(m.shape[0], m.shape[1], -1)[..., 0]) != 0)
-        return cls(_place(np.stack(masks), device), K, pose[[vi - 1 for vi in views]], footprint)
+        K, poses, views, _ = cameras_from_params(params_json, views, 'VisualHull.from_params')
+        return cls(_place(masks_from_dir(mask_dir, views), device), K, poses, footprint)
 
     def _on(self, device):
         """The dilated masks where ``device`` is (moved once and kept when that is not where they were given)."""
@@ -379,6 +374,34 @@ class VisualHull(object):
             return Mesh(v.cpu().numpy(), f.cpu().numpy())
         v, f = host_marching_cubes(grid, 0.0)
         return Mesh(to_world(v, grid.shape[0], box_size), f)
+
+
+def cameras_from_params(params_json, views=None, what='cameras_from_params'):
+    """The dataset's params.json ('K', 'pose_c2w' in OpenGL axes, 'n_view', optionally 'imhw'), read as tools/render_mesh.py reads it
+    -> (K float32 [3, 3], world_mats float32 [n, 4, 4] in OpenCV axes, the view numbers from 1, (H, W) or None).  ``views``: view
+    numbers from 1 (default: all)."""
+    with open(params_json) as f:
+        para = json.load(f)
+    K = np.array(para['K']).astype(np.float32)
+    pose = np.array(para['pose_c2w']).astype(np.float32).copy()
+    pose[:, :3, 1:3] *= -1.0                                          # OpenGL -> OpenCV, stage1/dataloading/dataset.py:56
+    views = list(views) if views else list(range(1, int(para.get('n_view', len(pose))) + 1))
+    for vi in views:
+        if not 1 <= vi <= len(pose):
+            raise ValueError('%s: view %d of %d' % (what, vi, len(pose)))
+    hw = tuple(int(x) for x in para['imhw']) if 'imhw' in para else None
+    return K, pose[[vi - 1 for vi in views]], views, hw
+
+
+def masks_from_dir(mask_dir, views):
+    """mask_dir/view_VV.png (imgmetrics.load_image) of the view numbers ``views`` -> bool [n, H, W]."""
+    import os
+    from .imgmetrics import load_image
+    masks = []
+    for vi in views:
+        m = load_image(os.path.join(mask_dir, 'view_%02d.png' % vi))
+        masks.append((m.reshape(m.shape[0], m.shape[1], -1)[..., 0]) != 0)
+    return np.stack(masks)
 
 
 def _place(masks, device):

@@ -35,6 +35,9 @@ Bytes (``to_img``, the rule of imgmetrics.to_img in float32): clip to [0, 1], x 
 Baked visibility (``bake_occlusion``, or ``bake_materials(..., occlusion=K)``): the rows' points and normals go through
   meshocclude.occlusion_rows (K cosine-weighted directions about the row's normal, any-hit against the mesh itself) and the ambient
   occlusion and the bent normal of each row are scattered like any other map; a row that casts nothing (a zero normal) bakes ``fill``.
+Baked photographs (``bake_views``): the rows' points and normals go through meshproject.project_rows (which views see the row, and the
+  weighted sums of what their images show there); the mean, the best view's sample, the number of seeing views and the weighted spread
+  of each row are scattered like any other map; a row no view sees bakes ``fill``.
 """
 import math
 import os
@@ -439,13 +442,82 @@ def bake_occlusion(mesh, size=2048, atlas=None, K=64, bias=None, t_max=float('in
     return out
 
 
+# ------------------------------------------------------------------------------------------------ the photographs on the atlas
+class _Projector(object):
+    """The views of a bake: the index (a MeshIndex for device tensors, the host twin for numpy arrays), the images, masks and bias, made
+    (and, on the device, uploaded) once; ``bake`` turns one chunk of rows into texels of 'photo', 'photo_best', 'seen' and 'spread'."""
+
+    def __init__(self, v, f, images, camera_mats, world_mats, masks, options):
+        from . import meshdist as md, meshocclude as mo
+        self.index = md._prepare((v, f), None, 'mesh')
+        if isinstance(self.index, md.MeshIndex):
+            dev = self.index.vertices.device
+            place = lambda x: x if x is None or (torch.is_tensor(x) and x.is_cuda) else torch.from_numpy(np.array(to_numpy(x))).to(dev)
+            images, masks = place(images), place(masks)
+        else:
+            images, masks = to_numpy(images), to_numpy(masks)
+        self.images, self.masks, self.cameras = images, masks, (camera_mats, world_mats)
+        self.options = dict(options)
+        if self.options.get('bias') is None:
+            self.options['bias'] = mo.default_bias(self.index)
+
+    def bake(self, atlas, points, normals, f0, f1, out, fill):
+        from . import meshproject as mp
+        with Phase(PHASE_EVENTS, 'project'):
+            res = mp.project_rows(self.index, points, normals, self.images, self.cameras[0], self.cameras[1], masks=self.masks, **self.options)
+            maps = {'photo': mp.mean(res), 'photo_best': res.best_value, 'seen': res.n_seen[:, None], 'spread': mp.spread(res)}
+            unseen = (res.n_seen == 0)[:, None]
+            if torch.is_tensor(res.weight):
+                rows = {k: torch.where(unseen, float(fill), m.float()) for k, m in maps.items()}
+            else:
+                rows = {k: np.where(unseen, np.float32(fill), m.astype(np.float32)) for k, m in maps.items()}
+        with Phase(PHASE_EVENTS, 'scatter'):
+            for name, r in rows.items():
+                out[name] = atlas_scatter(atlas, r.contiguous() if torch.is_tensor(r) else np.ascontiguousarray(r), f0, f1, out.get(name),
+                                          fill if name not in out else None)
+
+
+def bake_views(mesh, images, camera_mats, world_mats, size=2048, atlas=None, masks=None, chunk_faces=None, fill=0.0, device=None, **options):
+    """The photographs on the atlas of ``mesh``: per texel row, meshproject.project_rows over ``images`` [V, H, W, C] (uint8 or float32)
+    of the cameras (camera_mats, world_mats) -> {'atlas': Atlas, 'photo': float32 [T, T, C] = the weighted mean of what the seeing views
+    show, 'photo_best': [T, T, C] = the view of the largest weight alone, 'seen': [T, T, 1] = the number of seeing views as a float,
+    'spread': [T, T, C] = the weighted standard deviation over the seeing views (photo-consistency)}; texels no face owns, and rows no
+    view sees, hold ``fill``.  ``options``: project_rows' bias, cos_min, weight and frame.  Row normals are the ones atlas_points
+    returns.  Chunk of faces by chunk of faces as bake_occlusion; a bake in chunks equals a bake in one call bit for bit.  One code
+    path: device tensors (or ``device='cuda'``: the mesh is moved there) run the kernels and return device tensors; a numpy mesh
+    runs the definition and returns numpy arrays."""
+    if images is None:
+        raise ValueError('bake_views: images are required (visibility alone: meshproject.face_visibility)')
+    v, f, vn = mesh_parts(mesh)
+    _no_cpu_tensor(v, 'bake_views')
+    if on_device(v, device):
+        v, f, vn = device_mesh(v, f, vn, device, prefix='atlas', widen_normals=True)
+    else:
+        v, f, vn = host_mesh(to_numpy(v), to_numpy(f), to_numpy(vn), prefix='atlas', widen_normals=True)
+    atlas = Atlas(size, f.shape[0]) if atlas is None else atlas
+    if atlas.F != f.shape[0]:
+        raise ValueError('bake_views: %d faces, the atlas was laid out for %d' % (f.shape[0], atlas.F))
+    step = max(1, CHUNK_ROWS // atlas.K) if chunk_faces is None else int(chunk_faces)
+    if step < 1:
+        raise ValueError('bake_views: chunk_faces = %d' % step)
+    projector = _Projector(v, f, images, camera_mats, world_mats, masks, options)      # (building the index also checks the faces)
+    out = {'atlas': atlas}
+    for f0 in range(0, atlas.F, step):
+        f1 = min(f0 + step, atlas.F)
+        with Phase(PHASE_EVENTS, 'points'):
+            p, _, nrm = atlas_points(atlas, v, f, vn, f0, f1)
+        projector.bake(atlas, p, nrm, f0, f1, out, fill)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ the writer
 def export_textured(path, mesh, baked, gamma=1.0):
     """Write the textured asset: ``name.obj`` (v, vt, f v/vt; vn and f v/vt/vn when the mesh has vertex normals), ``name.mtl``
     (map_Kd name_albedo.png; norm name_normal.png), the PNGs (bytes by ``to_img``; the albedo raised to 1 / gamma first, the normals
     stored as n / 2 + 0.5 -- OBJECT space, not tangent space) and ``name_specular.npy`` (float32 [T, T, C]: the SG weights have more
     than three channels and are not an image); with 'occlusion' / 'bent' (bake_occlusion) also ``name_ao.png`` (one channel, map_Ka) and
-    ``name_bent.png`` (stored as n / 2 + 0.5 like the normals).  ``path``: name.obj, or the name without an extension; ``baked``: bake_materials'
+    ``name_bent.png`` (stored as n / 2 + 0.5 like the normals); with 'photo' and 'seen' (bake_views) also ``name_photo.png`` (C = 1, 3 or 4)
+    and ``name_seen.png`` (one channel, the number of seeing views as a byte, 255 at most), named in one comment line.  ``path``: name.obj, or the name without an extension; ``baked``: bake_materials'
     result (only the maps it holds are written) -> {what: file path}."""
     from PIL import Image
     base = path[:-4] if path.lower().endswith('.obj') else path
@@ -480,6 +552,14 @@ def export_textured(path, mesh, baked, gamma=1.0):
         files['bent'] = os.path.join(folder, name + '_bent.png')
         Image.fromarray(to_img(to_numpy(baked['bent']).astype(np.float32) / np.float32(2.0) + np.float32(0.5))).save(files['bent'])
         mtl.append('# bent normals: %s_bent.png, object space, stored as n / 2 + 0.5' % name)
+    if 'photo' in baked and 'seen' in baked:
+        photo = to_img(to_numpy(baked['photo']).astype(np.float32))
+        files['photo'] = os.path.join(folder, name + '_photo.png')
+        Image.fromarray(photo[:, :, 0] if photo.shape[2] == 1 else photo).save(files['photo'])
+        files['seen'] = os.path.join(folder, name + '_seen.png')
+        Image.fromarray(np.clip(to_numpy(baked['seen']).astype(np.float32)[:, :, 0], 0.0, 255.0).astype(np.uint8)).save(files['seen'])
+        mtl.append('# the photographs on the atlas: %s_photo.png (the mean over the seeing views), %s_seen.png (their number, 255 at most)'
+                   % (name, name))
     with open(files['mtl'], 'w') as out:
         out.write('\n'.join(mtl) + '\n')
     uv = atlas_uv(atlas).reshape(-1, 2)

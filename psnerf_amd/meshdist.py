@@ -528,6 +528,31 @@ class MeshIndex(object):
         table = table.to(device=points.device, dtype=torch.float64).contiguous()
         return hip.occlusion_rows(self.index, points, normals, table, local=local, bias=bias, t_max=t_max, bits=bits, n_tests=n_tests, out=out)
 
+    def project_rows(self, points, normals, images, views, hw=None, masks=None, bias=0.0, cos_min=0.0, weight='cosine', frame='raw',
+                     bits=False, n_tests=None, out=None):
+        """points / normals float64 [R, 3] on the index's device; images uint8 or float32 [V, H, W, C] (or None with ``hw`` = (H, W):
+        visibility only); views float64 [V, 16] (hull._views); masks [V, H, W] or None -- device tensors, or numpy arrays that are
+        uploaded -> meshproject.Projection of device tensors: meshproject.host_project_rows on the device (csrc/meshproject.hip).
+        The rows are worked on in the order given: consecutive rows should be neighbours on the surface, as the rows of an atlas
+        and the vertices of an extracted mesh are.  n_tests: an int64 [1] device tensor to which the ray-triangle tests are added."""
+        from . import hip
+        from .meshproject import Projection, check_modes
+        if not (torch.is_tensor(points) and points.is_cuda and torch.is_tensor(normals) and normals.is_cuda):
+            raise RuntimeError('MeshIndex.project_rows: points and normals must be device tensors (host arrays: meshproject.host_project_rows)')
+        uniform, camera_normal = check_modes(weight, frame, 'MeshIndex.project_rows')
+        points = points.to(torch.float64).reshape(-1, 3).contiguous()
+        normals = normals.to(torch.float64).reshape(-1, 3).contiguous()
+        dev = points.device
+        place = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.array(x))).to(dev).contiguous()   # (a copy: read-only arrays)
+        views = place(views).to(torch.float64)
+        if images is not None:
+            images = place(images)
+        if masks is not None:
+            masks = place(masks)
+            masks = masks.view(torch.uint8) if masks.dtype == torch.bool else (masks if masks.dtype == torch.uint8 else (masks != 0).view(torch.uint8))
+        return Projection(*hip.project_rows(self.index, points, normals, views, images, hw=hw, masks=masks, bias=bias, cos_min=cos_min,
+                                            uniform=uniform, camera_normal=camera_normal, bits=bits, n_tests=n_tests, out=out))
+
     def face_areas_cumulative(self):
         return torch.cumsum(face_areas(self.vertices, self.faces), dim=0)
 
@@ -572,6 +597,12 @@ class _HostMesh(object):
     def occlusion(self, points, normals, table, local=True, bias=0.0, t_max=np.inf, bits=False, n_tests=None):
         from .meshocclude import host_occlusion_rows
         return host_occlusion_rows(self.vertices, self.faces, to_numpy(points), to_numpy(normals), to_numpy(table), local, bias, t_max, bits)
+
+    def project_rows(self, points, normals, images, views, hw=None, masks=None, bias=0.0, cos_min=0.0, weight='cosine', frame='raw',
+                     bits=False, n_tests=None):
+        from .meshproject import host_project_table
+        return host_project_table(self.vertices, self.faces, to_numpy(points), to_numpy(normals), None if images is None else to_numpy(images),
+                                  to_numpy(views), hw, None if masks is None else to_numpy(masks), bias, cos_min, weight, frame, bits)
 
     def contains(self, points, axis=2, vote=False):
         return _contains(self, points, axis, vote)

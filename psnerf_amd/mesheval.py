@@ -57,7 +57,7 @@ def _rng_copy(rng):
 
 
 def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=100000, rng=None, device=None, vote=False, report=False,
-                  align=None, align_options=None):
+                  align=None, align_options=None, visible_from=None):
     """Compare the mesh ``pred`` with the ground truth ``gt`` (anything with ``.vertices`` and ``.faces``) -> dict.  Device tensors, or
     ``device='cuda'``, take the device path; otherwise the numpy host path.  ``rng``: np.random.RandomState (default: the global
     np.random).
@@ -89,7 +89,14 @@ def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=10000
     ``align_options``, a dict of its keyword arguments, says otherwise) and everything above is computed for the moved prediction;
     ``alignment`` then holds the registration's result without its history (matrix, scale, rotation, translation, rms, used,
     iterations, converged, mode).  The registration draws its samples from a COPY of the rng's state, so the evaluation's own draws
-    are those of the call without ``align``."""
+    are those of the call without ``align``.
+    ``visible_from``: None (default: every output is what it was without the argument), or (camera_mats, world_mats, H, W): the
+    samples are drawn exactly as without it, and each side's samples are then KEPT iff some view sees them on their OWN mesh
+    (meshproject.project_rows without images or masks; the row normal is the sampled face's unit normal) -- a turntable rig never
+    saw the underside, where the reconstruction is free invention and the scan is often open.  accuracy, completeness, their
+    squared forms, chamfer, precision, recall, fscore, their counts and the normal consistency then run over the kept samples;
+    ``visible_fraction_pred`` and ``visible_fraction_gt`` are the kept shares, raw['pred_visible'] / raw['gt_visible'] the masks (the
+    other raw arrays keep all samples); the volume block is unchanged.  A side of which no sample is seen raises ValueError."""
     pred_m, gt_m = _prepare(pred, device, 'pred'), _prepare(gt, device, 'gt')
     alignment = None
     if align is not None:
@@ -103,6 +110,22 @@ def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=10000
     _, pred_gt_dist, pred_gt_tri = gt_m.closest_point(pred_pts)
     _, gt_pred_dist, gt_pred_tri = pred_m.closest_point(gt_pts)
     out = {'num_samples': int(num_samples)}
+    pred_n, gt_n = _unit_face_normals(pred_m), _unit_face_normals(gt_m)
+    all_dist, all_tri, all_face = (pred_gt_dist, gt_pred_dist), (pred_gt_tri, gt_pred_tri), (pred_face, gt_face)
+    visible = None
+    if visible_from is not None:
+        from . import meshproject
+        camera_mats, world_mats, height, width = visible_from
+        visible = []
+        for side, m, pts, face, unit in (('pred', pred_m, pred_pts, pred_face, pred_n), ('gt', gt_m, gt_pts, gt_face, gt_n)):
+            seen = meshproject.project_rows(m, pts, unit[face], None, camera_mats, world_mats, hw=(height, width)).n_seen > 0
+            out['visible_fraction_' + side] = int(seen.sum()) / max(int(seen.shape[0]), 1)
+            if out['visible_fraction_' + side] == 0.0:
+                raise ValueError('evaluate_mesh: no sample of %s is seen by any view of visible_from' % side)
+            visible.append(seen)
+        pred_gt_dist, gt_pred_dist = pred_gt_dist[visible[0]], gt_pred_dist[visible[1]]
+        pred_gt_tri, gt_pred_tri = pred_gt_tri[visible[0]], gt_pred_tri[visible[1]]
+        pred_face, gt_face = pred_face[visible[0]], gt_face[visible[1]]
     out['chamfer'] = float((pred_gt_dist.mean() + gt_pred_dist.mean()) / 2)
     out['accuracy'], out['completeness'] = float(pred_gt_dist.mean()), float(gt_pred_dist.mean())
     out['accuracy2'], out['completeness2'] = float((pred_gt_dist * pred_gt_dist).mean()), float((gt_pred_dist * gt_pred_dist).mean())
@@ -119,12 +142,13 @@ def evaluate_mesh(pred, gt, num_samples=10000, thresholds=None, iou_points=10000
         p, r = n_p / max(len(pred_gt_dist), 1), n_r / max(len(gt_pred_dist), 1)
         out['precision_count'][t], out['recall_count'][t], out['precision'][t], out['recall'][t] = n_p, n_r, p, r
         out['fscore'][t] = 2.0 * p * r / (p + r) if p + r > 0.0 else 0.0
-    pred_n, gt_n = _unit_face_normals(pred_m), _unit_face_normals(gt_m)
     out['normals_accuracy'] = float(abs((pred_n[pred_face] * gt_n[pred_gt_tri]).sum(1)).mean())
     out['normals_completeness'] = float(abs((gt_n[gt_face] * pred_n[gt_pred_tri]).sum(1)).mean())
     out['normals'] = (out['normals_accuracy'] + out['normals_completeness']) / 2
-    raw = {'pred_surf_pts': pred_pts, 'gt_surf_pts': gt_pts, 'pred_face': pred_face, 'gt_face': gt_face, 'pred_gt_dist': pred_gt_dist,
-           'gt_pred_dist': gt_pred_dist, 'pred_gt_tri': pred_gt_tri, 'gt_pred_tri': gt_pred_tri}
+    raw = {'pred_surf_pts': pred_pts, 'gt_surf_pts': gt_pts, 'pred_face': all_face[0], 'gt_face': all_face[1], 'pred_gt_dist': all_dist[0],
+           'gt_pred_dist': all_dist[1], 'pred_gt_tri': all_tri[0], 'gt_pred_tri': all_tri[1]}
+    if visible is not None:
+        raw['pred_visible'], raw['gt_visible'] = visible
     n_iou = int(iou_points)
     out['iou_points'] = n_iou
     if n_iou > 0:
